@@ -6,6 +6,7 @@
         bench.py --gpus N --steps K --warmup W                      # data parallel over RCCL (weak scaling); sliding window sharded
     python bench.py --mode infer | --mode sliding                   # one section only (its own JSON line)
     python bench.py --breakdown                                     # per-kernel event timing table (not a timed run)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR  # + what the last timed train step computed, DIR/<name>.npy
 
 ONE JSON line on rank 0.  ``value`` = the TRAIN throughput (the timed region the driver's clock brackets: W warm-up steps, then
 exactly K steps between barriers + synchronize, max over ranks).  The same process then measures, each bracketed the same way
@@ -197,15 +198,18 @@ def synth_volume(V, dev, z0=0, z1=None, seed=3):
     return vol.unsqueeze(-1).contiguous()
 
 
-def _timed(fn, steps, world, dev):
-    """The contract's timed region: barrier + synchronize on both sides, MAX over ranks."""
+def _timed(fn, steps, world, dev, result=None):
+    """The contract's timed region: barrier + synchronize on both sides, MAX over ranks.  ``result``: a list that receives what the last call
+    of ``fn`` returned."""
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        fn()
+        r = fn()
     torch.cuda.synchronize()
+    if result is not None:
+        result.append(r)
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
@@ -214,6 +218,32 @@ def _timed(fn, steps, world, dev):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
     return elapsed
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20
+
+
+def dump_outputs(d, whole, sampled):
+    """--dump-outputs: write each array as ``d/<name>.npy`` in float32.  ``whole`` arrays are written in full; a ``sampled`` array with more than
+    DUMP_SAMPLE elements is reduced to the elements at DUMP_SAMPLE sorted flat indices drawn with seed 0 (the same indices for the same shape in
+    every run), so that two builds given the same arguments can be compared output for output."""
+    import numpy as np
+
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in whole.items()}
+    for k, v in sampled.items():
+        v = v.detach().reshape(-1)
+        if v.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(v.numel(), DUMP_SAMPLE, replace=False))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        arrays[k] = v.float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    print(f"[bench] --dump-outputs: {', '.join(f'{k}{list(v.shape)}' for k, v in arrays.items())} ({total / 2**20:.1f} MiB) -> {d}", file=sys.stderr)
 
 
 def run_sliding(a, model, dev, rank, world, V, warmup, steps):
@@ -424,7 +454,12 @@ def main():
     ap.add_argument("--no-cfg5", action="store_true", help="skip the RCAN x4 super-resolution (cfg 5) sub-record of the single-GPU line")
     ap.add_argument("--sliding-timeout", type=float, default=240.0,
                     help="N > 1: seconds after which a hung sliding-window section is abandoned (the line is printed without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed train steps, write what the last one computed as DIR/<name>.npy (float32, rank 0): loss, logits (a fixed "
+                         "sample of 2^20 voxels), params and grads (every parameter and its gradient, flattened in named_parameters() order)")
     a = ap.parse_args()
+    if a.dump_outputs is not None and (a.arch != "resunet" or a.mode not in ("all", "train") or a.breakdown):
+        ap.error("--dump-outputs covers the timed ResUNet train step: --arch resunet, --mode all or train, no --breakdown")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -503,9 +538,13 @@ def main():
         except Exception:
             opt = torch.optim.AdamW(model.parameters(), lr=1e-3, capturable=want_graph)
 
+        last_logits = [None]                                           # the model output of the last eager step (--dump-outputs)
+
         def eager_step():
             opt.zero_grad(set_to_none=True)
-            loss = loss_fn(net(x), tgt)
+            logits = net(x)
+            last_logits[0] = logits.detach()
+            loss = loss_fn(logits, tgt)
             loss.backward()
             opt.step()
             return loss
@@ -513,6 +552,7 @@ def main():
         step = eager_step
         graphed = False
         gstep = None
+        runner = None                                                  # the step object whose .outputs hold the last step's model output
         if want_graph:
             # HIP-graph capture of the whole step (forward, loss, backward, AdamW): one launch per step instead of ~170
             try:
@@ -521,6 +561,7 @@ def main():
                 gstep = DataParallelTrainStep(net, loss_fn, opt, x, tgt) if multi else GraphedTrainStep(net, loss_fn, opt, x, tgt)
                 step = lambda: gstep()  # noqa: E731
                 graphed = True
+                runner = gstep
             except Exception as e:  # capture is an optimisation, never a requirement
                 print(f"[bench] graph capture failed ({type(e).__name__}: {e}); running eagerly", file=sys.stderr)
                 torch.cuda.synchronize()
@@ -529,6 +570,7 @@ def main():
 
                     estep = DataParallelTrainStep(net, loss_fn, opt, x, tgt, graph=False, broadcast_parameters=False)
                     step = lambda: estep()  # noqa: E731
+                    runner = estep
         feed_note = "device-resident batch, H2D excluded (the host-fed step is timed beside it: host_fed_ms_per_step)"
         inner_step, fed_step = step, None
         if not a.breakdown:
@@ -592,8 +634,15 @@ def main():
         prof = L.Profile(names=CONV_ENTRIES)
         if not graphed:
             L.lib.prof = prof
-        elapsed = _timed(step, a.steps, world, dev)
+        loss_t = []
+        elapsed = _timed(step, a.steps, world, dev, result=loss_t)
         L.lib.prof = None
+        if a.dump_outputs is not None and rank == 0:       # before anything else steps the model
+            logits_t = runner.outputs if runner is not None else last_logits[0]
+            params = [p for _, p in model.named_parameters()]
+            dump_outputs(a.dump_outputs, whole=dict(loss=loss_t[0], params=torch.cat([p.detach().reshape(-1) for p in params]),
+                                                    grads=torch.cat([p.grad.detach().reshape(-1) for p in params])),
+                         sampled=dict(logits=logits_t))
         device_resident_ms = host_fed_ms = None
         if fed_step is not None:      # the other feed, the same K steps, as a sub-field beside the headline
             other = 1e3 * _timed(inner_step if a.feed == "host" else fed_step, a.steps, world, dev) / a.steps

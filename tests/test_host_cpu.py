@@ -687,6 +687,30 @@ def test_bench_roofline_arithmetic_is_what_design_states():
     assert abs(head["hbm_frac"] - gb / 8000.0) < 1e-3 and len(top) == 2 and "families" in head
 
 
+def test_bench_dump_outputs_is_float32_sampled_and_bounded(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, whole arrays kept whole, a large output reduced to the same seeded sample in every run, and a
+    dump beyond the 64 MiB budget refused before anything is written."""
+    import bench
+
+    logits = torch.randn(2, 1, 40, 160, 170, generator=torch.Generator().manual_seed(0)).to(torch.float16)
+    assert logits.numel() > bench.DUMP_SAMPLE
+    params = torch.arange(1000, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), whole=dict(loss=torch.tensor(0.25, requires_grad=True), params=params), sampled=dict(logits=logits))
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("loss", "params", "logits")}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss"].shape == () and a["loss"] == 0.25 and np.array_equal(a["params"], params.numpy())
+    flat = logits.reshape(-1).float().numpy()
+    assert a["logits"].shape == (bench.DUMP_SAMPLE,) and np.isin(a["logits"], flat).all()
+    assert np.array_equal(a["logits"], np.load(tmp_path / "b" / "logits.npy"))
+    small = torch.randn(3, 4)
+    bench.dump_outputs(str(tmp_path / "c"), whole={}, sampled=dict(y=small))
+    assert np.array_equal(np.load(tmp_path / "c" / "y.npy"), small.reshape(-1).numpy())
+    with pytest.raises(SystemExit, match="budget"):
+        bench.dump_outputs(str(tmp_path / "big"), whole=dict(p=torch.zeros(bench.DUMP_MAX_BYTES // 4 + 1)), sampled={})
+    assert not (tmp_path / "big").exists()
+
+
 def test_channel_pad_plan_covers_every_parameter_and_is_exact_on_the_oracle():
     """engine.channel_pad_plan / pad_channels / unpad_channel_grads (feature maps that are not multiples of 16, e.g. CartoCell's [52, 68, 84]): every
     parameter of the module has a plan entry, the padded tensors have exactly the shapes of the padded architecture, un-padding is the inverse, and

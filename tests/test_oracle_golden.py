@@ -96,10 +96,16 @@ def test_net_oracle_forward_matches_reference(resunet_golden):
 def test_net_oracle_grads_match_reference(resunet_golden):
     sd, x, tgt, fm = _small(resunet_golden)
     loss, logits, grads = net_oracle.train_step_grads(sd, x, tgt, feature_maps=fm)
+    # The bias of a conv that an InstanceNorm follows has an exact gradient of 0: the fixture holds fp32 rounding noise for those (<= 5e-8 of the
+    # largest norm, and it changes with the host's CPU kernels), every other norm is >= 8e-4 of the largest.  Zero is checked as zero.
+    gmax = max(float(resunet_golden[k]) for k in resunet_golden.files if k.startswith("small/gradnorm/"))
     for k in resunet_golden.files:
         if k.startswith("small/gradnorm/"):
             name = k[len("small/gradnorm/"):]
             ref = float(resunet_golden[k])
+            if ref < 1e-6 * gmax:
+                assert grads[name].norm().item() < 1e-6 * gmax, name
+                continue
             assert abs(grads[name].norm().item() - ref) <= 1e-4 * max(ref, 1e-6) + 1e-9, name
         if k.startswith("small/grad/"):
             name = k[len("small/grad/"):]
@@ -218,7 +224,9 @@ def test_tta_group_and_transforms_match_reference(tta_golden):
 
 def test_head_activations_oracle_matches_the_reference_method(head_acts_golden):
     """Row A: oracle.loss_oracle.apply_head_activations against ``Base_Workflow.apply_model_activations`` itself (inference and
-    training, sigmoid / tanh / linear channels, one and two softmax groups, semantic "class" blocks): bit-exact."""
+    training, sigmoid / tanh / linear channels, one and two softmax groups, semantic "class" blocks): within 2 ulp.  The same torch ops are
+    bit-exact on a host whose CPU kernels match those that recorded the fixture; another host's vectorised exp and softmax sums (AVX2, AVX-512,
+    scalar, other thread counts) round some elements 1-2 ulp apart, while a wrong activation, channel order or softmax group is off by many."""
     from oracle import loss_oracle as LO
 
     g = head_acts_golden
@@ -228,7 +236,9 @@ def test_head_activations_oracle_matches_the_reference_method(head_acts_golden):
         acts = [str(a) for a in g[f"{name}/acts"]]
         x = torch.from_numpy(g[f"{name}/logits"])
         for training, key in ((False, "infer"), (True, "train")):
-            np.testing.assert_array_equal(LO.apply_head_activations(x, acts, training=training).numpy(), g[f"{name}/{key}"], err_msg=f"{name} {key}")
+            got, want = LO.apply_head_activations(x, acts, training=training).numpy(), g[f"{name}/{key}"]
+            assert got.dtype == want.dtype and got.shape == want.shape, f"{name} {key}"
+            np.testing.assert_array_max_ulp(got, want, maxulp=2)
 
 
 def test_oracle_pipeline_matches_the_reference_harness(harness_golden, resunet_golden):
