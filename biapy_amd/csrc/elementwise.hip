@@ -916,47 +916,69 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const TX* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
-// output head (1x1x1 conv to <= 4 fp32 channels, planar output) and its backward
+// output head (1x1x1 conv to <= 8 fp32 channels, planar output) and its backward
 // ------------------------------------------------------------------------------------------------
-template <typename T, int CIN>
+// COUT is a template parameter (one instance per channel count 1..8): every channel loop unrolls and a[] stays in registers.  The arithmetic is
+// that of the former run-time-Cout kernel, operation for operation (same fmaf chain per channel, same softmax order), so Cout <= 4 is bit-identical.
+template <typename T, int CIN, int COUT>
 __global__ void __launch_bounds__(256) head_fwd_kernel(const T* __restrict__ x, int x_ld, const float* __restrict__ w,
-                                                       const float* __restrict__ b, int Cout, int act, float* __restrict__ out,
+                                                       const float* __restrict__ b, int act, float* __restrict__ out,
                                                        int64_t sn, int64_t sc, int64_t vps, int N) {
   constexpr int KPL = ElemTraits<T>::KPL;
-  __shared__ float ws[4 * CIN + 4];
-  for (int i = threadIdx.x; i < Cout * CIN; i += blockDim.x) ws[i] = w[i];
-  if (threadIdx.x < Cout) ws[4 * CIN + threadIdx.x] = b ? b[threadIdx.x] : 0.f;
+  __shared__ float ws[COUT * CIN + COUT];
+  for (int i = threadIdx.x; i < COUT * CIN; i += blockDim.x) ws[i] = w[i];
+  if (threadIdx.x < COUT) ws[COUT * CIN + threadIdx.x] = b ? b[threadIdx.x] : 0.f;
   __syncthreads();
+  // per-channel codes, 4 bits each (channel 0 in the low nibble): 0 linear, 1 sigmoid, 2 tanh, 3 softmax - consecutive
+  // softmax channels form ONE group (apply_model_activations, base_workflow.py:1403-1457); a head may hold several groups.
+  // gend[co]: last channel of the softmax group that starts at co, or -1 (no group starts there)
+  int gend[COUT];
+#pragma unroll
+  for (int co = 0; co < COUT; ++co) {
+    gend[co] = -1;
+    if (((act >> (4 * co)) & 15) == 3 && (co == 0 || ((act >> (4 * (co - 1))) & 15) != 3)) {
+      int e = co;
+      while (e + 1 < COUT && ((act >> (4 * (e + 1))) & 15) == 3) ++e;
+      gend[co] = e;
+    }
+  }
   const int64_t total = (int64_t)N * vps;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    // the weights are re-read from LDS in every iteration: hoisted out of the loop (the channel loops are unrolled) they took up to
+    // COUT * CIN VGPRs - occupancy 8 -> 4 at Cout 4 and AGPR spills at CIN 32
+    asm volatile("" ::: "memory");
     float f[CIN];
 #pragma unroll
     for (int q = 0; q < CIN / KPL; ++q) unpack16<T>(*reinterpret_cast<const u32x4_t*>(x + (size_t)i * x_ld + q * KPL), f + q * KPL);
     int n = (int)(i / vps);
     int64_t v = i - (int64_t)n * vps;
-    float a[4];
-    for (int co = 0; co < Cout; ++co) {
-      a[co] = ws[4 * CIN + co];
+    float a[COUT];
+#pragma unroll
+    for (int co = 0; co < COUT; ++co) {
+      a[co] = ws[COUT * CIN + co];
 #pragma unroll
       for (int c = 0; c < CIN; ++c) a[co] = fmaf(f[c], ws[co * CIN + c], a[co]);
     }
-    // per-channel codes, 4 bits each (channel 0 in the low nibble): 0 linear, 1 sigmoid, 2 tanh, 3 softmax - consecutive
-    // softmax channels form ONE group (apply_model_activations, base_workflow.py:1403-1457)
-    for (int co = 0; co < Cout; ++co) {
+    // channel order, as before; a group's members are addressed with compile-time indices under the run-time bound e = gend[co]
+#pragma unroll
+    for (int co = 0; co < COUT; ++co) {
       const int code = (act >> (4 * co)) & 15;
       if (code == 1) a[co] = 1.f / (1.f + expf(-a[co]));
       else if (code == 2) a[co] = tanhf(a[co]);
-      else if (code == 3 && (co == 0 || ((act >> (4 * (co - 1))) & 15) != 3)) {
-        int e = co;
-        while (e + 1 < Cout && ((act >> (4 * (e + 1))) & 15) == 3) ++e;
+      else if (gend[co] >= 0) {
+        const int e = gend[co];
         float m = a[co];
-        for (int k = co + 1; k <= e; ++k) m = fmaxf(m, a[k]);
+#pragma unroll
+        for (int k = co + 1; k < COUT; ++k) if (k <= e) m = fmaxf(m, a[k]);
         float ssum = 0.f;
-        for (int k = co; k <= e; ++k) { a[k] = expf(a[k] - m); ssum += a[k]; }
-        for (int k = co; k <= e; ++k) a[k] /= ssum;
+#pragma unroll
+        for (int k = co; k < COUT; ++k) if (k <= e) { a[k] = expf(a[k] - m); ssum += a[k]; }
+#pragma unroll
+        for (int k = co; k < COUT; ++k) if (k <= e) a[k] /= ssum;
       }
     }
-    for (int co = 0; co < Cout; ++co) out[n * sn + co * sc + v] = a[co];
+#pragma unroll
+    for (int co = 0; co < COUT; ++co) out[n * sn + co * sc + v] = a[co];
   }
 }
 
@@ -1021,6 +1043,81 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const TX* __restrict__ x,
     float sum = redh[0][i] + redh[1][i] + redh[2][i] + redh[3][i];
     if (i < COUT * CIN) dw[(size_t)blockIdx.x * (COUT * CIN) + i] = sum;
     else if (db) db[(size_t)blockIdx.x * COUT + (i - COUT * CIN)] = sum;
+  }
+}
+
+// Cout 5..8: the input channels are split into 16-channel slices, one workgroup each (the accumulators of head_bwd_kernel would not fit: COUT = 4 at
+// CIN = 32 already takes 256 VGPRs).  Slice s reads every dout channel but only x[:, s] and w[:, s]; it writes dx[:, s] (no cross-slice sum) and
+// the dW[:, s] columns of its workgroup column's partial row.  Per thread: dwl[COUT][16] + o[16] + f[16].  The numerics are head_bwd_kernel's: fp32
+// dout, per-thread fmaf chains in channel order, wave shuffles, the four waves in a fixed order, then bpxred::reduce_partials over the rows.
+// 1-D grid of ncol * (Cin / 16) workgroups: the slices of one column are 8 workgroups apart - the same XCD (workgroups go round-robin over the
+// eight), dispatched together - so the halves of one x row are read, and the halves of one dx row written, at about the same time.  With the slice
+// in blockIdx.y every column of slice 0 ran before slice 1 began: each x line came from HBM twice and dx went out in half lines (Cin 32, Cout 8:
+// 775 us at 4 x 128^3).
+template <typename T, int COUT, typename TX = T>
+__global__ void __launch_bounds__(256) head_bwd_slice_kernel(const TX* __restrict__ x, int x_ld, const float* __restrict__ w, int Cin,
+                                                             const float* __restrict__ dout, int64_t sn, int64_t sc, T* __restrict__ dx,
+                                                             int dx_ld, float* __restrict__ dw, float* __restrict__ db, int64_t vps, int N) {
+  constexpr int KPL = ElemTraits<T>::KPL, CS = 16;
+  static_assert(ElemTraits<TX>::KPL == KPL, "x and dx: the same element size");
+  const int nsl = Cin / CS, ncol = (int)gridDim.x / nsl;
+  const int sl = (int)(blockIdx.x >> 3) % nsl, col = (int)(blockIdx.x / (8 * nsl)) * 8 + (int)(blockIdx.x & 7);
+  const int c0 = sl * CS;
+  __shared__ float ws[COUT * CS];
+  for (int i = threadIdx.x; i < COUT * CS; i += blockDim.x) ws[i] = w[(i / CS) * Cin + c0 + i % CS];
+  __syncthreads();
+  float dwl[COUT][CS];
+  float dbl[COUT];
+#pragma unroll
+  for (int co = 0; co < COUT; ++co) {
+    dbl[co] = 0.f;
+#pragma unroll
+    for (int c = 0; c < CS; ++c) dwl[co][c] = 0.f;
+  }
+  const int64_t total = (int64_t)N * vps;
+  for (int64_t i = (int64_t)col * blockDim.x + threadIdx.x; i < total; i += (int64_t)ncol * blockDim.x) {
+    asm volatile("" ::: "memory");   // w[:, s] from LDS in every iteration (see head_fwd_kernel): the accumulators need the registers
+    float f[CS], o[CS];
+#pragma unroll
+    for (int q = 0; q < CS / KPL; ++q) unpack16<TX>(*reinterpret_cast<const u32x4_t*>(x + (size_t)i * x_ld + c0 + q * KPL), f + q * KPL);
+#pragma unroll
+    for (int c = 0; c < CS; ++c) o[c] = 0.f;
+    int n = (int)(i / vps);
+    int64_t v = i - (int64_t)n * vps;
+    float d[COUT];
+#pragma unroll
+    for (int co = 0; co < COUT; ++co) d[co] = dout[n * sn + co * sc + v];
+#pragma unroll
+    for (int co = 0; co < COUT; ++co) {
+      dbl[co] += d[co];
+#pragma unroll
+      for (int c = 0; c < CS; ++c) { o[c] = fmaf(d[co], ws[co * CS + c], o[c]); dwl[co][c] = fmaf(d[co], f[c], dwl[co][c]); }
+    }
+#pragma unroll
+    for (int q = 0; q < CS / KPL; ++q) *reinterpret_cast<u32x4_t*>(dx + (size_t)i * dx_ld + c0 + q * KPL) = pack16<T>(o + q * KPL);
+  }
+  __shared__ float redh[4][COUT * CS + COUT];
+  const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+#pragma unroll
+  for (int co = 0; co < COUT; ++co) {
+#pragma unroll
+    for (int c = 0; c < CS; ++c) {
+      float a = dwl[co][c];
+#pragma unroll
+      for (int m = 1; m < 64; m <<= 1) a += __shfl_xor(a, m, 64);
+      if (ln == 0) redh[wv][co * CS + c] = a;
+    }
+    float a = dbl[co];
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) a += __shfl_xor(a, m, 64);
+    if (ln == 0) redh[wv][COUT * CS + co] = a;
+  }
+  __syncthreads();
+  // this slice's columns of the workgroup-column's partial row ([blocks][COUT][Cin]); the bias row ([blocks][COUT]) from slice 0
+  for (int i = threadIdx.x; i < COUT * CS + COUT; i += blockDim.x) {
+    float sum = redh[0][i] + redh[1][i] + redh[2][i] + redh[3][i];
+    if (i < COUT * CS) dw[(size_t)col * (COUT * Cin) + (i / CS) * Cin + c0 + i % CS] = sum;
+    else if (db && sl == 0) db[(size_t)col * COUT + (i - COUT * CS)] = sum;
   }
 }
 
@@ -2850,21 +2947,30 @@ extern "C" int bpx_head_fwd(int dtype, int64_t vps, int N, bpx_tensor x, const f
   BPX_CHECK(x.cs == 0, "bpx_head_fwd: chunk-planar tensors (cs != 0) are not accepted here");
   const char* fn = "bpx_head_fwd";
   BPX_CHECK(x.ptr && w_d && out_d, "%s: null pointer", fn);
-  BPX_CHECK(Cout >= 1 && Cout <= 4, "%s: Cout must be 1..4 (got %d)", fn, Cout);
+  BPX_CHECK(Cout >= 1 && Cout <= 8, "%s: Cout must be 1..8 (got %d)", fn, Cout);
   BPX_CHECK(x.C == 16 || x.C == 32, "%s: Cin must be 16 or 32 (got %d)", fn, x.C);
   int64_t total = (int64_t)N * vps;
   hipStream_t s = (hipStream_t)stream;
-#define HL(T, CIN) head_fwd_kernel<T, CIN><<<grid_for(total), 256, 0, s>>>((const T*)x.ptr, x.ld, w_d, b_d, Cout, head_act, out_d, sn, sc, vps, N)
+#define HL2(T, CIN, CO) head_fwd_kernel<T, CIN, CO><<<grid_for(total), 256, 0, s>>>((const T*)x.ptr, x.ld, w_d, b_d, head_act, out_d, sn, sc, vps, N)
+#define HL(T, CIN)                                                                                                      \
+  do {                                                                                                                  \
+    switch (Cout) {                                                                                                     \
+      case 1: HL2(T, CIN, 1); break; case 2: HL2(T, CIN, 2); break; case 3: HL2(T, CIN, 3); break; case 4: HL2(T, CIN, 4); break; \
+      case 5: HL2(T, CIN, 5); break; case 6: HL2(T, CIN, 6); break; case 7: HL2(T, CIN, 7); break; default: HL2(T, CIN, 8); break; \
+    }                                                                                                                   \
+  } while (0)
   if (dtype == BPX_BF16) { if (x.C == 16) HL(uint16_t, 16); else HL(uint16_t, 32); }
   else if (dtype == BPX_F16) { if (x.C == 16) HL(f16_t, 16); else HL(f16_t, 32); }
   else if (dtype == BPX_F32) { if (x.C == 16) HL(float, 16); else HL(float, 32); }
   else BPX_FAIL("%s: dtype must be BF16, F16 or F32", fn);
+#undef HL2
 #undef HL
   BPX_LAUNCH_CHECK(fn);
   return 0;
 }
 
-// scratch of the per-workgroup partials (the kernels launch at most 1024 workgroup columns)
+// scratch of the per-workgroup partials (the kernels launch at most 1024 workgroup columns; Cout 5..8: one row per column, its Cin / 16 slices
+// write disjoint parts of it)
 extern "C" int64_t bpx_head_bwd_workspace(int Cin, int Cout) { return (int64_t)1024 * ((int64_t)Cout * Cin + Cout) * 4; }
 extern "C" int64_t bpx_conv3d_c1_wgrad_workspace(int Cout) { return (int64_t)1024 * 28 * Cout * 4; }
 extern "C" int64_t bpx_conv1x1_c1_wgrad_workspace(int Cout) { return (int64_t)1024 * Cout * 4; }
@@ -2874,21 +2980,30 @@ extern "C" int bpx_head_bwd(int dtype, int64_t vps, int N, bpx_tensor x, const f
   BPX_CHECK(x.cs == 0 && dx.cs == 0, "bpx_head_bwd: chunk-planar tensors (cs != 0) are not accepted here");
   const char* fn = "bpx_head_bwd";
   BPX_CHECK(x.ptr && w_d && dout_d && dx.ptr && dw_d, "%s: null pointer", fn);
-  BPX_CHECK(Cout >= 1 && Cout <= 4, "%s: Cout must be 1..4 (got %d)", fn, Cout);
+  BPX_CHECK(Cout >= 1 && Cout <= 8, "%s: Cout must be 1..8 (got %d)", fn, Cout);
   BPX_CHECK(x.C == 16 || x.C == 32, "%s: Cin must be 16 or 32 (got %d)", fn, x.C);
   BPX_CHECK(ws_d && ws_bytes >= bpx_head_bwd_workspace(x.C, Cout), "%s: workspace too small (%lld bytes)", fn, (long long)ws_bytes);
   int64_t total = (int64_t)N * vps;
   int blocks = (int)std::min<int64_t>(cdiv64(total, 256), 1024);
+  if (Cout > 4 && x.C > 16) blocks = (blocks + 7) & ~7;   // the sliced kernel pairs columns 8 workgroups apart (<= 1024 still)
   hipStream_t s = (hipStream_t)stream;
   float* pw = reinterpret_cast<float*>(ws_d);
   float* pb = db_d ? pw + (size_t)blocks * Cout * x.C : nullptr;
 #define HL2(T, CIN, CO, TX) head_bwd_kernel<T, CIN, CO, TX><<<blocks, 256, 0, s>>>((const TX*)x.ptr, x.ld, w_d, Cout, dout_d, sn, sc, (T*)dx.ptr, dx.ld, pw, pb, vps, N)
-#define HL(T, CIN, TX) do { if (Cout == 1) HL2(T, CIN, 1, TX); else if (Cout == 2) HL2(T, CIN, 2, TX); else if (Cout == 3) HL2(T, CIN, 3, TX); else HL2(T, CIN, 4, TX); } while (0)
+#define HS2(T, CO, TX) head_bwd_slice_kernel<T, CO, TX><<<blocks * (x.C / 16), 256, 0, s>>>((const TX*)x.ptr, x.ld, w_d, x.C, dout_d, sn, sc, (T*)dx.ptr, dx.ld, pw, pb, vps, N)
+#define HL(T, CIN, TX)                                                                                                        \
+  do {                                                                                                                        \
+    switch (Cout) {                                                                                                           \
+      case 1: HL2(T, CIN, 1, TX); break; case 2: HL2(T, CIN, 2, TX); break; case 3: HL2(T, CIN, 3, TX); break; case 4: HL2(T, CIN, 4, TX); break; \
+      case 5: HS2(T, 5, TX); break; case 6: HS2(T, 6, TX); break; case 7: HS2(T, 7, TX); break; default: HS2(T, 8, TX); break;              \
+    }                                                                                                                         \
+  } while (0)
   if (dtype == BPX_BF16) { if (x.C == 16) HL(uint16_t, 16, uint16_t); else HL(uint16_t, 32, uint16_t); }
   else if (dtype == BPX_MIX16) { if (x.C == 16) HL(uint16_t, 16, f16_t); else HL(uint16_t, 32, f16_t); }   // x fp16, dx bf16
   else if (dtype == BPX_F32) { if (x.C == 16) HL(float, 16, float); else HL(float, 32, float); }
   else BPX_FAIL("%s: dtype must be BF16, F32 or MIX16", fn);
 #undef HL2
+#undef HS2
 #undef HL
   BPX_LAUNCH_CHECK(fn);
   // dw[co][ci] flat = one "tap", one "input channel", Cout*Cin outputs; bias rows of Cout values

@@ -98,8 +98,8 @@ class NetConfig:
             raise NotImplementedError("input channels must be 1 or a multiple of 16")
         if self.post_up not in (0, 1, 2):
             raise NotImplementedError("post up-sampling: z factor 1 or 2 (y / x factor 2)")
-        if sum(self.out_channels) > 4:
-            raise NotImplementedError("output head supports <= 4 channels")
+        if sum(self.out_channels) > 8:
+            raise NotImplementedError(f"output head supports <= 8 channels (got {sum(self.out_channels)})")
         self.depth = len(fm) - 1
         dv = [0.0] * len(fm) if self.dropout is None else [float(v) for v in list(self.dropout)]
         if len(dv) < len(fm) or any(not (0.0 <= v < 1.0) for v in dv):

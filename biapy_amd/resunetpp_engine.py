@@ -66,8 +66,8 @@ class PPConfig:
             raise NotImplementedError("ResUNet++ engine: one input channel (the first-layer kernels are the Cin = 1 ones)")
         if any(c % 16 for c in fm):
             raise NotImplementedError(f"feature_maps {fm} must be multiples of 16 (MFMA tile)")
-        if fm[0] not in (16, 32) or sum(self.out_channels) > 4:
-            raise NotImplementedError("output head supports <= 4 channels from 16 or 32 features")
+        if fm[0] not in (16, 32) or sum(self.out_channels) > 8:
+            raise NotImplementedError(f"output head supports <= 8 channels from 16 or 32 features (got {sum(self.out_channels)} from {fm[0]})")
         if self.activation not in L.ACT:
             raise NotImplementedError(f"activation={self.activation!r} is not implemented on the MI355X engine")
 

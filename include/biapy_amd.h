@@ -399,14 +399,15 @@ int64_t bpx_maxpool3d_bwd_r1_workspace(int dtype, int N, int D, int H, int W, in
 int bpx_maxpool3d_bwd_r1(int dtype, int N, int D, int H, int W, int sz, bpx_tensor x, bpx_tensor dy, bpx_tensor addend, bpx_tensor dx,
                          const float* img_d, float* dw_d, void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
 
-/* Output head: Conv3d k=1 to `Cout` (<= 4) fp32 channels (resunet.py:346-348) with the head
- * activation (base_workflow.py:1403-1457) fused: head_act holds one 4-bit code per output channel (channel 0 in the low
- * nibble): 0 = linear (logits), 1 = sigmoid, 2 = tanh, 3 = softmax, consecutive softmax channels forming one group.
+/* Output head: Conv3d k=1 to `Cout` (<= 8) fp32 channels (resunet.py:346-348) with the head
+ * activation (base_workflow.py:1403-1457) fused: head_act holds one 4-bit code per output channel, Cout <= 8 codes (channel 0
+ * in the low nibble; eight softmax channels = 0x33333333): 0 = linear (logits), 1 = sigmoid, 2 = tanh, 3 = softmax, consecutive
+ * softmax channels forming one group (a head may hold several groups, separated by other codes).  Cin is 16 or 32.
  * out is (N,Cout,D,H,W) fp32 contiguous per channel plane with arbitrary strides given in elements. */
 int bpx_head_fwd(int dtype, int64_t voxels_per_sample, int N, bpx_tensor x, const float* w_d /* [Cout][Cin] */,
                  const float* b_d, int Cout, int head_act, float* out_d, int64_t out_stride_n, int64_t out_stride_c,
                  bpx_stream_t stream);
-/* bwd: dx, dW (overwritten) and db (added to).  The parameter gradients are sums of per-workgroup partials held in ws_d
+/* bwd (Cout <= 8): dx, dW (overwritten) and db (added to).  The parameter gradients are sums of per-workgroup partials held in ws_d
  * (>= bpx_head_bwd_workspace bytes) and combined in a fixed order right after the kernel - no atomics, bit-reproducible from run to run. */
 int64_t bpx_head_bwd_workspace(int Cin, int Cout);
 int bpx_head_bwd(int dtype, int64_t voxels_per_sample, int N, bpx_tensor x, const float* w_d, int Cout,
