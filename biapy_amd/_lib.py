@@ -120,6 +120,9 @@ _SIGS = {
     "bpx_tensor_stats_tiles": ([_i64], _i),
     "bpx_norm_bwd_finalize": ([_vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
     "bpx_norm_bwd_finalize_deferred": ([_vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
+    "bpx_batchnorm_finalize": ([_vp, _i, _i, _i, _i64, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _vp], _i),
+    "bpx_batchnorm_bwd_finalize": ([_vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
+    "bpx_batchnorm_eval_records": ([_i, _vp, _i, _vp], _i),
     "bpx_gather3d_tables": ([_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp], _i),
     "bpx_scatter3d_tables": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp], _i),
     "bpx_scatter3d_regions": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp], _i),
@@ -189,6 +192,12 @@ class PackJob(C.Structure):
     """bpx_pack_job (include/biapy_amd.h)."""
     _fields_ = [("w_d", C.c_void_p), ("packed_d", C.c_void_p), ("mode", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class BnEvalJob(C.Structure):
+    """bpx_bn_eval_job (include/biapy_amd.h)."""
+    _fields_ = [("gamma_d", C.c_void_p), ("beta_d", C.c_void_p), ("running_mean_d", C.c_void_p), ("running_var_d", C.c_void_p), ("out_d", C.c_void_p),
+                ("C", C.c_int32), ("eps", C.c_float)]
 
 
 class AdamTensor(C.Structure):

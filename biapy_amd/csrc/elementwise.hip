@@ -408,6 +408,82 @@ __global__ void __launch_bounds__(512) gn_bwd_finalize_kernel(const double* __re
   }
 }
 
+// ---- BatchNorm3d: the statistics of a channel are over the whole batch ---------------------------------------------------------------------
+// One 1024-thread block per 16 channels, thread = (tile lane, channel).  A lane walks its tiles of sample 0, then of sample 1, ... into the same
+// fp64 accumulators, and lane_reduce sums the lanes in a fixed order: the batch totals have a fixed summation order (bit-reproducible).
+__device__ __forceinline__ void batch_sums(const float* __restrict__ part, int N, int tiles, int tstride, int C, int c0, double (*red)[1024]) {
+  constexpr int cb = 16, lanes = 1024 / cb;
+  const int c = threadIdx.x % cb, tl = threadIdx.x / cb;
+  double s1 = 0.0, s2 = 0.0;
+  if (c0 + c < C)
+    for (int n = 0; n < N; ++n)
+      tile_sums(part + (size_t)n * tiles * 2 * C + c0 + c, C, (tiles + tstride - 1) / tstride, (size_t)tstride * 2 * C, tl, lanes, s1, s2);
+  lane_reduce(red, cb, lanes, s1, s2);
+}
+
+__global__ void __launch_bounds__(1024) bn_finalize_kernel(const float* __restrict__ part, int N, int tiles, int tstride, int C, double inv_count,
+                                                          double unbias, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                          float momentum, float* __restrict__ rmean, float* __restrict__ rvar,
+                                                          int64_t* __restrict__ nbt, bpx_norm_rec* __restrict__ out, int out_ld, int out_off) {
+  __shared__ double red[2][1024];
+  const int c0 = blockIdx.x * 16;
+  batch_sums(part, N, tiles, tstride, C, c0, red);
+  if ((int)threadIdx.x < 16 && c0 + (int)threadIdx.x < C) {
+    const int cc = c0 + threadIdx.x;
+    const double m = red[0][threadIdx.x] * inv_count;
+    double v = red[1][threadIdx.x] * inv_count - m * m;
+    if (v < 0.0) v = 0.0;
+    const float rstd = (float)(1.0 / sqrt(v + (double)eps));
+    const float ga = gamma ? gamma[cc] : 1.f, be = beta ? beta[cc] : 0.f;
+    bpx_norm_rec r;
+    r.mean = (float)m; r.rstd = rstd; r.scale = ga * rstd; r.shift = be - (float)m * ga * rstd;
+    for (int n = 0; n < N; ++n) out[(size_t)n * out_ld + out_off + cc] = r;
+    const double mo = (double)momentum;
+    if (rmean) rmean[cc] = (float)((1.0 - mo) * (double)rmean[cc] + mo * m);
+    if (rvar) rvar[cc] = (float)((1.0 - mo) * (double)rvar[cc] + mo * v * unbias);
+  }
+  if (nbt && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;
+}
+
+// the formulas of norm_bwd_finalize_kernel (cpg = 1) with the batch totals; the coefficients are the same for every sample
+__global__ void __launch_bounds__(1024) bn_bwd_finalize_kernel(const float* __restrict__ red_part, int N, int tiles, int tstride, int C,
+                                                              double inv_count, const bpx_norm_rec* __restrict__ rec, const float* __restrict__ gamma,
+                                                              float* __restrict__ dgamma, float* __restrict__ dbeta, bpx_nbwd_coef* __restrict__ coef) {
+  __shared__ double red[2][1024];
+  const int c0 = blockIdx.x * 16;
+  batch_sums(red_part, N, tiles, tstride, C, c0, red);
+  if ((int)threadIdx.x < 16 && c0 + (int)threadIdx.x < C) {
+    const int cc = c0 + threadIdx.x;
+    const double S1 = red[0][threadIdx.x], S2 = red[1][threadIdx.x];
+    const bpx_norm_rec r = rec[cc];
+    const double ga = gamma ? (double)gamma[cc] : 1.0;
+    const double m1 = ga * S1 * inv_count, m2 = ga * S2 * inv_count, rs = (double)r.rstd;
+    bpx_nbwd_coef k;
+    k.a = (float)(ga * rs);
+    k.b = (float)(-rs * rs * m2);
+    k.c0 = (float)(-rs * m1 + rs * rs * (double)r.mean * m2);
+    k.pad = 0.f;
+    for (int n = 0; n < N; ++n) coef[(size_t)n * C + cc] = k;
+    if (dgamma) dgamma[cc] += (float)S2;
+    if (dbeta) dbeta[cc] += (float)S1;
+  }
+}
+
+// eval mode: one block per BN layer of the network (blockIdx.x = job), records from the running statistics replicated to the N rows
+struct BnEvalBatch { bpx_bn_eval_job job[64]; };
+
+__global__ void __launch_bounds__(256) bn_eval_records_kernel(const BnEvalBatch b, int N) {
+  const bpx_bn_eval_job j = b.job[blockIdx.x];
+  for (int c = threadIdx.x; c < j.C; c += blockDim.x) {
+    const float rm = j.running_mean_d[c];
+    const float rstd = (float)(1.0 / sqrt((double)j.running_var_d[c] + (double)j.eps));
+    const float ga = j.gamma_d ? j.gamma_d[c] : 1.f, be = j.beta_d ? j.beta_d[c] : 0.f;
+    bpx_norm_rec r;
+    r.mean = rm; r.rstd = rstd; r.scale = ga * rstd; r.shift = be - rm * r.scale;
+    for (int n = 0; n < N; ++n) j.out_d[(size_t)n * j.C + c] = r;
+  }
+}
+
 // TT: element type of the activation tensor t (BPX_MIX16: fp16 beside bf16 gradients), else T
 template <typename T, typename TT = T>
 __global__ void __launch_bounds__(256) norm_bwd_apply_kernel(const T* __restrict__ g, int g_ld, const TT* __restrict__ t, int t_ld,
@@ -2014,6 +2090,52 @@ extern "C" int bpx_norm_bwd_finalize_deferred(float* red_part_d, int N, int tile
                                               bpx_stream_t stream) {
   return norm_bwd_finalize_impl("bpx_norm_bwd_finalize_deferred", true, red_part_d, N, tiles, C, count_per_channel, rec_d, gamma_d, dgamma_d, dbeta_d, groups, coef_d,
                                 stream);
+}
+
+extern "C" int bpx_batchnorm_finalize(float* stats_part_d, int N, int tiles, int C, int64_t count_per_sample, const float* gamma_d, const float* beta_d,
+                                      float eps, float momentum, float* running_mean_d, float* running_var_d, int64_t* num_batches_tracked_d,
+                                      bpx_norm_rec* out_d, int out_ld, int out_off, bpx_stream_t stream) {
+  const char* fn = "bpx_batchnorm_finalize";
+  BPX_CHECK(stats_part_d && out_d, "%s: null pointer", fn);
+  BPX_CHECK(N >= 1 && tiles >= 1 && C >= 1 && out_off >= 0 && out_off + C <= out_ld, "%s: bad shape N %d tiles %d C %d columns [%d, %d) of %d", fn, N, tiles, C,
+            out_off, out_off + C, out_ld);
+  const int64_t n = (int64_t)N * count_per_sample;
+  BPX_CHECK(n > 1, "%s: expected more than 1 value per channel when training (N * voxels = %lld)", fn, (long long)n);
+  const int tstride = compact_stats(stats_part_d, N, tiles, C, (hipStream_t)stream);   // consumes the partials
+  bn_finalize_kernel<<<(unsigned)cdiv(C, 16), 1024, 0, (hipStream_t)stream>>>(stats_part_d, N, tiles, tstride, C, 1.0 / (double)n,
+                                                                               (double)n / (double)(n - 1), gamma_d, beta_d, eps, momentum, running_mean_d,
+                                                                               running_var_d, num_batches_tracked_d, out_d, out_ld, out_off);
+  BPX_LAUNCH_CHECK(fn);
+  return 0;
+}
+
+extern "C" int bpx_batchnorm_bwd_finalize(float* red_part_d, int N, int tiles, int C, int64_t count_per_sample, const bpx_norm_rec* rec_d,
+                                          const float* gamma_d, float* dgamma_d, float* dbeta_d, int running_stats, bpx_nbwd_coef* coef_d,
+                                          bpx_stream_t stream) {
+  const char* fn = "bpx_batchnorm_bwd_finalize";
+  BPX_CHECK(red_part_d && rec_d && coef_d, "%s: null pointer", fn);
+  BPX_CHECK(N >= 1 && tiles >= 1 && C >= 1 && count_per_sample >= 1, "%s: bad shape N %d tiles %d C %d", fn, N, tiles, C);
+  const int tstride = compact_stats(red_part_d, N, tiles, C, (hipStream_t)stream);     // consumes the partials
+  // running statistics (eval-mode forward): the mean and variance do not depend on the input, their terms vanish (m1 = m2 = 0: b = c0 = 0)
+  const double inv_count = running_stats ? 0.0 : 1.0 / ((double)N * (double)count_per_sample);
+  bn_bwd_finalize_kernel<<<(unsigned)cdiv(C, 16), 1024, 0, (hipStream_t)stream>>>(red_part_d, N, tiles, tstride, C, inv_count, rec_d, gamma_d, dgamma_d, dbeta_d,
+                                                                                   coef_d);
+  BPX_LAUNCH_CHECK(fn);
+  return 0;
+}
+
+extern "C" int bpx_batchnorm_eval_records(int count, const bpx_bn_eval_job* jobs, int N, bpx_stream_t stream) {
+  const char* fn = "bpx_batchnorm_eval_records";
+  BPX_CHECK(jobs && count >= 1 && count <= 64 && N >= 1, "%s: 1 ... 64 jobs and N >= 1 (got %d, N %d)", fn, count, N);
+  BnEvalBatch b{};
+  for (int i = 0; i < count; ++i) {
+    const bpx_bn_eval_job& j = jobs[i];
+    BPX_CHECK(j.running_mean_d && j.running_var_d && j.out_d && j.C >= 1, "%s: job %d: null pointer or C %d", fn, i, j.C);
+    b.job[i] = j;
+  }
+  bn_eval_records_kernel<<<(unsigned)count, 256, 0, (hipStream_t)stream>>>(b, N);
+  BPX_LAUNCH_CHECK(fn);
+  return 0;
 }
 
 

@@ -65,8 +65,16 @@ class NetConfig:
         if len(zd) != len(fm) - 1 or any(v not in (1, 2) for v in zd):
             raise NotImplementedError(f"z_down={self.z_down!r}: one value per level, each 1 or 2")
         self.z_down = tuple(zd)
-        if self.normalization not in ("in", "gn"):
-            raise NotImplementedError(f"normalization={self.normalization!r}: the MI355X engine implements 'in' (the reference default) and 'gn'")
+        if self.normalization not in ("in", "gn", "bn"):
+            raise NotImplementedError(f"normalization={self.normalization!r}: the MI355X engine implements 'in' (the reference default), 'gn' and 'bn' "
+                                      f"(sync_bn: cross-rank batch statistics are not implemented)")
+        if self.normalization == "bn":
+            # BatchNorm3d (blocks.py:2113-2127): statistics over the whole batch (bpx_batchnorm_finalize), running buffers on the device
+            why = ("2-D networks" if self.ndim != 3 else "feature maps that are not multiples of 16" if any(int(c) % 16 for c in fm)
+                   else "super-resolution stages" if self.post_up else "dropout (drop_values > 0)" if self.dropout is not None and any(float(v) > 0 for v in self.dropout)
+                   else None)
+            if why:
+                raise NotImplementedError(f"normalization='bn': {why} are not implemented with BatchNorm on the MI355X engine")
         # 'gn': torch.nn.GroupNorm(8, C) for every norm layer - what blocks.py:2122-2125 means (the reference's own call,
         # nn.GroupNorm(out_channels, num_groups=8), raises a TypeError, so there is no reference output to pin this mode to)
         self.gn_groups = 8 if self.normalization == "gn" else 0
@@ -147,6 +155,8 @@ def unlift_grads(G: Dict[str, torch.Tensor], P: Dict[str, torch.Tensor]) -> Dict
     """Gradients of lifted parameters back in the shapes of the module's parameters (centre z-tap / dropped unit extent)."""
     out = {}
     for n, p in P.items():
+        if n not in G:
+            continue
         g = G[n]
         if g.shape != p.shape:
             g = g[:, :, 1].reshape(p.shape) if p.shape[-1] == 3 else g.reshape(p.shape)
@@ -268,6 +278,20 @@ class _Stats:
         L.check(lib.bpx_groupnorm_finalize(sums.data_ptr(), B, Ct, count, gamma.data_ptr(), beta.data_ptr(), EPS, groups, rec.data_ptr(), st))
 
 
+_BN_BUFFERS = (".running_mean", ".running_var", ".num_batches_tracked")
+
+
+def bn_layers(cfg: "NetConfig") -> List[str]:
+    """Module names of every norm layer of the network (forward order); their parameters / buffers are ``name + ".weight"`` etc."""
+    prefixes = [(f"down_path.{i}", i == 0) for i in range(cfg.depth)] + [("bottleneck", False)]
+    prefixes += [(f"up_paths.0.{j}.conv_block", False) for j in range(cfg.depth)]
+    out = []
+    for prefix, first in prefixes:
+        k = block_keys(prefix, first)
+        out += ([] if first else [k["g0"][:-len(".weight")]]) + [k["g1"][:-len(".weight")]]
+    return out
+
+
 # InstanceNorm-backward finalize of the residual blocks: per-sample blocks + dgamma / dbeta with the deferred reductions (BPX_NBF_DEFER=0: the plain entry)
 _NBF = lib.bpx_norm_bwd_finalize_deferred if os.environ.get("BPX_NBF_DEFER", "1") != "0" else lib.bpx_norm_bwd_finalize
 
@@ -336,12 +360,68 @@ class ResUNetEngine:
         self._side_used = False
         self._pack_cache: Dict[Tuple[int, int, int], torch.Tensor] = {}
         self._pack_versions: Dict[Tuple[int, int, int], Tuple[int, int]] = {}
+        # BatchNorm ('bn'): batch statistics and running-buffer updates (training) or records from the running buffers (eval); the module sets
+        # bn_training (= module.training) and bn_hparams {layer name: (eps, momentum)} before every forward; without them: (1e-5, 0.1)
+        self.bn = cfg.normalization == "bn"
+        self.bn_training = True
+        self.bn_hparams: Dict[str, Tuple[float, Optional[float]]] = {}
+        self._bn_steps = 0                      # training-mode forwards: the kernels update the running buffers without a version bump
+        self._bn_cache = None
+        self._bn_eval: Optional[Dict[str, torch.Tensor]] = None      # eval-mode records of the running forward
+        self._bn_running = 0                                          # the backward's forward ran in eval mode (bpx_batchnorm_bwd_finalize)
 
     def clear_caches(self) -> None:
-        """Drop the packed / lifted weight copies kept for inference (ResUNet.train() calls this)."""
+        """Drop the packed / lifted weight copies and BatchNorm eval records kept for inference (ResUNet.train() calls this)."""
         self._pack_cache.clear()
         self._pack_versions.clear()
         self._lift_cache = None
+        self._bn_cache = None
+
+    # ---- BatchNorm ------------------------------------------------------------------------------------
+    def _bn_hp(self, layer: str) -> Tuple[float, float]:
+        eps, mom = self.bn_hparams.get(layer, (EPS, 0.1))
+        if mom is None:
+            raise NotImplementedError(f"normalization='bn': {layer} has momentum=None (cumulative moving average); the MI355X engine implements a float momentum")
+        return float(eps), float(mom)
+
+    def _norm_finalize(self, P, layer: str, part, B, tiles, C, count, rec, rec_ld, rec_off, st, lo: int = 0):
+        """Records of channels [lo, lo + C) of norm layer `layer` from one producer's partials (training mode; eval-mode BN records come from
+        _bn_eval_records).  BatchNorm updates the running buffers of those channels; num_batches_tracked with the call that covers channel 0."""
+        g, b = P[layer + ".weight"], P[layer + ".bias"]
+        if not self.bn:
+            _Stats.finalize(part, B, tiles, C, count, g[lo:lo + C], b[lo:lo + C], rec, rec_ld, rec_off, st, self.cfg.gn_groups)
+            return
+        eps, mom = self._bn_hp(layer)
+        rm, rv, nbt = (P.get(layer + s) for s in _BN_BUFFERS)
+        L.check(lib.bpx_batchnorm_finalize(part.data_ptr(), B, tiles, C, count, g[lo:].data_ptr(), b[lo:].data_ptr(), eps, mom,
+                                           None if rm is None else rm[lo:].data_ptr(), None if rv is None else rv[lo:].data_ptr(),
+                                           L.ptr(nbt) if lo == 0 else None, rec.data_ptr(), rec_ld, rec_off, st))
+
+    def _bn_eval_records(self, P, B, dev, cache: bool) -> Dict[str, torch.Tensor]:
+        """{layer: (B, C, 4) records} of every BN layer from the running buffers, ONE launch (bpx_batchnorm_eval_records).  Kept while the
+        parameters and buffers keep their storage and version, weights_epoch() and the count of training-mode forwards (load_state_dict copies in
+        place: a new version) and the layers' eps; a captured forward computes them inside the graph (cache = False), so a replay reads the buffers
+        of its time."""
+        layers = bn_layers(self.cfg)
+        ts = [P[n + s] for n in layers for s in (".weight", ".bias", ".running_mean", ".running_var")]
+        eps = [float(self.bn_hparams.get(n, (EPS, None))[0]) for n in layers]
+        key = (B, dev, _WEIGHTS_EPOCH[0], self._bn_steps, tuple(eps)) + tuple((t.data_ptr(), t._version) for t in ts)
+        if cache and self._bn_cache is not None and self._bn_cache[0] == key:
+            return self._bn_cache[1]
+        if any(t.dtype != torch.float32 or not t.is_contiguous() for t in ts):
+            raise TypeError("normalization='bn': weight, bias, running_mean and running_var must be contiguous float32 tensors")
+        Cs = [P[n + ".weight"].numel() for n in layers]
+        buf = torch.empty((B * sum(Cs), 4), dtype=torch.float32, device=dev)
+        jobs = (L.BnEvalJob * len(layers))()
+        recs, o = {}, 0
+        for q, (n, c) in enumerate(zip(layers, Cs)):
+            recs[n] = buf[o:o + B * c].view(B, c, 4)
+            jobs[q] = L.BnEvalJob(P[n + ".weight"].data_ptr(), P[n + ".bias"].data_ptr(), P[n + ".running_mean"].data_ptr(),
+                                  P[n + ".running_var"].data_ptr(), recs[n].data_ptr(), c, eps[q])
+            o += B * c
+        L.check(lib.bpx_batchnorm_eval_records(len(layers), C.cast(jobs, C.c_void_p), B, L.stream_ptr()))
+        self._bn_cache = (key, recs) if cache else None
+        return recs
 
     # ---- weight-gradient side stream ------------------------------------------------------------------
     # The wgrad kernels only produce parameter gradients; nothing on the dgrad chain waits for them.  They run on a second
@@ -535,21 +615,26 @@ class ResUNetEngine:
         k = blk.keys
         vox = D * H * W
         C1 = blk.cout
+        stats = self._bn_eval is None          # eval-mode BN takes its records from the running buffers: the producers get null statistics pointers
         # ---- conv1 -> h (+ stats) ----------------------------------------------------------------
         if blk.first and self.cfg.in_ch == 1:
             tiles = lib.bpx_conv3d_c1_stats_tiles(D, H, W)
-            part = _Stats.alloc(B, tiles, C1, dev)
+            part = _Stats.alloc(B, tiles, C1, dev) if stats else None
             L.check(lib.bpx_conv3d_c1_fwd(self.dt, B, D, H, W, img.data_ptr(), P[k["w1"]].data_ptr(), P[k["b1"]].data_ptr(),
-                                          L.tview(blk.h), part.data_ptr(), st))
+                                          L.tview(blk.h), L.ptr(part), st))
         else:
             tiles = lib.bpx_conv3d_stats_tiles(self.dt, B, D, H, W, C1)
-            part = _Stats.alloc(B, tiles, C1, dev)
+            part = _Stats.alloc(B, tiles, C1, dev) if stats else None
             wp = self._pack(P[k["w1"]], L.PK_K3, blk.cin, C1, cache)
             L.check(lib.bpx_conv3d_fwd(self.dt, B, D, H, W, L.tview(blk.x, blk.x_c0, blk.cin),
                                        L.ptr(blk.rec_x), self.act if blk.rec_x is not None else 0, wp.data_ptr(), P[k["b1"]].data_ptr(),
-                                       L.NULL_T, None, None, L.tview(blk.h), part.data_ptr(), st))
-        blk.rec_h = _recs(B, C1, dev)
-        _Stats.finalize(part, B, tiles, C1, vox, P[k["g1"]], P[k["be1"]], blk.rec_h, C1, 0, st, self.cfg.gn_groups)
+                                       L.NULL_T, None, None, L.tview(blk.h), L.ptr(part), st))
+        n1 = k["g1"][:-len(".weight")]
+        if self._bn_eval is not None:
+            blk.rec_h = self._bn_eval[n1]
+        else:
+            blk.rec_h = _recs(B, C1, dev)
+            self._norm_finalize(P, n1, part, B, tiles, C1, vox, blk.rec_h, C1, 0, st)
         # ---- dropout: conv2 reads the materialised, masked activation instead of forming it in its prologue -------
         x2, rec2, act2 = L.tview(blk.h), blk.rec_h.data_ptr(), self.act
         if blk.drop_p > 0.0 and self.drop_active:
@@ -574,7 +659,7 @@ class ResUNetEngine:
         if pool is not None:
             L.check(lib.bpx_conv3d_fwd_pool(self.dt, B, D, H, W, x2, rec2, act2, wp2.data_ptr(),
                                             P[k["b2"]].data_ptr(), sc, wsc_ptr, P[k["bsc"]].data_ptr(),
-                                            L.tview(blk.out, blk.out_c0, C1), L.ptr(part2), pool[0], L.tview(pool[1]), pool[2].data_ptr(), st))
+                                            L.tview(blk.out, blk.out_c0, C1), L.ptr(part2), pool[0], L.tview(pool[1]), L.ptr(pool[2]), st))
         else:
             L.check(lib.bpx_conv3d_fwd(self.dt, B, D, H, W, x2, rec2, act2, wp2.data_ptr(),
                                        P[k["b2"]].data_ptr(), sc, wsc_ptr, P[k["bsc"]].data_ptr(),
@@ -604,6 +689,12 @@ class ResUNetEngine:
             # a captured forward must contain its own pack kernels: operands cached during the warm-up would freeze the
             # weights of every later replay at their capture-time values (graphs.GraphedInference)
             cache_weights = False
+        self._bn_eval = None
+        if self.bn:
+            if not self.bn_training:
+                self._bn_eval = self._bn_eval_records(P, x.shape[0], x.device, cache_weights)
+            else:
+                self._bn_steps += 1
         plan = self._pad_plan
         if plan is not None or any(needs_lift(w) for w in P.values()):
             # 2D / anisotropic levels: zero-padded 3x3x3 weights.  Inference keeps the lifted copies while the parameters
@@ -649,6 +740,9 @@ class ResUNetEngine:
         S = [(D0, H0, W0)]
         for i in range(Lv):
             S.append((S[i][0] // cfg.z_down[i], S[i][1] // 2, S[i][2] // 2))
+        if self.bn and self.bn_training and B * S[Lv][0] * S[Lv][1] * S[Lv][2] == 1:
+            # what torch.nn.functional.batch_norm raises (at the bottleneck's first norm, the first with one value per channel); up front, not from a kernel
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size torch.Size([{B}, {fm[Lv - 1]}, 1, 1, 1])")
 
         def buf(i, C):
             return torch.empty((B,) + S[i] + (C,), dtype=T, device=dev)
@@ -671,21 +765,24 @@ class ResUNetEngine:
             k_ = blk.keys
             fused = bool(lib.bpx_conv3d_fwd_pool_supported(self.dt, B, D, H, W, fm[i], cat[i].shape[-1], fm[i])) and all(
                 P[k_[q]].data_ptr() % 16 == 0 for q in ("b2", "bsc", "wsc"))
+            stats = self._bn_eval is None
             if fused:
                 ptiles = lib.bpx_conv3d_stats_tiles(self.dt, B, D, H, W, fm[i])
-                ppart = _Stats.alloc(B, ptiles, fm[i], dev)
-                part, tiles = self._res_block_fwd(P, blk, B, img, st, cache_weights, want_out_stats=True, pool=(cfg.z_down[i], pooled, ppart))
+                ppart = _Stats.alloc(B, ptiles, fm[i], dev) if stats else None
+                part, tiles = self._res_block_fwd(P, blk, B, img, st, cache_weights, want_out_stats=stats, pool=(cfg.z_down[i], pooled, ppart))
             else:
-                part, tiles = self._res_block_fwd(P, blk, B, img, st, cache_weights, want_out_stats=True)
+                part, tiles = self._res_block_fwd(P, blk, B, img, st, cache_weights, want_out_stats=stats)
                 ptiles = lib.bpx_maxpool3d_stats_tiles(self.dt, D, H, W, cfg.z_down[i], fm[i])
-                ppart = _Stats.alloc(B, ptiles, fm[i], dev)
-                L.check(lib.bpx_maxpool3d_fwd(self.dt, B, D, H, W, cfg.z_down[i], L.tview(cat[i], fm[i + 1], fm[i]), L.tview(pooled), ppart.data_ptr(), st))
+                ppart = _Stats.alloc(B, ptiles, fm[i], dev) if stats else None
+                L.check(lib.bpx_maxpool3d_fwd(self.dt, B, D, H, W, cfg.z_down[i], L.tview(cat[i], fm[i + 1], fm[i]), L.tview(pooled), L.ptr(ppart), st))
             out_stats.append((part, tiles))
             blocks.append(blk)
             nxt = "bottleneck" if i == Lv - 1 else f"down_path.{i + 1}"
-            rec = _recs(B, fm[i], dev)
-            _Stats.finalize(ppart, B, ptiles, fm[i], S[i + 1][0] * S[i + 1][1] * S[i + 1][2], P[f"{nxt}.block.0.weight"],
-                            P[f"{nxt}.block.0.bias"], rec, fm[i], 0, st, cfg.gn_groups)
+            if self._bn_eval is not None:
+                rec = self._bn_eval[f"{nxt}.block.0"]
+            else:
+                rec = _recs(B, fm[i], dev)
+                self._norm_finalize(P, f"{nxt}.block.0", ppart, B, ptiles, fm[i], S[i + 1][0] * S[i + 1][1] * S[i + 1][2], rec, fm[i], 0, st)
             pools.append(pooled)
             cur, cur_rec = pooled, rec
         # ---------------- bottleneck ----------------------------------------------------------------
@@ -703,16 +800,21 @@ class ResUNetEngine:
             szl = cfg.z_down[i]
             wp = self._pack(P[wk], L.PK_CT if szl == 2 else L.PK_CT4, Cup, Cup, cache_weights)
             utiles = lib.bpx_convT3d_stats_tiles(Dl, Hl, Wl, szl)
-            upart = _Stats.alloc(B, utiles, Cup, dev)
+            upart = _Stats.alloc(B, utiles, Cup, dev) if self._bn_eval is None else None
             L.check(lib.bpx_convT3d_k2s2_fwd(self.dt, B, Dl, Hl, Wl, szl, L.tview(dec_in), wp.data_ptr(), P[bk].data_ptr(),
-                                             L.tview(cat[i], 0, Cup), upart.data_ptr(), st))
+                                             L.tview(cat[i], 0, Cup), L.ptr(upart), st))
             Ccat = Cup + fm[i]
             pre = f"up_paths.0.{j}.conv_block"
             vox = S[i][0] * S[i][1] * S[i][2]
-            rec = _recs(B, Ccat, dev)
+            rec = _recs(B, Ccat, dev) if self._bn_eval is None else self._bn_eval[f"{pre}.block.0"]
             g0, be0 = P[f"{pre}.block.0.weight"], P[f"{pre}.block.0.bias"]
             spart, stiles = out_stats[i]
-            if cfg.gn_groups:
+            if self._bn_eval is not None:
+                pass                                    # eval-mode BN: the records of the running buffers (above)
+            elif self.bn:      # the two column ranges of torch.cat([up, skip], 1) and of the running buffers ([:Cup], [Cup:])
+                self._norm_finalize(P, f"{pre}.block.0", upart, B, utiles, Cup, vox, rec, Ccat, 0, st)
+                self._norm_finalize(P, f"{pre}.block.0", spart, B, stiles, fm[i], vox, rec, Ccat, Cup, st, lo=Cup)
+            elif cfg.gn_groups:
                 _Stats.finalize_cat([(upart, utiles, Cup), (spart, stiles, fm[i])], B, vox, g0, be0, rec, cfg.gn_groups, st)
             else:
                 _Stats.finalize(upart, B, utiles, Cup, vox, g0[:Cup], be0[:Cup], rec, Ccat, 0, st)
@@ -766,7 +868,7 @@ class ResUNetEngine:
         ctx = None
         if save:
             ctx = dict(B=B, S=S, So=So, img=img, x_ndhwc=x_ndhwc, blocks=blocks, cat=cat, pools=pools, ups=ups, feat=feat, dec_out=dec_in, hw=hw,
-                       Pw=(P if P is not P_orig else None), want_dx=want_dx, wide_head=wide)
+                       Pw=(P if P is not P_orig else None), want_dx=want_dx, wide_head=wide, bn_running=self._bn_eval is not None)
         return logits, ctx
 
     # ------------------------------------------------------------------------------------------
@@ -823,8 +925,12 @@ class ResUNetEngine:
         coef = torch.empty((B, C1, 4), dtype=torch.float32, device=dev)
         # (deferred form: dgamma / dbeta arrive with the flush of the weight-gradient reductions; `red` holds their per-sample terms until then)
         self._keep.append(red)
-        L.check(_NBF(red.data_ptr(), B, tiles, C1, vox, blk.rec_h.data_ptr(), P[k["g1"]].data_ptr(),
-                                                   G[k["g1"]].data_ptr(), G[k["be1"]].data_ptr(), self.cfg.gn_groups or C1, coef.data_ptr(), st))
+        if self.bn:
+            L.check(lib.bpx_batchnorm_bwd_finalize(red.data_ptr(), B, tiles, C1, vox, blk.rec_h.data_ptr(), P[k["g1"]].data_ptr(), G[k["g1"]].data_ptr(),
+                                                   G[k["be1"]].data_ptr(), self._bn_running, coef.data_ptr(), st))
+        else:
+            L.check(_NBF(red.data_ptr(), B, tiles, C1, vox, blk.rec_h.data_ptr(), P[k["g1"]].data_ptr(),
+                         G[k["g1"]].data_ptr(), G[k["be1"]].data_ptr(), self.cfg.gn_groups or C1, coef.data_ptr(), st))
         first_c1 = blk.first and self.cfg.in_ch == 1
         if first_c1 and lib.bpx_conv3d_c1_wgrad_nb_supported(self.bdt, W) and os.environ.get("BPX_C1_NB", "1") != "0":
             # the first layer has no input gradient: its weight gradient is the only reader of dH = a * g1 + b * h + c0, which is therefore formed
@@ -865,7 +971,10 @@ class ResUNetEngine:
                                              red0.data_ptr(), st))
             coef0 = torch.empty((B, Cx, 4), dtype=torch.float32, device=dev)
             gng = self.cfg.gn_groups
-            if gng and (Cx // gng) not in (1, 2, 4, 8, 16, 32, 64):
+            if self.bn:
+                L.check(lib.bpx_batchnorm_bwd_finalize(red0.data_ptr(), B, tiles0, Cx, vox, blk.rec_x.data_ptr(), P[k["g0"]].data_ptr(), G[k["g0"]].data_ptr(),
+                                                       G[k["be0"]].data_ptr(), self._bn_running, coef0.data_ptr(), st))
+            elif gng and (Cx // gng) not in (1, 2, 4, 8, 16, 32, 64):
                 # the concatenated decoder input: 6 / 12 / 24 / 48 channels per group -> per-channel totals, then the general group kernel
                 sums0 = torch.empty((B, Cx, 2), dtype=torch.float64, device=dev)
                 L.check(lib.bpx_norm_channel_sums(red0.data_ptr(), B, tiles0, Cx, sums0.data_ptr(), Cx, 0, st))
@@ -906,6 +1015,7 @@ class ResUNetEngine:
         if self._deferred:
             L.check(lib.bpx_wgrad_defer_begin())
         Pw = ctx.get("Pw")
+        self._bn_running = int(ctx.get("bn_running", False))      # BatchNorm: the forward normalised with the running statistics (eval mode)
         try:
             G = self._backward(P if Pw is None else Pw, ctx, dlogits)
         finally:
@@ -933,7 +1043,7 @@ class ResUNetEngine:
         dev = dlogits.device
         st = L.stream_ptr()
         T = self.gdtype
-        names = list(P.keys())
+        names = [n for n in P if not n.endswith(_BN_BUFFERS)]       # BatchNorm running buffers have no gradient
         sizes = [P[n].numel() for n in names]
         flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
         self.last_flat_grad = flat

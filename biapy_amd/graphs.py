@@ -185,6 +185,10 @@ class DataParallelTrainStep:
 
     def __init__(self, model: torch.nn.Module, loss_fn: Callable, optimizer: torch.optim.Optimizer, x: torch.Tensor,
                  target: torch.Tensor, group=None, graph: bool = True, warmup: int = 3, broadcast_parameters: bool = True, overlap="auto"):
+        inner = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
+        if getattr(getattr(inner, "cfg", None), "normalization", None) == "bn":
+            raise NotImplementedError("DataParallelTrainStep: normalization='bn' needs its running buffers broadcast across ranks, which this step does "
+                                      "not do; use DistributedDataParallel (broadcast_buffers=True)")
         self.model, self.loss_fn, self.opt, self.group = model, loss_fn, optimizer, group
         self.overlapped = False
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1

@@ -22,7 +22,10 @@ Round 4: every per-element block activation of ``get_activation`` (blocks.py:197
 softplus, linear / none), the classification head (``"class"`` in ``output_channel_info``: ``forward`` returns ``{"pred", "class"}``) and
 ``explicit_activations`` (resunet.py:408-443) are built and pinned to fixtures generated from the reference class.
 
-Configurations outside the accelerated hot path (normalisation other than "in" / "gn", larger_io, separated decoders, contrastive head,
+``normalization="bn"`` builds ``nn.BatchNorm3d`` layers (running buffers in the state_dict); ``model.train()`` / ``model.eval()`` select batch or
+running statistics.  Not with 2D networks, widths that are not multiples of 16, super-resolution or dropout.
+
+Configurations outside the accelerated hot path (normalisation other than "in" / "gn" / "bn", larger_io, separated decoders, contrastive head,
 ``upsample_layer="upsampling"``, YX_DOWN != 2, Z_DOWN outside {1,2}, nconvs != 2, pre-activation order, softmax as a BLOCK
 activation) raise ``NotImplementedError`` at construction: they stay on the reference's plain-PyTorch classes, selected by the same registry.
 """
@@ -54,6 +57,8 @@ def _conv(ndim: int):
 def _inorm(ndim: int, c: int, kind: str = "in") -> nn.Module:
     if kind == "gn":          # what blocks.py:2122-2125 means by 'gn' (its own call raises): GroupNorm(8, C); same parameter names and shapes
         return nn.GroupNorm(8, c)
+    if kind == "bn":          # blocks.py:2113-2127: affine, running statistics (its state_dict adds running_mean / running_var / num_batches_tracked)
+        return nn.BatchNorm3d(c, eps=1e-5, momentum=0.1)
     return (nn.InstanceNorm2d if ndim == 2 else nn.InstanceNorm3d)(c, affine=True, momentum=0.1)
 
 
@@ -97,6 +102,7 @@ class ResUpBlock(nn.Module):
 class _ResUNetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, engine: ResUNetEngine, names: List[str], *params):
+        # params: the parameters, then any BatchNorm running buffers (updated in place by a training-mode forward; no gradient)
         P = dict(zip(names, (p.detach() for p in params)))
         need = any(p.requires_grad for p in params) and torch.is_grad_enabled()
         logits, saved = engine.forward(P, x.detach(), head_act=0, save=True)
@@ -109,7 +115,7 @@ class _ResUNetFn(torch.autograd.Function):
     def backward(ctx, dlogits):
         G = ctx.engine.backward(ctx.params, ctx.saved, dlogits)
         ctx.saved = None
-        return (None, None, None) + tuple(G[n] for n in ctx.names)
+        return (None, None, None) + tuple(G.get(n) for n in ctx.names)
 
 
 _SR_W1, _SR_WSC = "down_path.0.block.0.block.0.weight", "down_path.0.shortcut.0.weight"
@@ -261,6 +267,8 @@ class ResUNet(nn.Module):
                 raise ValueError(f"upsampling_position={upsampling_position!r}")
         if conv_block_order != "conv_norm_act" or list(conv_layers)[: depth + 1] != [2] * (depth + 1):
             unsupported("conv_block_order != 'conv_norm_act' or conv_layers != 2")
+        if normalization == "bn" and self.sr_pre:
+            unsupported("normalization='bn' with a super-resolution stage")
         dv = [float(d) for d in drop_values]
         if len(dv) < depth + 1 and any(d > 0 for d in dv):
             raise ValueError("'drop_values' needs one value per level and one for the bottleneck")
@@ -362,7 +370,18 @@ class ResUNet(nn.Module):
                 self._engines[self.compute_dtype] = ResUNetEngine(self.cfg, self.compute_dtype)
             self._engine = self._engines[self.compute_dtype]
         self._engine.drop_active = bool(self.training)      # nn.Dropout semantics: masks in training mode only (blocks.py:163)
+        if self.cfg.normalization == "bn":                  # nn.BatchNorm3d semantics: batch statistics in training mode, running ones in eval mode
+            hp = {n: (m.eps, m.momentum) for n, m in self.named_modules() if isinstance(m, nn.BatchNorm3d)}
+            bad = [n for n, (_, mo) in hp.items() if mo is None]
+            if bad:
+                raise NotImplementedError(f"normalization='bn': momentum=None (cumulative moving average) of {bad[0]} is not implemented on the MI355X engine")
+            self._engine.bn_training = bool(self.training)
+            self._engine.bn_hparams = hp
         return self._engine
+
+    def _bn_buffers(self):
+        """The BatchNorm running buffers by state_dict name (empty for 'in' / 'gn'); the engine reads and updates them in place."""
+        return {n: b for n, b in self.named_buffers()} if self.cfg.normalization == "bn" else {}
 
     def train(self, mode: bool = True):
         """Entering training mode drops the packed / lifted weight copies the inference path keeps (they are also keyed by
@@ -391,10 +410,15 @@ class ResUNet(nn.Module):
             return logits
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             gr = getattr(self, "_graphs", None)
-            if gr is not None and tuple(x.shape) == gr["shape"] and x.stride() == gr["stride"] and not torch.cuda.is_current_stream_capturing():
+            # a BatchNorm graph is bound to the mode it was captured in (batch statistics and buffer updates, or running statistics): replayed in
+            # that mode only
+            if (gr is not None and tuple(x.shape) == gr["shape"] and x.stride() == gr["stride"] and not torch.cuda.is_current_stream_capturing()
+                    and (self.cfg.normalization != "bn" or gr["training"] == self.training)):
                 return self._finish_outputs(_GraphedResUNetFn.apply(x, gr, *params))
-            return self._finish_outputs(_ResUNetFn.apply(x, self.engine(), names, *params))
+            bufs = self._bn_buffers()
+            return self._finish_outputs(_ResUNetFn.apply(x, self.engine(), names + list(bufs), *params, *bufs.values()))
         P = {n: p.detach() for n, p in zip(names, params)}
+        P.update(self._bn_buffers())
         logits, _ = self.engine().forward(P, x, head_act=0, save=False, cache_weights=not self.training)
         return self._finish_outputs(logits)
 
@@ -446,6 +470,9 @@ class ResUNet(nn.Module):
         names, params = self._named()
         eng = self.engine()
         P = {n: p.detach() for n, p in zip(names, params)}
+        P.update(self._bn_buffers())      # BatchNorm: the captured forward updates the module's own running buffers on every replay
+        # ... but capturing is not training: the warm-up forwards' buffer updates are undone below
+        bufs = {n: b.clone() for n, b in self._bn_buffers().items()}
         xs = x_example.detach().to(torch.float32).clone()
 
         def once():
@@ -468,8 +495,11 @@ class ResUNet(nn.Module):
         with torch.cuda.graph(gb, pool=gf.pool(), capture_error_mode="thread_local"):
             grads = eng.backward(P, saved, dl)
         torch.cuda.synchronize()
+        with torch.no_grad():
+            for n, b in bufs.items():
+                P[n].copy_(b)
         self._graphs = dict(shape=tuple(xs.shape), stride=xs.stride(), x=xs, logits=logits, saved=saved, dlogits=dl, grads=grads,
-                            names=names, fwd=gf, bwd=gb)
+                            names=names, fwd=gf, bwd=gb, training=self.training)
 
     def release_graphs(self) -> None:
         self._graphs = None
@@ -499,6 +529,7 @@ class ResUNet(nn.Module):
         P = {n: p.detach() for n, p in zip(names, params)}
         if self.sr_pre:
             return _sr_pre_forward(self.engine(), P, x.to(torch.float32), self.sr_pre, self.head_activation_code(head_activations), False)[0]
+        P.update(self._bn_buffers())
         out, _ = self.engine().forward(P, x.to(torch.float32), head_act=self.head_activation_code(head_activations), save=False,
                                        cache_weights=True)
         return out

@@ -112,6 +112,8 @@ class U_Net(nn.Module):
             unsupported("dropout")
         if explicit_activations or "class" in output_channel_info:
             unsupported("explicit head activations / classification head")
+        if normalization == "bn":
+            unsupported("normalization='bn' (BatchNorm is implemented for the ResUNet)")
         self.depth, self.ndim = depth, ndim
         self.z_down, self.yx_down = z_down, yx_down
         self.output_channels = output_channels

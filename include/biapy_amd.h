@@ -330,6 +330,40 @@ int bpx_norm_bwd_finalize(float* red_part_d /* consumed, see bpx_norm_finalize *
 int bpx_norm_bwd_finalize_deferred(float* red_part_d /* consumed, see bpx_norm_finalize */, int N, int tiles, int C, int64_t count_per_channel,
                           const bpx_norm_rec* rec_d, const float* gamma_d, float* dgamma_d, float* dbeta_d, int groups,
                           bpx_nbwd_coef* coef_d, bpx_stream_t stream);
+/* BatchNorm3d(C, eps, momentum, affine, track_running_stats) (blocks.py:2113-2127 'bn'), in the record / coefficient layouts above, so that the
+ * conv prologues, epilogues and the InstanceNorm backward kernels consume it unchanged.  Statistics are over all N samples x voxels, summed in
+ * fp64 in a fixed order (samples in index order, then the tile lanes): two identical calls give identical bits.  No atomics, no host sync.
+ *   bpx_batchnorm_finalize    : training-mode forward.  stats_part_d [N][tiles][2][C] as in bpx_norm_finalize (CONSUMED).  mean = S1/n,
+ *                               var = S2/n - mean^2 (biased, clamped at 0), n = N * count_per_sample; the same record goes to all N rows
+ *                               out_d[n*out_ld + out_off + c].  Non-null running buffers (pointers at the channel offset of this call) are
+ *                               updated in place: rm = (1-m) rm + m mean, rv = (1-m) rv + m var n/(n-1); num_batches_tracked_d (int64, may be
+ *                               null: pass it to ONE call per layer) += 1.  n must be > 1.
+ *   bpx_batchnorm_bwd_finalize: training-mode backward.  red_part_d [N][tiles][2][C] partials of {S1 = sum g, S2 = sum g*xhat} (CONSUMED) as
+ *                               the dgrad / fused-backward / norm-act-dropout kernels write them; rec_d the forward's records (row 0 is read).
+ *                               coef[n*C + c] = {a, b, c0} of bpx_norm_bwd_finalize with the batch totals and 1/n over N * count_per_sample, the
+ *                               same for every n; dgamma[c] += sum S2, dbeta[c] += sum S1 (dgamma / dbeta may be null).  It needs every sample
+ *                               for the coefficients anyway, so dgamma / dbeta are written by the same thread: there is no deferred form.
+ *                               running_stats != 0: the backward of an eval-mode forward (records from bpx_batchnorm_eval_records): the
+ *                               statistics are constants, so a = gamma*rstd and b = c0 = 0 (dgamma / dbeta as above).
+ *   bpx_batchnorm_eval_records: eval mode, every BN layer of a network in ONE launch (count <= 64 jobs, `jobs` is a HOST array copied into the
+ *                               kernel arguments): out_d[n*C + c] = {rm, rstd, scale, shift} for n < N with rstd = 1/sqrt(rv + eps),
+ *                               scale = gamma * rstd, shift = beta - rm * scale. */
+int bpx_batchnorm_finalize(float* stats_part_d, int N, int tiles, int C, int64_t count_per_sample, const float* gamma_d, const float* beta_d,
+                           float eps, float momentum, float* running_mean_d, float* running_var_d, int64_t* num_batches_tracked_d,
+                           bpx_norm_rec* out_d, int out_ld, int out_off, bpx_stream_t stream);
+int bpx_batchnorm_bwd_finalize(float* red_part_d, int N, int tiles, int C, int64_t count_per_sample, const bpx_norm_rec* rec_d,
+                               const float* gamma_d, float* dgamma_d, float* dbeta_d, int running_stats, bpx_nbwd_coef* coef_d,
+                               bpx_stream_t stream);
+typedef struct bpx_bn_eval_job {
+  const float* gamma_d;
+  const float* beta_d;
+  const float* running_mean_d;
+  const float* running_var_d;
+  bpx_norm_rec* out_d;   /* N x C records */
+  int32_t C;
+  float eps;
+} bpx_bn_eval_job;
+int bpx_batchnorm_eval_records(int count, const bpx_bn_eval_job* jobs, int N, bpx_stream_t stream);
 /* dx = a*g + b*t + c0 (+ addend): applies the coefficients above elementwise. dx may alias g. */
 int bpx_norm_bwd_apply(int dtype, int N, int64_t voxels, bpx_tensor g, bpx_tensor t, const bpx_nbwd_coef* coef_d,
                        bpx_tensor addend, bpx_tensor dx, bpx_stream_t stream);
