@@ -1,20 +1,25 @@
 #!/usr/bin/env python
 """bench.py - voxels/s of the 3D ResUNet hot path on MI355X (BASELINE.json metric: "train+infer" at 1/2/4/8 GPUs).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3                 # train step (fwd+bwd+AdamW) of cfg 2, then inference + cfg 3
+    python bench.py --gpus 1 --steps 10 --warmup 3                 # train step (fwd+bwd+AdamW) of cfg 2 alone: the headline line
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full          # the same, then every other measurement and check listed below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W                      # data parallel over RCCL (weak scaling); sliding window sharded
+        bench.py --gpus N --steps K --warmup W [--full]             # data parallel over RCCL (weak scaling); sliding window sharded
     python bench.py --mode infer | --mode sliding                   # one section only (its own JSON line)
     python bench.py --breakdown                                     # per-kernel event timing table (not a timed run)
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR  # + what the last timed train step computed, DIR/<name>.npy
 
-ONE JSON line on rank 0.  ``value`` = the TRAIN throughput (the timed region the driver's clock brackets: W warm-up steps, then
-exactly K steps between barriers + synchronize, max over ranks).  The same process then measures, each bracketed the same way
-and reported as a sub-record with its own roofline entry:
+ONE JSON line on rank 0.  ``value`` = the TRAIN throughput (the timed region: W warm-up steps, then exactly K steps between
+barriers + synchronize, max over ranks).  Without --full that is all a run does after setting up: time the K steps, write
+--dump-outputs, print the line.  With --full the same process first times the other feed (host_fed_ms_per_step), re-runs the step's
+launches eagerly for the ``roofline`` entries and, at N > 1, checks the ranks' gradients agree; then it measures, each bracketed the
+same way and reported as a sub-record with its own roofline entry:
   ``infer``   - forward + fused sigmoid of the same batch (weak scaling: every rank its own batch);
   ``sliding`` - cfg 3, crop -> forward -> blend of a 1024^3 synthetic volume, 4096 patches sharded over the ranks by Z-slab, each
                 rank holding only its input slab; strong scaling (N = 1 runs the whole 1024^3 volume on one GPU; --vol 512 is one GPU's
                 share of the 8-GPU job).
+and at N = 1 the ``train_bf16``, ``cfg4_resunetpp`` and ``cfg5_rcan_sr`` sub-records and the ``cpu_baseline``.  --mode infer / sliding
+time that section alone; their roofline entries, too, take runs of their own and come with --full only.
 Workload = BASELINE.json configs[1]: 3D ResUNet (feature maps 16-32-64-128-256, InstanceNorm, ELU), 128^3 1-channel patches,
 batch 4 per GPU, bf16 storage / fp32 accumulate, synthetic data, random-init weights.  One step = one pass over one batch.
 """
@@ -264,12 +269,13 @@ def run_sliding(a, model, dev, rank, world, V, warmup, steps):
     for _ in range(warmup):
         once()
     elapsed = _timed(once, steps, world, dev)
-    # per-kernel times of the blend and the gather of the last pass's geometry, on this rank (events on the launch stream)
+    # --full: per-kernel times of the blend and the gather of the last pass's geometry, on this rank (events on the launch stream)
     prof = L.Profile(names=("bpx_merge3d_blend", "bpx_crop3d_gather"))
-    L.lib.prof = prof
-    once()
-    torch.cuda.synchronize()
-    L.lib.prof = None
+    if a.full:
+        L.lib.prof = prof
+        once()
+        torch.cuda.synchronize()
+        L.lib.prof = None
     ms = {"bpx_merge3d_blend": 0.0, "bpx_crop3d_gather": 0.0}
     cnt = {"bpx_merge3d_blend": 0, "bpx_crop3d_gather": 0}
     for (name, _), (c, t) in prof.summary().items():
@@ -289,6 +295,14 @@ def run_sliding(a, model, dev, rank, world, V, warmup, steps):
     if rank == 0:
         mb = merge_bytes / (ms["bpx_merge3d_blend"] * 1e-3) / 1e9 if ms["bpx_merge3d_blend"] else None
         cb = crop_bytes / (ms["bpx_crop3d_gather"] * 1e-3) / 1e9 if ms["bpx_crop3d_gather"] else None
+        roofline = None
+        if a.full:
+            roofline = dict(bound="hbm", kernel="bpx_merge3d_blend", achieved=round(mb, 1) if mb else None, peak=HBM_PEAK / 1e9, unit="GB/s",
+                            frac=round(mb / (HBM_PEAK / 1e9), 4) if mb else None, **_tiling_traffic(V, world, plan.n_patches),
+                            algorithmic_bytes_per_pass=merge_bytes, launches=cnt["bpx_merge3d_blend"], ms_per_pass=round(ms["bpx_merge3d_blend"], 3),
+                            crop=dict(kernel="bpx_crop3d_gather", GBps=round(cb, 1) if cb else None, launches=cnt["bpx_crop3d_gather"],
+                                      ms_per_pass=round(ms["bpx_crop3d_gather"], 3), algorithmic_bytes_per_pass=crop_bytes),
+                            timed_on="one extra pass after the timed region, rank 0's share")
         rec = dict(
             metric="voxels/sec 3D ResUNet 128^3 patch (sliding-window inference: crop+forward+blend, patch voxels)",
             value=pv * steps / elapsed, unit="voxels/s", n_gpus=world, steps=steps, warmup=warmup, ms_per_step=1e3 * elapsed / steps,
@@ -297,12 +311,7 @@ def run_sliding(a, model, dev, rank, world, V, warmup, steps):
                                  % ("" if V == 1024 else " (one GPU's share of the 8-GPU job)", V, a.patch, plan.n_patches, world),
                         patches=plan.n_patches, volume=V, parallelism="z-slab x%d" % world, input_slices_rank0=[z_lo, z_hi]),
             mfma_frac_end_to_end=round(pv * steps / elapsed * FLOP_PER_VOXEL_FWD / (world * MFMA_PEAK_BF16), 5),
-            roofline=dict(bound="hbm", kernel="bpx_merge3d_blend", achieved=round(mb, 1) if mb else None, peak=HBM_PEAK / 1e9, unit="GB/s",
-                          frac=round(mb / (HBM_PEAK / 1e9), 4) if mb else None, **_tiling_traffic(V, world, plan.n_patches),
-                          algorithmic_bytes_per_pass=merge_bytes, launches=cnt["bpx_merge3d_blend"], ms_per_pass=round(ms["bpx_merge3d_blend"], 3),
-                          crop=dict(kernel="bpx_crop3d_gather", GBps=round(cb, 1) if cb else None, launches=cnt["bpx_crop3d_gather"],
-                                    ms_per_pass=round(ms["bpx_crop3d_gather"], 3), algorithmic_bytes_per_pass=crop_bytes),
-                          timed_on="one extra pass after the timed region, rank 0's share"),
+            roofline=roofline,
             checksum=float(out[0].double().mean().item()) if out[0] is not None else None)
     return rec
 
@@ -407,7 +416,7 @@ def conv_roofline(prof, prof_steps, dtype, timed_on):
     return head, top
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -431,6 +440,10 @@ def main():
                          "f16 = the fp16 forward that meets the Dice < 1e-4 bar at the speed of bf16 (the forward of the mixed training mode); "
                          "same = --dtype")
     ap.add_argument("--breakdown", action="store_true", help="print a per-kernel timing table of one step and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other feed, the roofline entries (eager launch-event steps), the rank self-check at N > 1, the "
+                         "sub-records (infer, sliding with its checksum, train_bf16, cfg4, cfg5) and the CPU baseline.  Off: set up, warm up, time the "
+                         "K steps, write --dump-outputs, print the line.  The --no-* options below trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-launch-events", action="store_true",
                     help="skip the eager per-launch event steps after a graph-replayed timed region (no roofline entry): a rocprofv3 kernel trace "
@@ -449,14 +462,19 @@ def main():
     ap.add_argument("--no-bf16-record", action="store_true", help="skip the pure-bf16 train sub-record (`train_bf16`) of the single-GPU mix16 line")
     ap.add_argument("--self-check", action="store_true",
                     help="verify (also with one rank under --force-ddp) that every rank's post-all-reduce gradient / parameter checksum agrees and that "
-                         "the gathered cfg-3 volume has the checksum of the single-GPU run committed in profiles/sliding_checksums.json; at N > 1 the "
-                         "checks run by default")
+                         "the gathered cfg-3 volume has the checksum of the single-GPU run committed in profiles/sliding_checksums.json; at N > 1 "
+                         "--full runs the checks by default")
     ap.add_argument("--no-cfg5", action="store_true", help="skip the RCAN x4 super-resolution (cfg 5) sub-record of the single-GPU line")
     ap.add_argument("--sliding-timeout", type=float, default=240.0,
                     help="N > 1: seconds after which a hung sliding-window section is abandoned (the line is printed without it)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed train steps, write what the last one computed as DIR/<name>.npy (float32, rank 0): loss, logits (a fixed "
                          "sample of 2^20 voxels), params and grads (every parameter and its gradient, flattened in named_parameters() order)")
+    return ap
+
+
+def main():
+    ap = arg_parser()
     a = ap.parse_args()
     if a.dump_outputs is not None and (a.arch != "resunet" or a.mode not in ("all", "train") or a.breakdown):
         ap.error("--dump-outputs covers the timed ResUNet train step: --arch resunet, --mode all or train, no --breakdown")
@@ -571,7 +589,7 @@ def main():
                     estep = DataParallelTrainStep(net, loss_fn, opt, x, tgt, graph=False, broadcast_parameters=False)
                     step = lambda: estep()  # noqa: E731
                     runner = estep
-        feed_note = "device-resident batch, H2D excluded (the host-fed step is timed beside it: host_fed_ms_per_step)"
+        feed_note = "device-resident batch, H2D excluded (--full times the host-fed step beside it: host_fed_ms_per_step)"
         inner_step, fed_step = step, None
         if not a.breakdown:
             # The reference copies every batch to the device (train_engine.py:116, 125: two H2D copies per step).  Here: the batch lies in PINNED host
@@ -604,7 +622,7 @@ def main():
             host_note = ("pinned host batch (%.1f MB): async H2D on a copy stream beside the previous step, then a device-to-device copy into the step's static "
                          "inputs; both inside the timed region" % ((xs_h.numel() * xs_h.element_size() + ts_h.numel() * ts_h.element_size()) / 1e6))
             if a.feed == "host":
-                step, feed_note = fed_step, host_note + " (the device-resident step is timed beside it: device_resident_ms_per_step)"
+                step, feed_note = fed_step, host_note + " (--full times the device-resident step beside it: device_resident_ms_per_step)"
         for _ in range(a.warmup):
             out = step()
         torch.cuda.synchronize()
@@ -615,7 +633,7 @@ def main():
             return breakdown(a, L, step, "train")
 
         self_check = None
-        if multi and (a.self_check or world > 1):
+        if multi and (a.self_check or (world > 1 and a.full)):
             # every rank must hold the SAME averaged gradients and the same parameters after a step (all-reduce + identical optimizer steps):
             # rank-local double checksums are gathered and compared on every rank; a mismatch fails the run instead of producing a number
             gsum = torch.zeros((), dtype=torch.float64, device=dev)
@@ -644,7 +662,7 @@ def main():
                                                     grads=torch.cat([p.grad.detach().reshape(-1) for p in params])),
                          sampled=dict(logits=logits_t))
         device_resident_ms = host_fed_ms = None
-        if fed_step is not None:      # the other feed, the same K steps, as a sub-field beside the headline
+        if fed_step is not None and a.full:      # the other feed, the same K steps, as a sub-field beside the headline
             other = 1e3 * _timed(inner_step if a.feed == "host" else fed_step, a.steps, world, dev) / a.steps
             if a.feed == "host":
                 device_resident_ms = other
@@ -654,7 +672,7 @@ def main():
         fb_graphs = getattr(model, "_graphs", None) is not None
         if fb_graphs:
             model.release_graphs()
-        if (graphed or fb_graphs) and not a.no_launch_events:
+        if (graphed or fb_graphs) and a.full and not a.no_launch_events:
             # a graph replay has no per-launch events: time the same launches on the same stream in eager steps right after
             # the timed region (same kernels, same shapes; `value` above is NOT taken from these steps)
             prof_steps = min(a.steps, 5)
@@ -697,7 +715,7 @@ def main():
 
     # ======================================================= infer =======================================================
     infer_rec = None
-    if a.mode in ("all", "infer"):
+    if a.mode == "infer" or (a.mode == "all" and a.full):
         model.eval()
         model.compute_dtype = inf_dtype                 # the engine is rebuilt for the inference storage type (fp16 by default)
         want_graph = a.graph == "on" or (a.graph == "auto" and not a.breakdown)   # no collective inside an inference step
@@ -724,7 +742,7 @@ def main():
         elapsed = _timed(step, a.steps, world, dev)
         L.lib.prof = None
         prof_steps = a.steps
-        if graphed and not a.no_launch_events:
+        if graphed and a.full and not a.no_launch_events:
             prof_steps = min(a.steps, 5)
             L.lib.prof = prof
             for _ in range(prof_steps):
@@ -755,7 +773,7 @@ def main():
 
     # ====================================================== sliding ======================================================
     sliding_rec = None
-    if a.mode == "all":
+    if a.mode == "all" and a.full:
         # Never lose the train line to a hung exchange (the multi-GPU sliding path has not seen an 8-GPU node before the driver's
         # scaling run): a watchdog prints the line without the sliding record and ends the process.
         done = threading.Event()
@@ -783,7 +801,7 @@ def main():
     # BASELINE.json labels cfg 2 "bf16": the headline runs the mixed mode (fp16 forward inside the Dice bar, bf16 gradients); the pure-bf16 train
     # step - same kernels, same 16 bits per element, forward outside the Dice bar - is timed beside it so the labelled dtype has its own number
     bf16_rec = None
-    if a.mode in ("all", "train") and a.dtype == "mix16" and world == 1 and not multi and not a.no_bf16_record and not a.breakdown:
+    if a.full and a.mode in ("all", "train") and a.dtype == "mix16" and world == 1 and not multi and not a.no_bf16_record and not a.breakdown:
         try:
             bf16_rec = run_train_bf16(a, dev)
         except Exception as e:  # noqa: BLE001
@@ -792,7 +810,7 @@ def main():
             line["train_bf16"] = bf16_rec
     # cfg 4 (ResUNet++ 80^3, B/C/D loss) as a sub-record of the single-GPU line: the second model family the path covers
     cfg4_rec = None
-    if a.mode == "all" and world == 1 and not multi and not a.no_cfg4:
+    if a.full and a.mode == "all" and world == 1 and not multi and not a.no_cfg4:
         try:
             del model
             torch.cuda.empty_cache()
@@ -804,7 +822,7 @@ def main():
 
     # cfg 5 (RCAN-3D x4, 64^3 -> 256^3, fp16 inference) as a sub-record of the single-GPU line
     cfg5_rec = None
-    if a.mode == "all" and world == 1 and not multi and not a.no_cfg5:
+    if a.full and a.mode == "all" and world == 1 and not multi and not a.no_cfg5:
         try:
             cfg5_rec = run_rcan_sr(a, dev)
             torch.cuda.synchronize()
@@ -846,7 +864,7 @@ def main():
             out["cfg4_resunetpp"] = cfg4_rec
         if cfg5_rec is not None:
             out["cfg5_rcan_sr"] = cfg5_rec
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.patch, quick=a.quick_cpu_baseline)
         finish(out, multi, rank)
         return

@@ -21,11 +21,11 @@ python scripts/pmc_traffic.py $(find $O/pmc_f -name "p_results.db" | head -1) $(
 python scripts/pmc_traffic.py $(find $O/pmc_tf -name "p_results.db" | head -1) $(find $O/pmc_tw -name "p_results.db" | head -1) > $O/pmc_traffic_tiling.json 2>> $O/pmc_traffic.err
 cp $O/pmc_traffic.json profiles/pmc_traffic.json; cp $O/pmc_traffic_tiling.json profiles/pmc_traffic_tiling.json
 ( time python -m pytest tests -m gpu -q -p no:cacheprovider ) > $O/${R}_gpu_tests.txt 2>&1
-python bench.py > $O/${R}_bench.json 2> $O/bench.err
-python bench.py --force-ddp --self-check --mode train --no-cpu-baseline > $O/${R}_bench_train_dp_1rank.json 2> $O/bench_dp.err
-python bench.py --mode sliding --vol 1024 --steps 1 --warmup 1 --no-cpu-baseline > $O/${R}_bench_sliding_1024.json 2> $O/bench_sliding.err
-python bench.py --mode sliding --vol 512 --steps 2 --warmup 1 --no-cpu-baseline > $O/${R}_bench_sliding_512.json 2>> $O/bench_sliding.err
-# the single-GPU checksums of the blended cfg-3 volumes (initial weights of seed 0): what `bench.py --gpus N` compares its gathered volume with
+python bench.py --full > $O/${R}_bench.json 2> $O/bench.err
+python bench.py --full --force-ddp --self-check --mode train --no-cpu-baseline > $O/${R}_bench_train_dp_1rank.json 2> $O/bench_dp.err
+python bench.py --full --mode sliding --vol 1024 --steps 1 --warmup 1 --no-cpu-baseline > $O/${R}_bench_sliding_1024.json 2> $O/bench_sliding.err
+python bench.py --full --mode sliding --vol 512 --steps 2 --warmup 1 --no-cpu-baseline > $O/${R}_bench_sliding_512.json 2>> $O/bench_sliding.err
+# the single-GPU checksums of the blended cfg-3 volumes (initial weights of seed 0): what `bench.py --gpus N --full` compares its gathered volume with
 python - "$O" "$R" <<'PY' > $O/sliding_checksums.json
 import json, sys
 O, R = sys.argv[1:3]
@@ -39,7 +39,7 @@ for vol, path, pick in ((512, f"{O}/{R}_bench_sliding_512.json", lambda d: d.get
 print(json.dumps(out, indent=1))
 PY
 BPX_BENCH_ONE_DEVICE=1 BPX_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29577 \
-   bench.py --gpus 2 --steps 5 --warmup 2 --vol 512 > $O/${R}_bench_2ranks_one_gpu_gloo.json 2> $O/bench_2rank.err
+   bench.py --gpus 2 --steps 5 --warmup 2 --vol 512 --full > $O/${R}_bench_2ranks_one_gpu_gloo.json 2> $O/bench_2rank.err
 python bench.py --arch resunetpp --batch 4 --steps 5 --warmup 2 > $O/${R}_bench_resunetpp_80.json 2> $O/bench_pp.err
 python bench.py --arch resunetpp --batch 4 --breakdown --graph off > $O/${R}_breakdown_resunetpp_events.txt 2> /dev/null
 python bench.py --breakdown --graph off --mode train > $O/${R}_breakdown_train_events.txt 2> /dev/null
@@ -85,7 +85,7 @@ python tests/gpu_diag.py --net --out $O/${R}_gpu_diag.txt > /dev/null 2>&1
 [ -f gpurun_out/diag_values.txt ] && cp gpurun_out/diag_values.txt $O/${R}_gpu_test_values.txt     # measured values the parity tests recorded (loss-curve gap, Dice rows)
 python tests/bench_kernels.py rcan 2>&1 | grep -v "Warning\|run_backward" > $O/${R}_rcan_trunk_64.txt
 cd /tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/kt -o train -- python $ROOT/bench.py --mode train --steps 20 --warmup 3 --no-cpu-baseline --no-launch-events --no-bf16-record > $ROOT/$O/kt_train.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/kt -o train -- python $ROOT/bench.py --full --mode train --steps 20 --warmup 3 --no-cpu-baseline --no-launch-events --no-bf16-record > $ROOT/$O/kt_train.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/kt -o resunetpp -- python $ROOT/bench.py --arch resunetpp --batch 4 --steps 20 --warmup 3 > $ROOT/$O/kt_pp.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/kt -o infer -- python $ROOT/bench.py --mode infer --steps 20 --warmup 3 --no-cpu-baseline --no-launch-events > $ROOT/$O/kt_infer.log 2>&1
 cd $ROOT

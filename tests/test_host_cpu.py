@@ -711,6 +711,15 @@ def test_bench_dump_outputs_is_float32_sampled_and_bounded(tmp_path):
     assert not (tmp_path / "big").exists()
 
 
+def test_bench_full_is_an_option_off_by_default():
+    """bench.py --full: a plain `--gpus 1 --steps K --warmup W` run times the headline alone; everything else it measures or checks needs --full."""
+    import bench
+
+    ap = bench.arg_parser()
+    assert ap.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert ap.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"]).full is True
+
+
 def test_channel_pad_plan_covers_every_parameter_and_is_exact_on_the_oracle():
     """engine.channel_pad_plan / pad_channels / unpad_channel_grads (feature maps that are not multiples of 16, e.g. CartoCell's [52, 68, 84]): every
     parameter of the module has a plan entry, the padded tensors have exactly the shapes of the padded architecture, un-padding is the inverse, and
