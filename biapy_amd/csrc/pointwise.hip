@@ -893,6 +893,21 @@ extern "C" int bpx_debug_set_pw_stream(int on) { g_pw_stream = on; return 0; }
 extern "C" int bpx_debug_set_convt_k1(int on) { g_convt_k1 = on; return 0; }
 extern "C" int bpx_convT3d_stats_tiles(int D, int H, int W, int sz) { return convt_groups((int64_t)D * H * W) * 4 * (sz == 1 ? 1 : 2); }
 
+// The operands the streaming kernel (pw_nbs_kernel) takes: the decoder blocks' input gradient at the large levels.  dtype: BF16 for MIX16 too.
+// Shared by conv1x1_impl and bpx_conv1x1_fwd_split_wgrad_query, which must never answer yes where the launcher would refuse.
+static bool pws_ok(int dtype, int N, int64_t vps, const bpx_tensor& x, bool has_coef, const float* bias_d, const bpx_tensor& g, const bpx_tensor& t,
+                   const void* coef_d, const bpx_tensor& addend, const bpx_tensor& y, const bpx_tensor& y2) {
+  const int KC = x.C / 16;
+  const int TV = KC == 1 ? 128 : 64;
+  const int64_t vox = (int64_t)N * vps;
+  auto span = [&](const bpx_tensor& q, int chunks) { return (q.cs ? (int64_t)q.cs * (chunks - 1) : 0) * 2 + vox * (int64_t)q.ld * 2; };
+  return g_pw_stream && dtype == BPX_BF16 && (KC == 1 || KC == 2) && x.C % 16 == 0 && has_coef && y2.ptr != nullptr && y.C + y2.C == 3 * x.C && y.C % 4 == 0 &&
+         g.C == 3 * x.C && t.C == 3 * x.C && bias_d == nullptr && addend.ptr == nullptr && vps % TV == 0 && vox >= 262144 &&
+         span(x, 1) < (1ll << 31) && span(g, 1) < (1ll << 31) && span(t, 3 * KC) < (1ll << 31) && (x.ld & 7) == 0 && (g.ld & 7) == 0 && (t.ld & 7) == 0 &&
+         (y.ld & 3) == 0 && (y2.ld & 3) == 0 && (((uintptr_t)x.ptr | (uintptr_t)g.ptr | (uintptr_t)t.ptr | (uintptr_t)coef_d) & 15) == 0 &&
+         (((uintptr_t)y.ptr | (uintptr_t)y2.ptr) & 7) == 0;
+}
+
 static int conv1x1_impl(const char* fn, int dtype, int N, int64_t vps, bpx_tensor x, const void* w_packed_d, const float* bias_d,
                         bpx_tensor g, bpx_tensor t, const bpx_nbwd_coef* coef_d, bpx_tensor addend, bpx_tensor y, bpx_tensor y2,
                         bpx_stream_t stream, float* wg_part = nullptr, int* wg_groups = nullptr) {
@@ -927,12 +942,7 @@ static int conv1x1_impl(const char* fn, int dtype, int N, int64_t vps, bpx_tenso
     const int KC = x.C / 16;
     const int TV = KC == 1 ? 128 : 64;
     const int64_t vox = (int64_t)N * vps;
-    auto span = [&](const bpx_tensor& q, int chunks) { return (q.cs ? (int64_t)q.cs * (chunks - 1) : 0) * 2 + vox * (int64_t)q.ld * 2; };
-    const bool ok = g_pw_stream && dtype == BPX_BF16 && (KC == 1 || KC == 2) && x.C % 16 == 0 && coef_d != nullptr && y2.ptr != nullptr && y.C + y2.C == 3 * x.C && y.C % 4 == 0 &&
-                    g.C == 3 * x.C && t.C == 3 * x.C && bias_d == nullptr && addend.ptr == nullptr && vps % TV == 0 && vox >= 262144 &&
-                    span(x, 1) < (1ll << 31) && span(g, 1) < (1ll << 31) && span(t, 3 * KC) < (1ll << 31) && (x.ld & 7) == 0 && (g.ld & 7) == 0 && (t.ld & 7) == 0 &&
-                    (y.ld & 3) == 0 && (y2.ld & 3) == 0 && (((uintptr_t)x.ptr | (uintptr_t)g.ptr | (uintptr_t)t.ptr | (uintptr_t)coef_d) & 15) == 0 &&
-                    (((uintptr_t)y.ptr | (uintptr_t)y2.ptr) & 7) == 0;
+    const bool ok = pws_ok(dtype, N, vps, x, coef_d != nullptr, bias_d, g, t, coef_d, addend, y, y2);
     if (ok) {
       PwsParams q{};
       q.x = x.ptr; q.x_ld = x.ld; q.g = g.ptr; q.g_ld = g.ld; q.t = t.ptr; q.t_ld = t.ld; q.t_cs = t.cs ? (int)t.cs : 16;
@@ -967,6 +977,14 @@ extern "C" int64_t bpx_conv1x1_fwd_split_wgrad_workspace(int dtype, int N, int64
   const int TV = K == 16 ? 128 : 64;
   if (vps % TV != 0 || (int64_t)N * vps < 262144) return 0;
   return (int64_t)256 * (3 * K) * K * 4;
+}
+// The same answer for the actual operands: 0 also where bpx_conv1x1_fwd_split_wgrad would refuse them (32-bit spans, pitches, alignment).
+// g and coef_d may be null when they are allocated after the query (16-byte aligned, g dense with g.ld = g.C): only their shape is read then.
+extern "C" int64_t bpx_conv1x1_fwd_split_wgrad_query(int dtype, int N, int64_t vps, bpx_tensor x, bpx_tensor g, bpx_tensor t, const void* coef_d,
+                                                     bpx_tensor y_lo, bpx_tensor y_hi) {
+  const int64_t need = bpx_conv1x1_fwd_split_wgrad_workspace(dtype, N, vps, x.C);
+  if (need <= 0 || x.cs != 0 || g.cs != 0 || y_lo.cs != 0 || y_hi.cs != 0 || y_hi.ptr == nullptr) return 0;
+  return pws_ok(dtype == BPX_MIX16 ? BPX_BF16 : dtype, N, vps, x, true, nullptr, g, t, coef_d, bpx_tensor{nullptr, 0, 0}, y_lo, y_hi) ? need : 0;
 }
 extern "C" int bpx_conv1x1_fwd_split_wgrad(int dtype, int N, int64_t vps, bpx_tensor x, const void* w_packed_d, bpx_tensor g, bpx_tensor t,
                                            const bpx_nbwd_coef* coef_d, bpx_tensor y_lo, bpx_tensor y_hi, float* dw_d, void* ws_d, int64_t ws_bytes,

@@ -321,7 +321,79 @@ class _Blk:
     drop_ctr: Optional[torch.Tensor] = None  # with dropout: the device step counter value THIS forward drew its masks with (its backward regenerates them from it)
 
 
+# ---- batches whose operands pass the kernels' 32-bit span ------------------------------------------------------------------------------
+# The kernels address a whole-batch operand with 32-bit offsets inside one 2 GiB buffer window.  A batch whose largest operand reaches that
+# span runs as consecutive sample groups, each under it: the forward of every group, then the backward of every group, with the weight
+# gradients of the groups summed in group order (two identical calls give identical bits).  Below the span a batch runs as one group, on
+# exactly the launches it always ran.  Training in the 16-bit modes bounds the operands' bytes (the 2 GiB buffer windows of the bf16 / mixed
+# backward kernels); inference, and fp32 training, whose kernels address with 64-bit pointers and bound element counts, bound elements (the 32-bit
+# indices of the elementwise and pointwise passes and of the chunk strides).
+SPAN_LIMIT = 1 << 31
+SPAN_MARGIN = 1 << 20      # pitch rounding of the chunk-planar buffers (their plane padding, L.PLANE_PAD_BYTES, is added to it)
+
+
+def span_in_bytes(dtype: torch.dtype, training: bool) -> bool:
+    """Whether batch_groups bounds bytes (16-bit training) or elements (inference, fp32 training)."""
+    return training and dtype != torch.float32
+
+
+def sample_span(cfg: NetConfig, dtype: torch.dtype, patch: Sequence[int], training: bool, unet: bool = False) -> Tuple[int, str]:
+    """(span of the largest operand of ONE sample of a (Z, Y, X) patch, what it is): bytes or elements as span_in_bytes says.  ``unet``: the
+    U-Net engine's decoder inputs ([up (fm[i]) | skip (fm[i])]) instead of the ResUNet's ([up (fm[i + 1]) | skip (fm[i])])."""
+    es = 4 if dtype == torch.float32 else 2
+    fm = list(cfg.feature_maps)
+    Lv = cfg.depth
+    S = [tuple(int(v) for v in patch)]
+    for i in range(Lv):
+        S.append((max(1, S[i][0] // cfg.z_down[i]), S[i][1] // 2, S[i][2] // 2))
+    vox = [s[0] * s[1] * s[2] for s in S]
+    ops = [(vox[0] * cfg.in_ch, 4, f"input ({cfg.in_ch} channels)")]
+    for i in range(Lv):
+        ops.append((vox[i] * fm[i], es, f"level-{i} activation ({fm[i]} channels)"))
+        cc = 2 * fm[i] if unet else fm[i] + fm[i + 1]
+        ops.append((vox[i] * cc, es, f"level-{i} decoder input ({cc} channels)"))
+    ops.append((vox[Lv] * fm[Lv], es, f"bottleneck activation ({fm[Lv]} channels)"))
+    vo = vox[0] * (cfg.post_up * 4 if cfg.post_up else 1)
+    if cfg.post_up:
+        ops.append((vo * fm[0], es, f"up-sampled level-0 activation ({fm[0]} channels)"))
+    ops.append((vo * sum(cfg.out_channels), 4, f"logits ({sum(cfg.out_channels)} channels)"))
+    nb = span_in_bytes(dtype, training)
+    n, _, what = max((e * (b if nb else 1), -k, w) for k, (e, b, w) in enumerate(ops))
+    return n, what
+
+
+def _plane_pad(cfg: NetConfig, unet: bool) -> int:
+    """Bytes a chunk-planar decoder input adds for its plane padding (L.PLANE_PAD_BYTES between consecutive 16-channel planes)."""
+    fm = list(cfg.feature_maps)
+    widest = max((2 * fm[i] if unet else fm[i] + fm[i + 1]) for i in range(cfg.depth))
+    return L.PLANE_PAD_BYTES * (widest // 16)
+
+
+def batch_groups(cfg: NetConfig, dtype: torch.dtype, B: int, patch: Sequence[int], training: bool, unet: bool = False) -> List[Tuple[int, int]]:
+    """Sample ranges [a, b) a batch of B patches runs as: [(0, B)] while its largest operand stays under the span, otherwise the fewest
+    groups of near-equal size (larger ones first) that each stay under it.  Raises NotImplementedError when one sample alone is beyond
+    it (on the host, before anything is launched)."""
+    per, what = sample_span(cfg, dtype, patch, training, unet)
+    unit = "bytes" if span_in_bytes(dtype, training) else "elements"
+    margin = SPAN_MARGIN + _plane_pad(cfg, unet)
+    if per + margin > SPAN_LIMIT:
+        raise NotImplementedError(f"patch {'x'.join(str(int(v)) for v in patch)}: one sample's {what} spans {per} {unit}, beyond the per-sample limit "
+                                  f"of 2^31 {unit} ({SPAN_LIMIT - margin} with the buffers' padding) of the MI355X kernels' 32-bit addressing")
+    if B * per + margin <= SPAN_LIMIT:
+        return [(0, B)]
+    g = (SPAN_LIMIT - margin) // per
+    n = -(-B // g)
+    out, a = [], 0
+    for q in range(n):
+        b = a + B // n + (1 if q < B % n else 0)
+        out.append((a, b))
+        a = b
+    return out
+
+
 class ResUNetEngine:
+    _unet_layout = False          # batch_groups: the U-Net engine's decoder inputs are [up (fm[i]) | skip (fm[i])]
+
     def __init__(self, cfg: NetConfig, dtype: torch.dtype = torch.bfloat16):
         assert dtype in (torch.bfloat16, torch.float32, torch.float16)
         self.cfg = cfg
@@ -462,6 +534,48 @@ class ResUNetEngine:
                 self._keep.append(self._ws)   # a side-stream kernel may still be using the old slab
             self._ws = torch.empty(max(nbytes, 32 << 20), dtype=torch.uint8, device=dev)
         return self._ws
+
+    # ---- sample groups (batch_groups) -------------------------------------------------------------------
+    def _groups_for(self, B: int, patch, save: bool) -> List[Tuple[int, int]]:
+        """The sample groups of a forward; BatchNorm couples the samples of a batch and keeps running it as one group."""
+        groups = [(0, B)] if self.bn else batch_groups(self.cfg, self.dtype, B, patch, save, unet=self._unet_layout)
+        self.last_groups = groups
+        return groups
+
+    def _forward_groups(self, groups, fwd, x: torch.Tensor, save: bool, x_ndhwc: Optional[torch.Tensor] = None, **kw):
+        """The forward of every group in turn; logits concatenated along the batch."""
+        outs, parts = [], []
+        for a, b in groups:
+            if x_ndhwc is not None:
+                lo, c = fwd(x=None, x_ndhwc=x_ndhwc[a:b], save=save, **kw)
+            else:
+                lo, c = fwd(x=x[a:b], save=save, **kw)
+            outs.append(lo)
+            parts.append(((a, b), c, getattr(self, "_prepacked", None)))
+        self.last_groups = list(groups)
+        return torch.cat(outs, 0), (dict(groups=parts) if save else None)
+
+    def _backward_groups(self, ctx, dlogits: torch.Tensor, bwd, on_last_block=None) -> Dict[str, torch.Tensor]:
+        """The backward of every group in turn (with the packed operands of its own forward); the groups' parameter gradients are summed in
+        group order, the input gradient ("__dx__") is concatenated."""
+        G, flat, dx = None, None, []
+        for (a, b), c, packed in ctx["groups"]:
+            self._prepacked = packed
+            Gi = bwd(c, dlogits[a:b])
+            if "__dx__" in Gi:
+                dx.append(Gi.pop("__dx__"))
+            if G is None:
+                G, flat = Gi, getattr(self, "last_flat_grad", None)
+            else:
+                for k, v in Gi.items():
+                    G[k].add_(v)
+        if flat is not None:
+            self.last_flat_grad = flat
+        if dx:
+            G["__dx__"] = torch.cat(dx, 0)
+        if on_last_block is not None:
+            on_last_block()          # every gradient is final here
+        return G
 
     # ---- dropout --------------------------------------------------------------------------------------
     # nn.Dropout(p) of a block sits behind Conv -> Norm -> Act of its first ConvBlock (blocks.py:163), i.e. on the tensor the second convolution's
@@ -679,6 +793,10 @@ class ResUNetEngine:
             x = x_ndhwc.permute(0, 4, 1, 2, 3)           # only its shape is used below
         else:
             assert x.is_cuda and x.dtype == torch.float32 and x.dim() == cfg.ndim + 2
+        groups = self._groups_for(x.shape[0], ((1,) + tuple(x.shape[2:]))[-3:], save)
+        if len(groups) > 1:
+            return self._forward_groups(groups, lambda **a: self.forward(P, head_act=head_act, cache_weights=cache_weights, want_dx=want_dx, **a),
+                                        x, save, x_ndhwc=x_ndhwc)
         if cfg.ndim == 2:
             x = x.unsqueeze(2)
         if self.drop_active and any(v > 0 for v in cfg.dropout):
@@ -894,7 +1012,9 @@ class ResUNetEngine:
         sc_ws = 0
         if (isinstance(dx_out, tuple) and blk.rec_x is not None and self._deferred and not self.use_side_stream and self.cfg.gn_groups == 0
                 and dOut.C * 3 == blk.cin and self.dtype != torch.float32):
-            sc_ws = int(lib.bpx_conv1x1_fwd_split_wgrad_workspace(self.bdt, B, vox, dOut.C))
+            # asked with the operands: the kernel's span, pitch and alignment bounds decide too (g0 and coef0 are allocated below, dense)
+            sc_ws = int(lib.bpx_conv1x1_fwd_split_wgrad_query(self.bdt, B, vox, dOut, L.Tensor(None, blk.cin, blk.cin, 0),
+                                                              L.tview(blk.x, blk.x_c0, blk.cin), None, dx_out[0], dx_out[1]))
         if blk.first and self.cfg.in_ch == 1:
             if getattr(self, "_r1_done", False):       # formed by bpx_maxpool3d_bwd_r1, the pass that wrote dOut (see _backward)
                 self._r1_done = False
@@ -1004,7 +1124,10 @@ class ResUNetEngine:
         """``on_last_block``: called (no arguments) right before the backward of the FIRST encoder block - the last stretch of the pass.  At that
         point every queued weight-gradient reduction has been flushed, so all parameter gradients except ``down_path.0.*`` are final in the flat
         slab (``self.last_flat_grad``, parameter order): a data-parallel step starts their all-reduce there and lets it run beside the rest of
-        the backward (graphs.DataParallelTrainStep; what DDP's buckets do for the reference, base_workflow.py:952-958)."""
+        the backward (graphs.DataParallelTrainStep; what DDP's buckets do for the reference, base_workflow.py:952-958).  A batch that ran as
+        several sample groups (batch_groups) calls it once, after the last group: only then are the summed gradients final."""
+        if ctx is not None and "groups" in ctx:
+            return self._backward_groups(ctx, dlogits, lambda c, d: self.backward(P, c, d), on_last_block)
         self._on_last_block = on_last_block
         self._keep = []   # buffers the side stream may still be reading; released after the final stream join
         # the ~29 weight-gradient reductions of a step run as one batched launch at the end (they are latency chains of a

@@ -17,6 +17,8 @@ from __future__ import annotations
 
 from typing import Callable, Optional
 
+import gc
+
 import torch
 import torch.distributed as dist
 
@@ -377,6 +379,9 @@ class DataParallelTrainStep:
         with torch.no_grad():
             _warm(eager, warmup, side)
             g1a, g1b, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            # what torch.cuda.graph does on entry and this raw capture_begin does not: collect unreachable cycles NOW, so that no earlier
+            # graph, event or tensor (a previous step object, say) is destroyed by a garbage-collection pass inside the capture
+            gc.collect()
             torch.cuda.synchronize()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):

@@ -42,6 +42,8 @@ class _CB:
 
 
 class UNetEngine(ResUNetEngine):
+    _unet_layout = True
+
     def __init__(self, cfg: NetConfig, ndim: int, dtype: torch.dtype = torch.bfloat16, nconvs: int = 2):
         super().__init__(cfg, dtype)
         assert ndim in (2, 3)
@@ -88,6 +90,9 @@ class UNetEngine(ResUNetEngine):
         """x: (B,C,Y,X) [2D] or (B,C,Z,Y,X) [3D] fp32.  Returns logits in the same channels-first planar layout, and the context."""
         cfg = self.cfg
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == self.ndim + 2
+        groups = self._groups_for(x.shape[0], ((1,) + tuple(x.shape[2:]))[-3:], save)
+        if len(groups) > 1:
+            return self._forward_groups(groups, lambda **a: self.forward(P, head_act=head_act, cache_weights=cache_weights, **a), x, save)
         if self.ndim == 2:
             x = x.unsqueeze(2)
         B, Cin, D0, H0, W0 = x.shape
@@ -216,6 +221,8 @@ class UNetEngine(ResUNetEngine):
             L.check(lib.bpx_conv3d_dgrad(self.gdt, B, D, H, W, L.tview(g1), w1t.data_ptr(), L.NULL_T, None, 0, dx_out, None, st))
 
     def backward(self, P: Dict[str, torch.Tensor], ctx, dlogits: torch.Tensor) -> Dict[str, torch.Tensor]:
+        if "groups" in ctx:
+            return self._backward_groups(ctx, dlogits, lambda c, d: self.backward(P, c, d))
         cfg = self.cfg
         B, S, zd, img, Pw = ctx["B"], ctx["S"], ctx["zd"], ctx["img"], ctx["Pw"]
         blocks: List[_CB] = ctx["blocks"]

@@ -272,6 +272,11 @@ int bpx_conv1x1_fwd_split(int dtype, int N, int64_t voxels, bpx_tensor x, const 
  * kernel streams anyway.  Only where the streaming kernel applies: _workspace answers the bytes of ws_d, or 0 = call bpx_conv1x1_fwd_split and
  * bpx_conv3d_wgrad instead (BPX_PWS_WG=0 forces that).  Between bpx_wgrad_defer_begin and _flush dw_d is complete at the flush and ws_d must stay untouched until then. */
 int64_t bpx_conv1x1_fwd_split_wgrad_workspace(int dtype, int N, int64_t voxels, int K);
+/* The same answer for the operands themselves: 0 also where the 32-bit spans, pitches or alignment keep them off the streaming kernel, so that a
+ * non-zero answer is always a call bpx_conv1x1_fwd_split_wgrad accepts.  g and coef_d may be null when they are allocated after the query (dense,
+ * 16-byte aligned); their shape is read then. */
+int64_t bpx_conv1x1_fwd_split_wgrad_query(int dtype, int N, int64_t voxels, bpx_tensor x, bpx_tensor g, bpx_tensor t, const void* coef_d,
+                                          bpx_tensor y_lo, bpx_tensor y_hi);
 int bpx_conv1x1_fwd_split_wgrad(int dtype, int N, int64_t voxels, bpx_tensor x, const void* w_packed_d, bpx_tensor g, bpx_tensor t,
                                 const bpx_nbwd_coef* coef_d, bpx_tensor y_lo, bpx_tensor y_hi, float* dw_d, void* ws_d, int64_t ws_bytes,
                                 bpx_stream_t stream);
