@@ -183,7 +183,7 @@ def _load() -> C.CDLL:
     # A/B hooks through the environment: wgrad partial-slab cap in percent
     for env, hook in (("BPX_WGRAD_CAP", "bpx_debug_set_wgrad_cap"), ("BPX_WGRAD_K1", "bpx_debug_set_wgrad_k1"),
                       ("BPX_PW_STREAM", "bpx_debug_set_pw_stream"), ("BPX_C1_PERSIST", "bpx_debug_set_c1_persist"),
-                      ("BPX_BWD_RS", "bpx_debug_set_bwd_rs")):
+                      ("BPX_BWD_RS", "bpx_debug_set_bwd_rs"), ("BPX_FUSED_BITS", "bpx_debug_set_bwd_fused")):
         if os.environ.get(env) is not None:
             getattr(lib, hook)(int(os.environ[env]))
     return lib

@@ -21,9 +21,8 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import contextlib
 import ctypes as C
-
-import os
 
 import torch
 
@@ -292,10 +291,6 @@ def bn_layers(cfg: "NetConfig") -> List[str]:
     return out
 
 
-# InstanceNorm-backward finalize of the residual blocks: per-sample blocks + dgamma / dbeta with the deferred reductions (BPX_NBF_DEFER=0: the plain entry)
-_NBF = lib.bpx_norm_bwd_finalize_deferred if os.environ.get("BPX_NBF_DEFER", "1") != "0" else lib.bpx_norm_bwd_finalize
-
-
 def _recs(B, C, dev):
     return torch.empty((B, C, 4), dtype=torch.float32, device=dev)
 
@@ -415,21 +410,14 @@ class ResUNetEngine:
         self.pdt = L.MIX16 if mixed else self.dt                 # weight packing: forward operators in the forward type, transposed ones in bf16
         self.act = L.ACT[cfg.activation]
         self._ws: Optional[torch.Tensor] = None
-        self._side_stream = None
-        self.planar_cat = os.environ.get("BPX_PLANAR_CAT", "1") != "0"
-        self.use_side_stream = False  # ALL weight-gradient kernels on a second stream: measured on cfg 2 19.5 vs 18.1 ms/step (early kernels, eager);
-        # 11.13 vs 11.18 with the final kernels under graph replay, 21 vs 15 ms eager - the big layers already launch one resident wave of workgroups.
-        # Round 4: the same for the SMALL levels only (<= side_small_vps voxels per sample, e.g. 4096 = the 16^3 and 8^3 levels of cfg 2, whose kernels are
-        # latency chains with one workgroup or less per CU) as a parallel branch of the captured graph: measured SLOWER too - same box, 30 graph-replayed
-        # steps: off 9.74 ms, <= 16^3 9.84 ms, <= 32^3 9.91 ms - and left off (BPX_SIDE_VPS=<voxels> switches it on).
-        self.side_small_vps = int(os.environ.get("BPX_SIDE_VPS", "0"))
+        self._keep: Optional[List[torch.Tensor]] = None      # per backward pass (_backward_pass)
+        self._deferred = False
         # dropout (p > 0 levels, training mode): see _drop_args
         self.drop_active = False               # set by the module before every forward (= module.training)
         self.drop_seed: Optional[int] = None
         self._drop_counter: Optional[torch.Tensor] = None
         self.drop_mask_io: Optional[Dict[int, torch.Tensor]] = None   # tests: {site: uint8 keep flags}; drop_mask_mode 1 = use them, 2 = record the drawn ones
         self.drop_mask_mode = 0
-        self._side_used = False
         self._pack_cache: Dict[Tuple[int, int, int], torch.Tensor] = {}
         self._pack_versions: Dict[Tuple[int, int, int], Tuple[int, int]] = {}
         # BatchNorm ('bn'): batch statistics and running-buffer updates (training) or records from the running buffers (eval); the module sets
@@ -495,45 +483,46 @@ class ResUNetEngine:
         self._bn_cache = (key, recs) if cache else None
         return recs
 
-    # ---- weight-gradient side stream ------------------------------------------------------------------
-    # The wgrad kernels only produce parameter gradients; nothing on the dgrad chain waits for them.  They run on a second
-    # HIP stream so that their workgroups co-reside with the dgrad kernels' (both are latency-bound at 2-3 waves/SIMD on
-    # their own).  Ordering: side waits for an event recorded on the main stream when the kernel's inputs exist; the
-    # main stream waits for the side stream once, at the end of backward.  Buffers read by side-stream kernels are kept
-    # alive in ctx["keep"] until then (PyTorch's allocator is stream-ordered per stream, not across streams).
-    def _side(self, dev, S=None):
-        """The side stream for a launch at spatial size S (None: only in the all-launches mode), or None = the current stream."""
-        small = S is not None and S[0] * S[1] * S[2] <= self.side_small_vps
-        if not (self.use_side_stream or small):
-            return None
-        if self._side_stream is None or self._side_stream.device != dev:
-            self._side_stream = torch.cuda.Stream(device=dev)
-        return self._side_stream
-
-    def _run_side(self, dev, fn, S=None):
-        side = self._side(dev, S)
-        if side is None:
-            fn(L.stream_ptr())
-            return
-        self._side_used = True
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
-        side.wait_event(ev)
-        with torch.cuda.stream(side):
-            fn(side.cuda_stream)
+    # ---- one backward pass -----------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _backward_pass(self, defer: bool):
+        """The state of one backward pass: ``self._keep``, the buffers its queued kernels still read, and with ``defer`` the deferred
+        weight-gradient window (bpx_wgrad_defer_begin): the step's reductions run as one batched launch at the flush.  The flush runs on
+        every exit, an exception included, and neither the window nor the list outlives the pass."""
+        self._keep, self._deferred = [], defer
+        if defer:
+            L.check(lib.bpx_wgrad_defer_begin())
+        try:
+            yield
+        finally:
+            try:
+                if defer:
+                    L.check(lib.bpx_wgrad_defer_flush(L.stream_ptr()))
+            finally:
+                self._keep, self._deferred = None, False
 
     def _workspace(self, nbytes: int, dev) -> torch.Tensor:
         """Scratch for the wgrad partial sums.  Deferred reductions (backward): one slab per call, kept until the flush.
         Otherwise grow-only (launches are stream-ordered, so one slab is enough)."""
-        if getattr(self, "_deferred", False):
+        if self._deferred:
             ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
             self._keep.append(ws)
             return ws
         if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
-            if self._ws is not None and hasattr(self, "_keep"):
-                self._keep.append(self._ws)   # a side-stream kernel may still be using the old slab
             self._ws = torch.empty(max(nbytes, 32 << 20), dtype=torch.uint8, device=dev)
         return self._ws
+
+    def _grad_slab(self, P: Dict[str, torch.Tensor], dev) -> Dict[str, torch.Tensor]:
+        """Parameter gradients as views of ONE zero-filled fp32 slab in parameter order (the wgrad kernels accumulate into them);
+        the slab is ``self.last_flat_grad``.  BatchNorm running buffers have no gradient."""
+        names = [n for n in P if not n.endswith(_BN_BUFFERS)]
+        flat = torch.zeros(sum(P[n].numel() for n in names), dtype=torch.float32, device=dev)
+        self.last_flat_grad = flat
+        G, o = {}, 0
+        for n in names:
+            G[n] = flat[o:o + P[n].numel()].view(P[n].shape)
+            o += P[n].numel()
+        return G
 
     # ---- sample groups (batch_groups) -------------------------------------------------------------------
     def _groups_for(self, B: int, patch, save: bool) -> List[Tuple[int, int]]:
@@ -551,7 +540,7 @@ class ResUNetEngine:
             else:
                 lo, c = fwd(x=x[a:b], save=save, **kw)
             outs.append(lo)
-            parts.append(((a, b), c, getattr(self, "_prepacked", None)))
+            parts.append(((a, b), c))
         self.last_groups = list(groups)
         return torch.cat(outs, 0), (dict(groups=parts) if save else None)
 
@@ -559,8 +548,7 @@ class ResUNetEngine:
         """The backward of every group in turn (with the packed operands of its own forward); the groups' parameter gradients are summed in
         group order, the input gradient ("__dx__") is concatenated."""
         G, flat, dx = None, None, []
-        for (a, b), c, packed in ctx["groups"]:
-            self._prepacked = packed
+        for (a, b), c in ctx["groups"]:
             Gi = bwd(c, dlogits[a:b])
             if "__dx__" in Gi:
                 dx.append(Gi.pop("__dx__"))
@@ -608,25 +596,58 @@ class ResUNetEngine:
         D, H, W = S
         nb = lib.bpx_conv3d_wgrad_workspace(B, D, H, W, x.C, dy.C, k)
         ws = self._workspace(nb, dev)
-        self._run_side(dev, lambda s_: L.check(lib.bpx_conv3d_wgrad_db2(self.bdt, B, D, H, W, x, L.ptr(rec), act, dy, k, dw.data_ptr(), L.ptr(db),
-                                                                        L.ptr(db2), ws.data_ptr(), ws.numel(), s_)), S)
+        L.check(lib.bpx_conv3d_wgrad_db2(self.bdt, B, D, H, W, x, L.ptr(rec), act, dy, k, dw.data_ptr(), L.ptr(db), L.ptr(db2), ws.data_ptr(), ws.numel(), st))
 
-    def _bwd_fused_ok(self, B, S, Ct: int, Cdy: int) -> bool:
-        """One-pass dgrad + wgrad (bpx_conv3d_bwd_fused) for this conv?  Not with the weight-gradient side stream (its point is one staging)."""
-        if os.environ.get("BPX_FUSED_BITS") is not None and not getattr(self, "_fused_bits_set", False):      # A/B aid: bpx_debug_set_bwd_fused bits
-            lib.bpx_debug_set_bwd_fused(int(os.environ["BPX_FUSED_BITS"]))
-            self._fused_bits_set = True
-        return (os.environ.get("BPX_BWD_FUSED", "1") != "0" and self.act <= 3 and not self.use_side_stream and self.cfg.gn_groups == 0 and self.dtype != torch.float32
+    def _bwd_fused_ok(self, B, S, Ct: int, Cdy: int, act: Optional[int] = None) -> bool:
+        """One-pass dgrad + wgrad (bpx_conv3d_bwd_fused) for this conv, whose prologue applies `act` (default: the network's)?"""
+        act = self.act if act is None else act
+        return (act <= 3 and self.cfg.gn_groups == 0 and self.dtype != torch.float32
                 and bool(lib.bpx_conv3d_bwd_fused_supported(self.bdt, B, S[0], S[1], S[2], Ct, Cdy)))
 
-    def _bwd_fused(self, B, S, dy: "L.Tensor", wt, t: "L.Tensor", rec, g: "L.Tensor", dw, db, db2, st, dev):
+    def _bwd_fused(self, B, S, dy: "L.Tensor", wt, t: "L.Tensor", rec, g: "L.Tensor", dw, db, db2, st, dev, act: Optional[int] = None):
         D, H, W = S
         tiles = lib.bpx_conv3d_bwd_fused_stats_tiles(B, D, H, W, t.C, dy.C)
         red = torch.empty((B, tiles, 2, t.C), dtype=torch.float32, device=dev)
         ws = self._workspace(lib.bpx_conv3d_bwd_fused_workspace(B, D, H, W, t.C, dy.C), dev)
-        L.check(lib.bpx_conv3d_bwd_fused(self.bdt, B, D, H, W, dy, wt.data_ptr(), t, rec.data_ptr(), self.act, g, red.data_ptr(),
+        L.check(lib.bpx_conv3d_bwd_fused(self.bdt, B, D, H, W, dy, wt.data_ptr(), t, rec.data_ptr(), self.act if act is None else act, g, red.data_ptr(),
                                          dw.data_ptr(), L.ptr(db), L.ptr(db2), ws.data_ptr(), ws.numel(), st))
         return tiles, red
+
+    def _norm_act_bwd(self, raw: torch.Tensor, rec, act, dA: "L.Tensor", gamma, dgamma, dbeta, st) -> torch.Tensor:
+        """Backward of a materialised ``act(IN(raw))`` (raw: a dense NDHWC tensor): dA -> d(raw), a new gradient tensor.  The elementwise
+        product with act' and the two InstanceNorm reductions, finalize, apply.  (Mixed mode: raw is the forward's fp16 tensor, d(raw) bf16.)"""
+        B, C, dev = raw.shape[0], raw.shape[-1], raw.device
+        vox = raw.numel() // (B * C)
+        tiles = lib.bpx_norm_act_tiles(self.gdt, vox, C)
+        red = torch.empty((B, tiles, 2, C), dtype=torch.float32, device=dev)
+        g = torch.empty(raw.shape, dtype=self.gdtype, device=dev)
+        L.check(lib.bpx_norm_act_bwd(self.bdt, B, vox, dA, L.tview(raw), rec.data_ptr(), act, L.NULL_T, L.tview(g), red.data_ptr(), st))
+        coef = torch.empty((B, C, 4), dtype=torch.float32, device=dev)
+        L.check(lib.bpx_norm_bwd_finalize(red.data_ptr(), B, tiles, C, vox, rec.data_ptr(), gamma.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), C,
+                                          coef.data_ptr(), st))
+        L.check(lib.bpx_norm_bwd_apply(self.bdt, B, vox, L.tview(g), L.tview(raw), coef.data_ptr(), L.NULL_T, L.tview(g), st))
+        return g
+
+    def _head_bwd(self, G, B, vox, feat: "L.Tensor", hw: torch.Tensor, dl: torch.Tensor, dfeat: "L.Tensor", st, dev) -> None:
+        """Backward of the heads (bpx_head_bwd, the (n_out, fm0) matrix hw on `feat`, fm0 = 16 or 32): the input gradient into dfeat, the
+        weight / bias gradients into G's zeroed ``heads.{h}`` entries - in place for one head, else through one matrix split by rows."""
+        outs = list(self.cfg.out_channels)
+        n_out, fm0 = sum(outs), feat.C
+        one_head = len(outs) == 1
+        hwg = G["heads.0.weight"] if one_head else torch.zeros((n_out, fm0), dtype=torch.float32, device=dev)
+        hbg = G["heads.0.bias"] if one_head else torch.zeros((n_out,), dtype=torch.float32, device=dev)
+        hws = self._workspace(lib.bpx_head_bwd_workspace(fm0, n_out), dev)
+        L.check(lib.bpx_head_bwd(self.bdt, vox, B, feat, hw.data_ptr(), n_out, dl.data_ptr(), n_out * vox, vox, dfeat, hwg.data_ptr(), hbg.data_ptr(),
+                                 hws.data_ptr(), hws.numel(), st))
+        if not one_head:
+            self._split_heads(G, hwg, hbg)
+
+    def _split_heads(self, G, hwg: torch.Tensor, hbg: torch.Tensor) -> None:
+        o = 0
+        for h, oc in enumerate(self.cfg.out_channels):
+            G[f"heads.{h}.weight"].copy_(hwg[o:o + oc].view(G[f"heads.{h}.weight"].shape))
+            G[f"heads.{h}.bias"].copy_(hbg[o:o + oc])
+            o += oc
 
     # ------------------------------------------------------------------------------------------
     def _pack_plan(self, train: bool):
@@ -866,8 +887,8 @@ class ResUNetEngine:
             return torch.empty((B,) + S[i] + (C,), dtype=T, device=dev)
 
         # torch.cat([up, skip], 1) buffers, chunk-planar (L.Planar): the transposed conv and the encoder block write whole planes
-        # instead of 64 / 32 of every 96 bytes, pooling reads a dense plane (A/B switch: self.planar_cat)
-        cat = [L.Planar(B, S[i], fm[i + 1] + fm[i], T, dev) if self.planar_cat else buf(i, fm[i + 1] + fm[i]) for i in range(Lv)]
+        # instead of 64 / 32 of every 96 bytes, pooling reads a dense plane
+        cat = [L.Planar(B, S[i], fm[i + 1] + fm[i], T, dev) for i in range(Lv)]
         blocks: List[_Blk] = []
         pools = []
         out_stats = []
@@ -986,13 +1007,16 @@ class ResUNetEngine:
         ctx = None
         if save:
             ctx = dict(B=B, S=S, So=So, img=img, x_ndhwc=x_ndhwc, blocks=blocks, cat=cat, pools=pools, ups=ups, feat=feat, dec_out=dec_in, hw=hw,
-                       Pw=(P if P is not P_orig else None), want_dx=want_dx, wide_head=wide, bn_running=self._bn_eval is not None)
+                       Pw=(P if P is not P_orig else None), want_dx=want_dx, wide_head=wide, bn_running=self._bn_eval is not None,
+                       prepacked=self._prepacked)
         return logits, ctx
 
     # ------------------------------------------------------------------------------------------
-    def _block_bwd(self, P, G, blk: _Blk, B, dOut: L.Tensor, img, st, dx_extra: Optional[L.Tensor] = None, dx_out: Optional[L.Tensor] = None):
+    def _block_bwd(self, P, G, blk: _Blk, B, dOut: L.Tensor, img, st, dx_extra: Optional[L.Tensor] = None, dx_out: Optional[L.Tensor] = None,
+                   r1_done: bool = False):
         """Backward of one residual block.  dOut: gradient of the block output (T, NDHWC view).
-        Writes parameter grads into G; writes the input gradient into dx_out (a view with blk.cin channels)."""
+        Writes parameter grads into G; writes the input gradient into dx_out (a view with blk.cin channels).  r1_done: the first block's
+        shortcut weight gradient was formed by bpx_maxpool3d_bwd_r1, the pass that wrote dOut (see _backward)."""
         D, H, W = blk.S
         k = blk.keys
         dev = blk.h.device
@@ -1010,23 +1034,20 @@ class ResUNetEngine:
         # decoder blocks at the large levels (round 6): the shortcut's weight gradient rides along in the pass that forms the block's input gradient
         # (bpx_conv1x1_fwd_split_wgrad below streams both of its operands anyway); everywhere else it is a launch of its own
         sc_ws = 0
-        if (isinstance(dx_out, tuple) and blk.rec_x is not None and self._deferred and not self.use_side_stream and self.cfg.gn_groups == 0
+        if (isinstance(dx_out, tuple) and blk.rec_x is not None and self.cfg.gn_groups == 0
                 and dOut.C * 3 == blk.cin and self.dtype != torch.float32):
             # asked with the operands: the kernel's span, pitch and alignment bounds decide too (g0 and coef0 are allocated below, dense)
             sc_ws = int(lib.bpx_conv1x1_fwd_split_wgrad_query(self.bdt, B, vox, dOut, L.Tensor(None, blk.cin, blk.cin, 0),
                                                               L.tview(blk.x, blk.x_c0, blk.cin), None, dx_out[0], dx_out[1]))
         if blk.first and self.cfg.in_ch == 1:
-            if getattr(self, "_r1_done", False):       # formed by bpx_maxpool3d_bwd_r1, the pass that wrote dOut (see _backward)
-                self._r1_done = False
-            else:
+            if not r1_done:
                 ws1 = self._workspace(lib.bpx_conv1x1_c1_wgrad_workspace(C1), dev)
-                self._run_side(dev, lambda s_: L.check(lib.bpx_conv1x1_c1_wgrad(self.gdt, B * vox, img.data_ptr(), dOut, G[k["wsc"]].data_ptr(),
-                                                                                ws1.data_ptr(), ws1.numel(), s_)))
+                L.check(lib.bpx_conv1x1_c1_wgrad(self.gdt, B * vox, img.data_ptr(), dOut, G[k["wsc"]].data_ptr(), ws1.data_ptr(), ws1.numel(), st))
         elif not sc_ws:
             self._wgrad(B, blk.S, L.tview(blk.x, blk.x_c0, blk.cin), None, 0, dOut, 1, G[k["wsc"]], None, st, dev)
         # conv2 dgrad fused with ELU' and the InstanceNorm reductions
         g1 = torch.empty((B, D, H, W, C1), dtype=T, device=dev)
-        self._keep.append(g1)   # read by the side-stream wgrad of conv1
+        self._keep.append(g1)
         w2t = self._pack(P[k["w2"]], L.PK_K3_T, C1, C1, False)
         if dropped:   # plain dgrad -> gradient of the masked activation; then mask, activation derivative and the IN-backward sums in one pass
             L.check(lib.bpx_conv3d_dgrad(self.gdt, B, D, H, W, dOut, w2t.data_ptr(), L.NULL_T, None, 0, L.tview(g1), None, st))
@@ -1049,16 +1070,16 @@ class ResUNetEngine:
             L.check(lib.bpx_batchnorm_bwd_finalize(red.data_ptr(), B, tiles, C1, vox, blk.rec_h.data_ptr(), P[k["g1"]].data_ptr(), G[k["g1"]].data_ptr(),
                                                    G[k["be1"]].data_ptr(), self._bn_running, coef.data_ptr(), st))
         else:
-            L.check(_NBF(red.data_ptr(), B, tiles, C1, vox, blk.rec_h.data_ptr(), P[k["g1"]].data_ptr(),
-                         G[k["g1"]].data_ptr(), G[k["be1"]].data_ptr(), self.cfg.gn_groups or C1, coef.data_ptr(), st))
+            L.check(lib.bpx_norm_bwd_finalize_deferred(red.data_ptr(), B, tiles, C1, vox, blk.rec_h.data_ptr(), P[k["g1"]].data_ptr(),
+                                                       G[k["g1"]].data_ptr(), G[k["be1"]].data_ptr(), self.cfg.gn_groups or C1, coef.data_ptr(), st))
         first_c1 = blk.first and self.cfg.in_ch == 1
-        if first_c1 and lib.bpx_conv3d_c1_wgrad_nb_supported(self.bdt, W) and os.environ.get("BPX_C1_NB", "1") != "0":
+        if first_c1 and lib.bpx_conv3d_c1_wgrad_nb_supported(self.bdt, W):
             # the first layer has no input gradient: its weight gradient is the only reader of dH = a * g1 + b * h + c0, which is therefore formed
             # inside that kernel and never stored (bpx_norm_bwd_apply's pass over three tensor units is gone)
             wsc = self._workspace(lib.bpx_conv3d_c1_wgrad_workspace(C1), dev)
             self._keep.append(coef)
-            self._run_side(dev, lambda s_: L.check(lib.bpx_conv3d_c1_wgrad_nb(self.bdt, B, D, H, W, img.data_ptr(), L.tview(g1), L.tview(blk.h), coef.data_ptr(),
-                                                                              G[k["w1"]].data_ptr(), G[k["b1"]].data_ptr(), wsc.data_ptr(), wsc.numel(), s_)))
+            L.check(lib.bpx_conv3d_c1_wgrad_nb(self.bdt, B, D, H, W, img.data_ptr(), L.tview(g1), L.tview(blk.h), coef.data_ptr(),
+                                               G[k["w1"]].data_ptr(), G[k["b1"]].data_ptr(), wsc.data_ptr(), wsc.numel(), st))
             self._keep.append(g1)
             return
         L.check(lib.bpx_norm_bwd_apply(self.bdt, B, vox, L.tview(g1), L.tview(blk.h), coef.data_ptr(), L.NULL_T, L.tview(g1), st))
@@ -1066,8 +1087,8 @@ class ResUNetEngine:
         # conv1
         if first_c1:
             wsc = self._workspace(lib.bpx_conv3d_c1_wgrad_workspace(C1), dev)
-            self._run_side(dev, lambda s_: L.check(lib.bpx_conv3d_c1_wgrad(self.gdt, B, D, H, W, img.data_ptr(), dH, G[k["w1"]].data_ptr(),
-                                                                           G[k["b1"]].data_ptr(), wsc.data_ptr(), wsc.numel(), s_)))
+            L.check(lib.bpx_conv3d_c1_wgrad(self.gdt, B, D, H, W, img.data_ptr(), dH, G[k["w1"]].data_ptr(), G[k["b1"]].data_ptr(),
+                                            wsc.data_ptr(), wsc.numel(), st))
             self._keep.append(g1)
             return
         xv = L.tview(blk.x, blk.x_c0, blk.cin)
@@ -1102,7 +1123,7 @@ class ResUNetEngine:
                                                        G[k["be0"]].data_ptr(), gng, coef0.data_ptr(), st))
             else:
                 self._keep.append(red0)
-                L.check(_NBF(red0.data_ptr(), B, tiles0, Cx, vox, blk.rec_x.data_ptr(), P[k["g0"]].data_ptr(),
+                L.check(lib.bpx_norm_bwd_finalize_deferred(red0.data_ptr(), B, tiles0, Cx, vox, blk.rec_x.data_ptr(), P[k["g0"]].data_ptr(),
                                                            G[k["g0"]].data_ptr(), G[k["be0"]].data_ptr(), gng or Cx, coef0.data_ptr(), st))
             if isinstance(dx_out, tuple):   # decoder block: the gradient of the concatenated input leaves as its (up, skip) parts
                 assert dx_extra is None
@@ -1128,35 +1149,20 @@ class ResUNetEngine:
         several sample groups (batch_groups) calls it once, after the last group: only then are the summed gradients final."""
         if ctx is not None and "groups" in ctx:
             return self._backward_groups(ctx, dlogits, lambda c, d: self.backward(P, c, d), on_last_block)
-        self._on_last_block = on_last_block
-        self._keep = []   # buffers the side stream may still be reading; released after the final stream join
-        # the ~29 weight-gradient reductions of a step run as one batched launch at the end (they are latency chains of a
-        # few hundred blocks each; back to back they cost 0.6 ms).  Not with the side stream: the flush is stream-ordered.
-        self._deferred = not self.use_side_stream      # (the small-level side branch is joined at the end of _backward, before the flush)
-        self._side_used = False
-        self._after_flush = []
-        if self._deferred:
-            L.check(lib.bpx_wgrad_defer_begin())
+        self._prepacked = ctx["prepacked"]                          # the packed operands of this context's own forward
         Pw = ctx.get("Pw")
         self._bn_running = int(ctx.get("bn_running", False))      # BatchNorm: the forward normalised with the running statistics (eval mode)
-        try:
-            G = self._backward(P if Pw is None else Pw, ctx, dlogits)
-        finally:
-            self._on_last_block = None
-            if self._deferred:
-                self._deferred = False
-                L.check(lib.bpx_wgrad_defer_flush(L.stream_ptr()))
-            self._keep = []
-        for fn in self._after_flush:
-            fn()
-        self._after_flush = []
+        # the ~29 weight-gradient reductions of a step run as one batched launch at the end (they are latency chains of a
+        # few hundred blocks each; back to back they cost 0.6 ms)
+        with self._backward_pass(defer=True):
+            G = self._backward(P if Pw is None else Pw, ctx, dlogits, on_last_block)
         if Pw is None:
             return G
         if self._pad_plan is not None:                        # zero-padded widths: the parameters' own rows / columns of the padded gradients
             G = unpad_channel_grads(G, self._pad_plan)
         return unlift_grads(G, P)                            # after the flush: it is the flush that writes the conv gradients
 
-    def _backward(self, P: Dict[str, torch.Tensor], ctx, dlogits: torch.Tensor) -> Dict[str, torch.Tensor]:
+    def _backward(self, P: Dict[str, torch.Tensor], ctx, dlogits: torch.Tensor, on_last_block) -> Dict[str, torch.Tensor]:
         cfg = self.cfg
         B, S, img = ctx["B"], ctx["S"], ctx["img"]
         blocks: List[_Blk] = ctx["blocks"]
@@ -1166,15 +1172,7 @@ class ResUNetEngine:
         dev = dlogits.device
         st = L.stream_ptr()
         T = self.gdtype
-        names = [n for n in P if not n.endswith(_BN_BUFFERS)]       # BatchNorm running buffers have no gradient
-        sizes = [P[n].numel() for n in names]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
-        self.last_flat_grad = flat
-        G: Dict[str, torch.Tensor] = {}
-        o = 0
-        for n, s in zip(names, sizes):
-            G[n] = flat[o:o + s].view(P[n].shape)
-            o += s
+        G = self._grad_slab(P, dev)
         # ---- head -------------------------------------------------------------------------------
         n_out = sum(cfg.out_channels)
         D0, H0, W0 = S[0]
@@ -1182,18 +1180,13 @@ class ResUNetEngine:
         vox0 = So[0] * So[1] * So[2]
         dl = dlogits.contiguous().float()
         dfeat = torch.empty((B,) + tuple(So) + (fm[0],), dtype=T, device=dev)
-        one_head = len(cfg.out_channels) == 1                     # its gradients are written in place (G is zeroed); several heads: split below
-        hwg = G["heads.0.weight"] if one_head else torch.zeros((n_out, fm[0]), dtype=torch.float32, device=dev)
-        hbg = G["heads.0.bias"] if one_head else torch.zeros((n_out,), dtype=torch.float32, device=dev)
         wide = ctx.get("wide_head")
         if wide is None:
-            hws = self._workspace(lib.bpx_head_bwd_workspace(fm[0], n_out), dev)
-            L.check(lib.bpx_head_bwd(self.bdt, vox0, B, L.tview(feat), ctx["hw"].data_ptr(), n_out, dl.data_ptr(), n_out * vox0, vox0,
-                                     L.tview(dfeat), hwg.data_ptr(), hbg.data_ptr(), hws.data_ptr(), hws.numel(), st))
+            self._head_bwd(G, B, vox0, L.tview(feat), ctx["hw"], dl, L.tview(dfeat), st, dev)
         else:
             # wide head (forward above): the head kernel's backward on the 16-channel tensor gives its gradient (the identity pick's own gradients are
             # discarded), then the 1x1x1 convolution's two gradients: k = 1 wgrad (rows 0 .. n_out of the padded matrix are the heads') and the
-            # pointwise GEMM with the transposed matrix.  The weight gradient is reduced right away (not with the step's batch): it is copied below.
+            # pointwise GEMM with the transposed matrix.  The weight gradient is reduced right away (not with the step's batch): its heads' rows are copied out at once.
             do16 = torch.empty((B,) + tuple(So) + (16,), dtype=T, device=dev)
             eg, ebg = torch.zeros((n_out, 16), dtype=torch.float32, device=dev), torch.zeros((n_out,), dtype=torch.float32, device=dev)
             hws = self._workspace(lib.bpx_head_bwd_workspace(16, n_out), dev)
@@ -1203,12 +1196,10 @@ class ResUNetEngine:
             db16 = torch.zeros((16,), dtype=torch.float32, device=dev)
             ws16 = self._workspace(lib.bpx_conv3d_wgrad_workspace(B, So[0], So[1], So[2], fm[0], 16, 1), dev)
             L.check(lib.bpx_conv3d_wgrad_db2(self.bdt, B, So[0], So[1], So[2], L.tview(feat), None, 0, L.tview(do16), 1, dw16.data_ptr(), db16.data_ptr(), None,
-                                             ws16.data_ptr(), ws16.numel(), st))         # on this stream (not the optional side stream): read right below
-            if self._deferred:
-                L.check(lib.bpx_wgrad_defer_flush(L.stream_ptr()))
-                L.check(lib.bpx_wgrad_defer_begin())
-            hwg.view(n_out, fm[0]).copy_(dw16.view(16, fm[0])[:n_out])
-            hbg.copy_(db16[:n_out])
+                                             ws16.data_ptr(), ws16.numel(), st))
+            L.check(lib.bpx_wgrad_defer_flush(L.stream_ptr()))
+            L.check(lib.bpx_wgrad_defer_begin())
+            self._split_heads(G, dw16.view(16, fm[0])[:n_out], db16[:n_out])
             wt16 = self._pack(wide["w16"], L.PK_DENSE_T, fm[0], 16, False)
             L.check(lib.bpx_conv1x1_fwd(self.gdt, B, vox0, L.tview(do16), wt16.data_ptr(), None, L.NULL_T, L.NULL_T, None, L.NULL_T, L.tview(dfeat), st))
             self._keep += [do16, dw16, db16, eg, ebg]
@@ -1222,11 +1213,6 @@ class ResUNetEngine:
             wt = self._pack(P["post_upsampling.weight"], L.PK_CT_T if cfg.post_up == 2 else L.PK_CT4_T, fm[0], fm[0], False)
             L.check(lib.bpx_convT3d_k2s2_dgrad(self.gdt, B, D0, H0, W0, cfg.post_up, L.tview(dup_feat), wt.data_ptr(), L.tview(dfeat), st))
             self._keep.append(dup_feat)
-        o = 0
-        for h, oc in enumerate(cfg.out_channels if not one_head else ()):
-            G[f"heads.{h}.weight"].copy_(hwg[o:o + oc].view(G[f"heads.{h}.weight"].shape))
-            G[f"heads.{h}.bias"].copy_(hbg[o:o + oc])
-            o += oc
         # ---- decoder (blocks list: enc 0..Lv-1, bottleneck, dec j=0..Lv-1 for levels Lv-1..0) -------
         dskip: List[Optional[torch.Tensor]] = [None] * Lv      # d(concat) leaves the decoder block as two dense tensors
         dOut = L.tview(dfeat)
@@ -1243,8 +1229,8 @@ class ResUNetEngine:
             dUp = L.tview(dup)
             wsn = lib.bpx_convT3d_k2s2_wgrad_workspace(B, Sl[0], Sl[1], Sl[2], szl, Cup, Cup)
             ws = self._workspace(wsn, dev)
-            self._run_side(dev, lambda s_, x_in=x_in, dUp=dUp, wk=wk, bk=bk, Sl=Sl, ws=ws, szl=szl: L.check(lib.bpx_convT3d_k2s2_wgrad(
-                self.bdt, B, Sl[0], Sl[1], Sl[2], szl, L.tview(x_in), dUp, G[wk].data_ptr(), G[bk].data_ptr(), ws.data_ptr(), ws.numel(), s_)), Sl)
+            L.check(lib.bpx_convT3d_k2s2_wgrad(self.bdt, B, Sl[0], Sl[1], Sl[2], szl, L.tview(x_in), dUp, G[wk].data_ptr(), G[bk].data_ptr(),
+                                               ws.data_ptr(), ws.numel(), st))
             dxin = torch.empty((B,) + Sl + (Cup,), dtype=T, device=dev)
             wt = self._pack(P[wk], L.PK_CT_T if szl == 2 else L.PK_CT4_T, Cup, Cup, False)
             L.check(lib.bpx_convT3d_k2s2_dgrad(self.gdt, B, Sl[0], Sl[1], Sl[2], szl, dUp, wt.data_ptr(), L.tview(dxin), st))
@@ -1260,21 +1246,20 @@ class ResUNetEngine:
             # dOut_i = dSkip + unpool(dP); written in place over dSkip
             skipv = L.tview(dskip[i])
             r1_ws = 0
-            if i == 0 and cfg.in_ch == 1 and self._deferred and not self.use_side_stream and self.dtype != torch.float32:
+            if i == 0 and cfg.in_ch == 1 and self.dtype != torch.float32:
                 # level 0 of a one-channel-image network (round 6): the first block's rank-1 shortcut weight gradient is a sum over the tensor this pass writes
                 r1_ws = int(lib.bpx_maxpool3d_bwd_r1_workspace(self.bdt, B, D, H, W, cfg.z_down[i], fm[i]))
             if r1_ws:
                 wsr = self._workspace(r1_ws, dev)
                 L.check(lib.bpx_maxpool3d_bwd_r1(self.bdt, B, D, H, W, cfg.z_down[i], L.tview(cat[i], Cup, fm[i]), L.tview(dP), skipv, skipv, img.data_ptr(),
                                                  G[blocks[0].keys["wsc"]].data_ptr(), wsr.data_ptr(), wsr.numel(), st))
-                self._r1_done = True
             else:
                 L.check(lib.bpx_maxpool3d_bwd(self.bdt, B, D, H, W, cfg.z_down[i], L.tview(cat[i], Cup, fm[i]), L.tview(dP), skipv, skipv, st))
-            if i == 0 and getattr(self, "_on_last_block", None) is not None:
-                if self._deferred:      # the reductions queued so far write their gradients now; the last block's are queued afresh
-                    L.check(lib.bpx_wgrad_defer_flush(L.stream_ptr()))
-                    L.check(lib.bpx_wgrad_defer_begin())
-                self._on_last_block()
+            if i == 0 and on_last_block is not None:
+                # the reductions queued so far write their gradients now; the last block's are queued afresh
+                L.check(lib.bpx_wgrad_defer_flush(L.stream_ptr()))
+                L.check(lib.bpx_wgrad_defer_begin())
+                on_last_block()
             if i > 0:
                 dPn = torch.empty((B,) + S[i] + (fm[i - 1],), dtype=T, device=dev)
                 self._block_bwd(P, G, blocks[i], B, skipv, img, st, None, L.tview(dPn))
@@ -1282,10 +1267,8 @@ class ResUNetEngine:
                 dP = dPn
             elif ctx.get("want_dx"):
                 dx0 = torch.empty((B,) + S[0] + (cfg.in_ch,), dtype=T, device=dev)
-                self._block_bwd(P, G, blocks[0], B, skipv, img, st, None, L.tview(dx0))
+                self._block_bwd(P, G, blocks[0], B, skipv, img, st, None, L.tview(dx0), r1_done=bool(r1_ws))
                 G["__dx__"] = dx0
             else:
-                self._block_bwd(P, G, blocks[0], B, skipv, img, st, None, None)  # the image needs no gradient
-        if self._side_used and self._side_stream is not None:
-            torch.cuda.current_stream(dev).wait_stream(self._side_stream)
+                self._block_bwd(P, G, blocks[0], B, skipv, img, st, None, None, r1_done=bool(r1_ws))  # the image needs no gradient
         return G

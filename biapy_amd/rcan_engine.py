@@ -22,7 +22,6 @@ Weights are packed with one launch per step from the second step on (``ResUNetEn
 """
 from __future__ import annotations
 
-import os
 from typing import Dict
 
 import torch
@@ -63,7 +62,7 @@ class RCANEngine(ResUNetEngine):
         super().__init__(NetConfig(in_ch=1, feature_maps=[filters, filters], out_channels=(out_channels,), activation="silu"), dtype)
         self.Fc, self.num_rg, self.num_rcab, self.red, self.n_out = filters, num_rg, num_rcab, max(1, filters // reduction), out_channels
         self.silu = L.ACT["silu"]
-        self.up_group = int(os.environ.get("BPX_RCAN_UP_GROUP", "8"))   # sub-positions per backward call of the x scale stage (8: 128-channel blocks; 1: 16-channel blocks)
+        self.up_group = 8                # sub-positions per backward call of the x scale stage (8: 128-channel blocks; 1: 16-channel blocks)
         self.scale = int(scale)          # > 0: conv(filters -> filters * scale^3) + 3-D pixel shuffle in front of the last conv (rcan.py:344-345)
         if self.scale and (filters != 16 or self.scale not in (2, 3, 4) or dtype == torch.float32):
             raise NotImplementedError("RCANEngine: the up-scaling stage needs 16 filters, scale 2..4 and 16-bit storage (bpx_conv3d_fwd_shuffle)")
@@ -176,15 +175,8 @@ class RCANEngine(ResUNetEngine):
         # T: storage type of the gradient tensors (bf16 in the mixed mode, compute_dtype float16: the forward tensors are fp16 - engine.ResUNetEngine's
         # codes: gdt = kernels on gradient tensors only, bdt = backward kernels that also read a forward tensor)
         vox, Fc, T, dev, st, c = D * H * W, self.Fc, self.gdtype, dy_out.device, L.stream_ptr(), self._c
-        self._keep = []
-        flat = torch.zeros(sum(p.numel() for p in P.values()), dtype=torch.float32, device=dev)   # ONE fill for the ~1,650 parameter gradients
-        G, o = {}, 0
-        for n, p in P.items():
-            G[n] = flat[o:o + p.numel()].view(p.shape)
-            o += p.numel()
-        self._deferred = True
-        L.check(lib.bpx_wgrad_defer_begin())
-        try:
+        G = self._grad_slab(P, dev)                                          # ONE fill for the ~1,650 parameter gradients
+        with self._backward_pass(defer=True):
             def buf(C=Fc):
                 t_ = torch.empty((B, D, H, W, C), dtype=T, device=dev)
                 self._keep.append(t_)
@@ -271,9 +263,6 @@ class RCANEngine(ResUNetEngine):
             wsc = self._workspace(lib.bpx_conv3d_c1_wgrad_workspace(self.Fc), dev)
             L.check(lib.bpx_conv3d_c1_wgrad(self.gdt, B, D, H, W, ctx["img"].data_ptr(), L.tview(df0), G["sf.weight"].data_ptr(), G["sf.bias"].data_ptr(),
                                             wsc.data_ptr(), wsc.numel(), st))
-        finally:
-            self._deferred = False
-            L.check(lib.bpx_wgrad_defer_flush(st))
         G["conv2.weight"].copy_(dw16[: self.n_out])
         G["conv2.bias"].copy_(db16[: self.n_out])
         if self.scale:                                                       # rows back from [sub-position][channel] to PyTorch's [channel][sub-position]
@@ -281,5 +270,4 @@ class RCANEngine(ResUNetEngine):
             gw, gb = rows_from_subposition_major(dwu, dbu, Fc, s3)
             G["upscale.0.weight"].copy_(gw)
             G["upscale.0.bias"].copy_(gb)
-        self._keep = []
         return G

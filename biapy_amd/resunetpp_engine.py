@@ -33,8 +33,6 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
-import os
-
 import torch
 
 from . import _lib as L
@@ -174,17 +172,7 @@ class ResUNetPPEngine(ResUNetEngine):
 
     def _in_bwd(self, raw: _V, rec, act, dA: torch.Tensor, gamma, dgamma, dbeta) -> torch.Tensor:
         """Backward of a materialised ``act(IN(raw))``: dA (dense) -> d(raw)."""
-        B, C, vox = self._B, raw.C, raw.vox
-        # (mixed mode: raw is the forward pass's fp16 tensor, every gradient tensor bf16 - engine.ResUNetEngine's codes: gdt = kernels on gradient
-        #  tensors only, bdt = backward kernels that also read a forward tensor)
-        tiles = lib.bpx_norm_act_tiles(self.gdt, vox, C)
-        red = torch.empty((B, tiles, 2, C), dtype=torch.float32, device=self._dev)
-        g = torch.empty((B,) + raw.S + (C,), dtype=self.gdtype, device=self._dev)
-        L.check(lib.bpx_norm_act_bwd(self.bdt, B, vox, L.tview(dA), raw.view(), rec.data_ptr(), act, L.NULL_T, L.tview(g), red.data_ptr(), self._st))
-        coef = torch.empty((B, C, 4), dtype=torch.float32, device=self._dev)
-        L.check(lib.bpx_norm_bwd_finalize(red.data_ptr(), B, tiles, C, vox, rec.data_ptr(), gamma.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), C,
-                                          coef.data_ptr(), self._st))
-        L.check(lib.bpx_norm_bwd_apply(self.bdt, B, vox, L.tview(g), raw.view(), coef.data_ptr(), L.NULL_T, L.tview(g), self._st))
+        g = self._norm_act_bwd(raw.buf, rec, act, L.tview(dA), gamma, dgamma, dbeta, self._st)
         self._keep.append(dA)
         return g
 
@@ -213,20 +201,15 @@ class ResUNetPPEngine(ResUNetEngine):
         if G is not None:
             def bwd():
                 dy = L.tview(y.grad)
-                fused = (nrm is not None and nrm.act <= 3 and os.environ.get("BPX_BWD_FUSED", "1") != "0" and self.dtype != torch.float32 and not self.use_side_stream
-                         and x.view().cs == 0 and bool(lib.bpx_conv3d_bwd_fused_supported(self.bdt, B, D, H, W, x.C, Cout)))
+                fused = nrm is not None and x.view().cs == 0 and self._bwd_fused_ok(B, x.S, x.C, Cout, nrm.act)
                 if not fused:
                     self._wgrad(B, x.S, x.view(), nrm.rec if nrm else None, nrm.act if nrm else 0, dy, 3, G[wk], G[bk], self._st, self._dev)
                 wt = self._pack(P[wk], L.PK_K3_T, x.C, Cout, False)
                 g = torch.empty((B, D, H, W, x.C), dtype=self.gdtype, device=self._dev)
-                if nrm is not None and fused:
+                if fused:
                     # round 5 (first part): dgrad (+ act', + IN-backward sums) and wgrad (+ bias gradient) of the conv in ONE pass
                     # over (dy, x) - the level-0 / level-1 shapes the cfg-2 engine fuses too (bpx_conv3d_bwd_fused_supported)
-                    rt = lib.bpx_conv3d_bwd_fused_stats_tiles(B, D, H, W, x.C, Cout)
-                    red = torch.empty((B, rt, 2, x.C), dtype=torch.float32, device=self._dev)
-                    ws = self._workspace(lib.bpx_conv3d_bwd_fused_workspace(B, D, H, W, x.C, Cout), self._dev)
-                    L.check(lib.bpx_conv3d_bwd_fused(self.bdt, B, D, H, W, dy, wt.data_ptr(), x.view(), nrm.rec.data_ptr(), nrm.act, L.tview(g), red.data_ptr(),
-                                                     G[wk].data_ptr(), G[bk].data_ptr(), None, ws.data_ptr(), ws.numel(), self._st))
+                    rt, red = self._bwd_fused(B, x.S, dy, wt, x.view(), nrm.rec, L.tview(g), G[wk], G[bk], None, self._st, self._dev, nrm.act)
                 elif nrm is not None:
                     rt = lib.bpx_conv3d_stats_tiles(self.dt, B, D, H, W, x.C)
                     red = torch.empty((B, rt, 2, x.C), dtype=torch.float32, device=self._dev)
@@ -538,16 +521,7 @@ class ResUNetPPEngine(ResUNetEngine):
         self._B, self._dev, self._st, self._P = B, x.device, L.stream_ptr(), P
         self._begin_recorded_packs(P, save, x.device, cache_weights)   # one batched weight-pack launch from the second step on
         self._tape: List[Callable[[], None]] = []
-        self._late: List[Callable[[], None]] = []
-        self._keep = []
-        self._G = None
-        if save:
-            names = list(P.keys())
-            flat = torch.zeros(sum(P[n].numel() for n in names), dtype=torch.float32, device=x.device)
-            self._G, o = {}, 0
-            for n in names:
-                self._G[n] = flat[o:o + P[n].numel()].view(P[n].shape)
-                o += P[n].numel()
+        self._G = self._grad_slab(P, x.device) if save else None
         img = x.reshape(B, D0, H0, W0).contiguous()
         S = [(D0, H0, W0)]
         for i in range(1, depth + 1):
@@ -585,48 +559,31 @@ class ResUNetPPEngine(ResUNetEngine):
         if save:
             # the packed operands and the parameter versions they were made from travel with the context: a later forward() replaces the
             # engine's own map, and an optimizer step between this forward and its backward would leave the map stale
-            ctx = dict(tape=self._tape, late=self._late, G=self._G, feat=feat, hw=hw, B=B, S0=S[0], P=P, prepacked=self._prepacked,
+            ctx = dict(tape=self._tape, G=self._G, feat=feat, hw=hw, B=B, S0=S[0], P=P, prepacked=self._prepacked,
                        pack_names=self._pack_names, pack_seen=self._pack_seen, versions={n: t._version for n, t in P.items()})
-        self._tape, self._late, self._G = [], [], None
-        self._keep = []
+        self._tape, self._G = [], None
         return logits, ctx
 
     def backward(self, P: Dict[str, torch.Tensor], ctx, dlogits: torch.Tensor) -> Dict[str, torch.Tensor]:
         cfg = self.pp
         B, feat, G = ctx["B"], ctx["feat"], ctx["G"]
         self._B, self._dev, self._st, self._P, self._G = B, dlogits.device, L.stream_ptr(), ctx["P"], G
-        self._late = ctx["late"]
-        self._keep = []
         stale = [n for n, v in ctx["versions"].items() if ctx["P"][n]._version != v]
         if stale:
             raise RuntimeError(f"ResUNet++ backward: {len(stale)} parameters (first: {stale[0]}) were modified in place after the forward pass of this context")
         self._prepacked, self._pack_names, self._pack_seen = ctx["prepacked"], ctx["pack_names"], ctx["pack_seen"]
-        fm = list(cfg.feature_maps)
-        n_out = sum(cfg.out_channels)
         D0, H0, W0 = ctx["S0"]
-        vox0 = D0 * H0 * W0
-        self._deferred = True
-        L.check(lib.bpx_wgrad_defer_begin())
+        late = self._late = []                                         # gradients of padded / re-shaped weights: copied after the flush wrote them
         try:
-            dl = dlogits.contiguous().float()
-            feat.grad = torch.empty((B, D0, H0, W0, fm[0]), dtype=self.gdtype, device=self._dev)
-            hwg = torch.zeros((n_out, fm[0]), dtype=torch.float32, device=self._dev)
-            hbg = torch.zeros((n_out,), dtype=torch.float32, device=self._dev)
-            hws = self._workspace(lib.bpx_head_bwd_workspace(fm[0], n_out), self._dev)
-            L.check(lib.bpx_head_bwd(self.bdt, vox0, B, feat.view(), ctx["hw"].data_ptr(), n_out, dl.data_ptr(), n_out * vox0, vox0, L.tview(feat.grad),
-                                     hwg.data_ptr(), hbg.data_ptr(), hws.data_ptr(), hws.numel(), self._st))
-            o = 0
-            for h, oc in enumerate(cfg.out_channels):
-                G[f"heads.{h}.weight"].copy_(hwg[o:o + oc].view(G[f"heads.{h}.weight"].shape))
-                G[f"heads.{h}.bias"].copy_(hbg[o:o + oc])
-                o += oc
-            for fn in reversed(ctx["tape"]):
-                fn()
+            with self._backward_pass(defer=True):
+                dl = dlogits.contiguous().float()
+                feat.grad = torch.empty((B, D0, H0, W0, cfg.feature_maps[0]), dtype=self.gdtype, device=self._dev)
+                self._head_bwd(G, B, D0 * H0 * W0, feat.view(), ctx["hw"], dl, L.tview(feat.grad), self._st, self._dev)
+                for fn in reversed(ctx["tape"]):
+                    fn()
         finally:
-            self._deferred = False
-            L.check(lib.bpx_wgrad_defer_flush(self._st))
-        for fn in self._late:                                          # gradients of padded / re-shaped weights: copied after the flush wrote them
+            self._late, self._G = None, None
+        for fn in late:
             fn()
-        self._keep, self._late, self._G = [], [], None
         ctx["tape"] = []
         return G

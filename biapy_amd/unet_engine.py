@@ -174,27 +174,13 @@ class UNetEngine(ResUNetEngine):
         return logits, ctx
 
     # ---- backward -------------------------------------------------------------------------------------------------------
-    def _norm_act_bwd(self, B, vox, C, dA, raw, rec, gamma, dgamma, dbeta, st, dev):
-        """d(act(IN(raw))) -> d(raw): elementwise product with act' + the two InstanceNorm reductions, finalize, apply."""
-        # (mixed mode, compute_dtype float16: `raw` is the forward pass's fp16 tensor, every gradient tensor bf16 - the codes of engine.ResUNetEngine:
-        #  gdt = kernels that touch gradient tensors only, bdt = backward kernels that also read a forward activation)
-        tiles = lib.bpx_norm_act_tiles(self.gdt, vox, C)
-        red = torch.empty((B, tiles, 2, C), dtype=torch.float32, device=dev)
-        g = torch.empty(raw.shape, dtype=self.gdtype, device=dev)
-        L.check(lib.bpx_norm_act_bwd(self.bdt, B, vox, dA, L.tview(raw), rec.data_ptr(), self.act, L.NULL_T, L.tview(g), red.data_ptr(), st))
-        coef = torch.empty((B, C, 4), dtype=torch.float32, device=dev)
-        L.check(lib.bpx_norm_bwd_finalize(red.data_ptr(), B, tiles, C, vox, rec.data_ptr(), gamma.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), C,
-                                          coef.data_ptr(), st))
-        L.check(lib.bpx_norm_bwd_apply(self.bdt, B, vox, L.tview(g), L.tview(raw), coef.data_ptr(), L.NULL_T, L.tview(g), st))
-        return g
-
     def _conv_block_bwd(self, Pw, G, cb: _CB, B, dA: "L.Tensor", img, dx_out: Optional["L.Tensor"], st, dev):
         D, H, W = cb.S
         vox = D * H * W
         p, C1 = cb.prefix, cb.cout
         k = lambda c, leaf: f"{p}.block.{c}.block.{leaf}"   # noqa: E731
         # output norm+act of the last conv
-        g2 = self._norm_act_bwd(B, vox, C1, dA, cb.h[1], cb.rec[1], Pw[k(1, "1.weight")], G[k(1, "1.weight")], G[k(1, "1.bias")], st, dev)
+        g2 = self._norm_act_bwd(cb.h[1], cb.rec[1], self.act, dA, Pw[k(1, "1.weight")], G[k(1, "1.weight")], G[k(1, "1.bias")], st)
         self._keep.append(g2)
         # conv 2: weights, then the input gradient fused with act' and the reductions of the first norm
         self._wgrad(B, cb.S, L.tview(cb.h[0]), cb.rec[0], self.act, L.tview(g2), 3, G[k(1, "0.weight")], G[k(1, "0.bias")], st, dev)
@@ -223,37 +209,24 @@ class UNetEngine(ResUNetEngine):
     def backward(self, P: Dict[str, torch.Tensor], ctx, dlogits: torch.Tensor) -> Dict[str, torch.Tensor]:
         if "groups" in ctx:
             return self._backward_groups(ctx, dlogits, lambda c, d: self.backward(P, c, d))
+        Pw = ctx["Pw"]
+        with self._backward_pass(defer=False):
+            G = self._grad_slab(Pw, dlogits.device)        # in the LIFTED shapes, un-lifted at the end
+            self._backward(Pw, G, ctx, dlogits)
+        return unlift_grads(G, P)   # gradients in the shapes of the module's parameters
+
+    def _backward(self, Pw, G, ctx, dlogits: torch.Tensor) -> None:
         cfg = self.cfg
-        B, S, zd, img, Pw = ctx["B"], ctx["S"], ctx["zd"], ctx["img"], ctx["Pw"]
+        B, S, zd, img = ctx["B"], ctx["S"], ctx["zd"], ctx["img"]
         blocks: List[_CB] = ctx["blocks"]
         cat, ups, feat = ctx["cat"], ctx["ups"], ctx["feat"]
         fm, Lv = list(cfg.feature_maps), cfg.depth
         dev, st, T = dlogits.device, L.stream_ptr(), self.gdtype       # T: storage type of the gradient tensors
-        self._keep = []
-        # parameter gradients in the LIFTED shapes (one zero-filled slab: the wgrad kernels accumulate), un-lifted at the end
-        names = list(Pw.keys())
-        flat = torch.zeros(sum(Pw[n].numel() for n in names), dtype=torch.float32, device=dev)
-        G: Dict[str, torch.Tensor] = {}
-        o = 0
-        for n in names:
-            G[n] = flat[o:o + Pw[n].numel()].view(Pw[n].shape)
-            o += Pw[n].numel()
         # ---- head -------------------------------------------------------------------------------
-        n_out = sum(cfg.out_channels)
         D0, H0, W0 = S[0]
-        vox0 = D0 * H0 * W0
         dl = dlogits.contiguous().float()
         dfeat = torch.empty((B, D0, H0, W0, fm[0]), dtype=T, device=dev)
-        hwg = torch.zeros((n_out, fm[0]), dtype=torch.float32, device=dev)
-        hbg = torch.zeros((n_out,), dtype=torch.float32, device=dev)
-        hws = self._workspace(lib.bpx_head_bwd_workspace(fm[0], n_out), dev)
-        L.check(lib.bpx_head_bwd(self.bdt, vox0, B, L.tview(feat), ctx["hw"].data_ptr(), n_out, dl.data_ptr(), n_out * vox0, vox0,
-                                 L.tview(dfeat), hwg.data_ptr(), hbg.data_ptr(), hws.data_ptr(), hws.numel(), st))
-        o = 0
-        for h, oc in enumerate(cfg.out_channels):
-            G[f"heads.{h}.weight"].copy_(hwg[o:o + oc].view(G[f"heads.{h}.weight"].shape))
-            G[f"heads.{h}.bias"].copy_(hbg[o:o + oc])
-            o += oc
+        self._head_bwd(G, B, D0 * H0 * W0, L.tview(feat), ctx["hw"], dl, L.tview(dfeat), st, dev)
         # ---- decoder: walk from level 0 down to the bottleneck ---------------------------------------------------------
         dcat: List[Optional[torch.Tensor]] = [None] * Lv
         dA = L.tview(dfeat)
@@ -264,8 +237,8 @@ class UNetEngine(ResUNetEngine):
             self._conv_block_bwd(Pw, G, blocks[Lv + 1 + j], B, dA, None, L.tview(dcat[i]), st, dev)
             vox = S[i][0] * S[i][1] * S[i][2]
             pre = f"up_paths.0.{j}.up"
-            dup = self._norm_act_bwd(B, vox, Cup, L.tview(dcat[i], 0, Cup), up_raw, urec, Pw[f"{pre}.1.weight"], G[f"{pre}.1.weight"],
-                                     G[f"{pre}.1.bias"], st, dev)
+            dup = self._norm_act_bwd(up_raw, urec, self.act, L.tview(dcat[i], 0, Cup), Pw[f"{pre}.1.weight"], G[f"{pre}.1.weight"],
+                                     G[f"{pre}.1.bias"], st)
             keep.append(dup)
             Dl, Hl, Wl = S[i + 1]
             ws = self._workspace(lib.bpx_convT3d_k2s2_wgrad_workspace(B, Dl, Hl, Wl, zd[i], Cl, Cup), dev)
@@ -292,5 +265,3 @@ class UNetEngine(ResUNetEngine):
                 dP = dPn
             else:
                 self._conv_block_bwd(Pw, G, blocks[0], B, skipv, img, None, st, dev)   # the image needs no gradient
-        self._keep = []
-        return unlift_grads(G, P)   # gradients in the shapes of the module's parameters

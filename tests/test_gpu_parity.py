@@ -365,6 +365,41 @@ def test_dropout_backward_uses_the_masks_of_its_own_forward():
     assert any(float(g.abs().max()) > 0 for g in ga)
 
 
+def test_backward_that_raises_leaves_no_state_for_the_next_one():
+    """A backward whose on_last_block callback raises (a failed all-reduce) must not change the next backward on the same engine.  At 1x64^3
+    (mixed mode, one input channel) the pooling backward of level 0 forms the first block's shortcut weight gradient (bpx_maxpool3d_bwd_r1)
+    before the callback runs; at 1x32^3 it does not, and bpx_conv1x1_c1_wgrad must.  down_path.0's shortcut weight gradient of the 32^3 pass is
+    non-zero and bit-equal to a fresh engine's."""
+    from biapy_amd import _lib as L
+    from biapy_amd.engine import NetConfig, ResUNetEngine
+    from oracle import net_oracle
+
+    fm = [16, 32]
+    assert L.lib.bpx_maxpool3d_bwd_r1_workspace(L.MIX16, 1, 64, 64, 64, 2, fm[0]) > 0
+    assert L.lib.bpx_maxpool3d_bwd_r1_workspace(L.MIX16, 1, 32, 32, 32, 2, fm[0]) == 0
+    P = {k: v.cuda() for k, v in net_oracle.init_state_dict(1, fm, seed=3).items()}
+    g = torch.Generator().manual_seed(4)
+    x64, x32 = torch.randn(1, 1, 64, 64, 64, generator=g).cuda(), torch.randn(1, 1, 32, 32, 32, generator=g).cuda()
+    dl32 = torch.randn(1, 1, 32, 32, 32, generator=g).cuda()
+
+    def fail():
+        raise RuntimeError("all-reduce failed")
+
+    eng = ResUNetEngine(NetConfig(in_ch=1, feature_maps=fm), torch.float16)
+    lo, ctx = eng.forward(P, x64, save=True)
+    with pytest.raises(RuntimeError, match="all-reduce failed"):
+        eng.backward(P, ctx, torch.ones_like(lo), on_last_block=fail)
+
+    def wsc_grad(e):
+        _, c = e.forward(P, x32, save=True)
+        return e.backward(P, c, dl32)["down_path.0.shortcut.0.weight"].clone()
+
+    got, want = wsc_grad(eng), wsc_grad(ResUNetEngine(NetConfig(in_ch=1, feature_maps=fm), torch.float16))
+    torch.cuda.synchronize()
+    assert float(want.abs().max()) > 0
+    assert torch.equal(got, want)
+
+
 def test_graphed_train_step_draws_a_new_dropout_mask_at_every_replay(K):
     """The dropout step counter lives on the device: a replayed HIP graph advances it, so two replays on the same batch give different losses
     and a model in eval mode gives the same logits twice."""
