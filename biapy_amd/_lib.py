@@ -113,6 +113,9 @@ _SIGS = {
     "bpx_convT3d_stats_tiles": ([_i, _i, _i, _i], _i),
     "bpx_convT3d_k2s2_dgrad": ([_i, _i, _i, _i, _i, _i, Tensor, _vp, Tensor, _vp], _i),
     "bpx_convT3d_k2s2_wgrad": ([_i, _i, _i, _i, _i, _i, Tensor, Tensor, _vp, _vp, _vp, _i64, _vp], _i),
+    "bpx_convT3d_k2s2_bwd": ([_i, _i, _i, _i, _i, _i, Tensor, Tensor, _vp, Tensor, _vp, _vp, _vp, _i64, _vp], _i),
+    "bpx_debug_set_convt_bwd": ([_i], _i),
+    "bpx_debug_convt_bwd_launches": ([], _i),
     "bpx_norm_finalize": ([_vp, _i, _i, _i, _i64, _vp, _vp, _f, _i, _vp, _i, _i, _vp], _i),
     "bpx_norm_channel_sums": ([_vp, _i, _i, _i, _vp, _i, _i, _vp], _i),
     "bpx_groupnorm_finalize": ([_vp, _i, _i, _i64, _vp, _vp, _f, _i, _vp, _vp], _i),
@@ -183,7 +186,8 @@ def _load() -> C.CDLL:
     # A/B hooks through the environment: wgrad partial-slab cap in percent
     for env, hook in (("BPX_WGRAD_CAP", "bpx_debug_set_wgrad_cap"), ("BPX_WGRAD_K1", "bpx_debug_set_wgrad_k1"),
                       ("BPX_PW_STREAM", "bpx_debug_set_pw_stream"), ("BPX_C1_PERSIST", "bpx_debug_set_c1_persist"),
-                      ("BPX_BWD_RS", "bpx_debug_set_bwd_rs"), ("BPX_FUSED_BITS", "bpx_debug_set_bwd_fused")):
+                      ("BPX_BWD_RS", "bpx_debug_set_bwd_rs"), ("BPX_FUSED_BITS", "bpx_debug_set_bwd_fused"),
+                      ("BPX_CT_BWD", "bpx_debug_set_convt_bwd")):
         if os.environ.get(env) is not None:
             getattr(lib, hook)(int(os.environ[env]))
     return lib

@@ -43,6 +43,7 @@ struct WgradParams {
   float* db2;                                    // host side only: a second destination of the bias gradient (reduce kernel), or null
   int tilesY, tilesX, tilesPerSample, totalTiles, groups;
   int tilesZ, stripY, order;   // order 1 (windowed shift-dy kernel): XCD-contiguous tile ranges walked in y-strips (conv3d_shared.h decode_tile); 0: tile = group + k * groups
+  void* dx; int dx_ld; const void* wT;   // wgrad_ct_kernel<.., DG = true>: the transposed conv's input gradient and its BPX_PK_CT_T weight pack
 };
 
 template <typename T, int ACTK = 0> __device__ __forceinline__ float act_rt(float u, int act) {
@@ -809,7 +810,14 @@ __global__ void __launch_bounds__(256, MC == 1 ? 4 : MC == 2 ? 3 : 2) wgrad_sdm_
 // and the x fragment of a K-chunk is shared by all subs.  Partials [group][sub][Cin][Cout] -> wgrad_reduce_kernel.
 // MC (round 6): x chunks per workgroup.  With one chunk a 32 -> 32 layer stages the 64 KB dy block of a tile TWICE (once per x chunk) for 16 MFMAs per
 // wave each time - the staging, not HBM, is what the level-0 launch of cfg 2 takes (150 us for 600 MB); MC = 2 stages it once for 32.
-template <int NS, int SZ, int MC = 1>   // SZ = z extent of the kernel = z stride (1 or 2): 4*SZ sub-positions, sub = (a*2 + b)*2 + c
+// DG: the workgroup also forms the layer's INPUT gradient dx[v][ci] = sum_{sub, co} dy[2v + sub][co] * W[ci][co][sub] of its tiles from the dy planes it
+// has staged (the planes are [sub][v][co], so a voxel's 8 consecutive co are the 16-byte B operand of a 16x16x32 MFMA as they lie) - the second pass
+// over dy of a separate dgrad launch (pw_kernel<.., PW_CONVTD>) goes away.  Only where ONE workgroup holds every input and output channel
+// (Cin = 16 MC, Cout = 16 NS: nchunks = nb = 1).  Wave w owns voxels 32 w .. 32 w + 31 of the tile and all Cin columns; the weight pack stays in
+// registers as A fragments (8 sub-positions x MC).  Operands, K order (one 32-wide step per sub-position, ascending) and column binding are those of
+// pw_kernel<uint16_t, 2, 2, PW_CONVTD>, so dx has the same bits.  The stores of a tile are issued one tile later, behind the requests of the next tile's
+// last dy batch: VMEM retires in order, and a wait for those loads would otherwise also be a wait for the write acknowledgements.
+template <int NS, int SZ, int MC = 1, bool DG = false>   // SZ = z extent of the kernel = z stride (1 or 2): 4*SZ sub-positions, sub = (a*2 + b)*2 + c
 __global__ void __launch_bounds__(256, NS == 1 ? 4 : 2) wgrad_ct_kernel(const WgradParams p) {
   using T = uint16_t;
   constexpr int TZ = 2, TY = 4, TX = 16, TV = TZ * TY * TX;       // x tile
@@ -856,6 +864,31 @@ __global__ void __launch_bounds__(256, NS == 1 ? 4 : 2) wgrad_ct_kernel(const Wg
   const int a_base = (g * 8 + trl) * VBA + trc;
   const int g_base = ((SPW * wave) * TV + g * 8 + trl) * VBG + trc;  // first sub of this wave; the next one is TV*VBG further
 
+  // DG: A fragments of the dgrad weight [k group 4 sub + g][Cin][8], row i of column block c bound to column (i / 4) * 4 MC + 4 c + i % 4 (pw_kernel)
+  static_assert(!DG || (MC == 2 && NS == 2 && SZ == 2), "the fused dgrad exists for the 32 -> 32 two-chunk instance");
+  u32x4_t wdg[DG ? NSUB : 1][DG ? MC : 1];
+  u32x4_t pend[DG ? 2 : 1];                      // packed dx of the previous tile: voxel (2 wave + ms) * 16 + i, channels 8 g .. 8 g + 7
+  uint32_t pend_off[DG ? 2 : 1];                 // their byte offsets in dx; ~0u = nothing to store (beyond the buffer range)
+  // (buffer-addressed: a voxel outside the volume stores to an offset beyond the range and is dropped - no branch around the store, so the waits
+  //  behind it stay counted)
+  const __amdgpu_buffer_rsrc_t rs_dx = __builtin_amdgcn_make_buffer_rsrc(DG ? p.dx : nullptr, 0, (int)0xFFFFFFF0u, 0x00020000);
+  if constexpr (DG) {
+    const uint16_t* __restrict__ wT = reinterpret_cast<const uint16_t*>(p.wT);
+#pragma unroll
+    for (int sb = 0; sb < NSUB; ++sb)
+#pragma unroll
+      for (int c = 0; c < MC; ++c)
+        wdg[sb][c] = *reinterpret_cast<const u32x4_t*>(wT + ((size_t)(4 * sb + g) * (16 * MC) + (i >> 2) * (4 * MC) + c * 4 + (i & 3)) * KPL);
+    pend_off[0] = pend_off[1] = ~0u;
+    pend[0] = pend[1] = u32x4_t{0u, 0u, 0u, 0u};
+  }
+  auto store_pending = [&]() {
+    if constexpr (DG) {
+#pragma unroll
+      for (int ms = 0; ms < 2; ++ms) __builtin_amdgcn_raw_buffer_store_b128(pend[ms], rs_dx, (int)pend_off[ms], 0, 0);
+    }
+  };
+
   for (int tt = grp; tt < p.totalTiles; tt += p.groups) {
     const int n = tt / p.tilesPerSample, tile = tt - n * p.tilesPerSample;
     const int z0 = (tile / (p.tilesX * p.tilesY)) * TZ, y0 = ((tile / p.tilesX) % p.tilesY) * TY, x0 = (tile % p.tilesX) * TX;
@@ -887,6 +920,7 @@ __global__ void __launch_bounds__(256, NS == 1 ? 4 : 2) wgrad_ct_kernel(const Wg
         if (full || (SZ * z0 + Z < SZ * D && 2 * y0 + Y < 2 * H && 2 * x0 + X < 2 * W))
           pg[u] = *reinterpret_cast<const u32x4_t*>(gin + (base_g + (uint32_t)(((Z * 2 * H + Y) * 2 * W + X) * p.dy_ld + co_base + subG * KPL) * 2u));
       }
+      if (DG && b0 + BATCH == NPG) store_pending();   // the previous tile's dx, behind this tile's last requests
 #pragma unroll
       for (int u = 0; u < BATCH; ++u) {
         const int q = (b0 + u) * (256 / PPVG) + qlane;
@@ -931,7 +965,37 @@ __global__ void __launch_bounds__(256, NS == 1 ? 4 : 2) wgrad_ct_kernel(const Wg
           for (int ns = 0; ns < NS; ++ns)
             acc[c][a][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[c]), __builtin_bit_cast(bf16x8_t, gf[a][ns]), acc[c][a][ns], 0, 0, 0);
     }
+
+    if constexpr (DG) {   // dx of the tile's 128 voxels x 32 channels: 8 K steps (k = sub * Cout + co), this wave's 2 x 16 voxels x MC column blocks
+      f32x4_t dacc[2][MC];
+#pragma unroll
+      for (int ms = 0; ms < 2; ++ms)
+#pragma unroll
+        for (int c = 0; c < MC; ++c) dacc[ms][c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int sb = 0; sb < NSUB; ++sb)
+#pragma unroll
+        for (int ms = 0; ms < 2; ++ms) {
+          const u32x4_t bf = *reinterpret_cast<const u32x4_t*>(sG + (size_t)((sb * TV + (2 * wave + ms) * 16 + i) * VBG + g * 16));
+#pragma unroll
+          for (int c = 0; c < MC; ++c)
+            dacc[ms][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wdg[sb][c]), __builtin_bit_cast(bf16x8_t, bf), dacc[ms][c], 0, 0, 0);
+        }
+#pragma unroll
+      for (int ms = 0; ms < 2; ++ms) {
+        const int vz = wave >> 1, vy = (wave & 1) * 2 + ms;        // voxel (2 wave + ms) * 16 + i of the 2x4x16 tile
+        const bool ok = full || (z0 + vz < D && y0 + vy < H && x0 + i < W);
+        pend_off[ms] = ok ? (uint32_t)((((n * D + z0 + vz) * H + y0 + vy) * W + x0 + i) * p.dx_ld + g * KPL) * 2u : ~0u;
+        float val[MC][4];
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) val[c][r] = dacc[ms][c][r] + 0.f;   // (pw_kernel adds its absent bias the same way)
+        pend[ms] = u32x4_t{pack_bf16x2(val[0][0], val[0][1]), pack_bf16x2(val[0][2], val[0][3]), pack_bf16x2(val[1][0], val[1][1]), pack_bf16x2(val[1][2], val[1][3])};
+      }
+    }
   }
+  store_pending();   // the last tile's dx
 
   float* pp = p.part + (size_t)grp * NSUB * p.Cin * p.Cout;
 #pragma unroll
@@ -1253,9 +1317,15 @@ int launch_wgrad_k1_dma(const WgradParams& w, int groups, hipStream_t s) {
 struct CtsParams {
   const void* x; int x_ld; const void* dy; int dy_ld;
   int Cin, Cout, D, H, W; int64_t voxels; int nblocks; int groups; float* part; float* dbpart;
+  void* dx; int dx_ld; const void* wT;   // DG: the input gradient and its BPX_PK_CT_T weight pack
 };
 
-template <int MC, int NS, int TV, bool XF16>
+// DG (64 -> 64, TV = 32): dx of the block's 32 voxels from the dy chunks in the ring slot, as wgrad_ct_kernel<.., DG> does.  The 8 output tiles
+// (2 voxel rows x 4 column blocks) go to the four waves WHOLE - wave w: voxel row w & 1, column blocks 2 (w >> 1) and 2 (w >> 1) + 1, all 16 K steps in
+// one accumulator chain each, ascending, with pw_kernel's operands: the same bits as pw_kernel<uint16_t, 2, 4, PW_CONVTD>, no sum across waves.  The
+// wave's 32 weight fragments stay in registers (the kernel runs one workgroup per CU: 512 registers per lane).  A block's store (one per lane)
+// joins the wave's VMEM queue behind the ring requests, so the counted wait of the ring allows for it (see the loop).
+template <int MC, int NS, int TV, bool XF16, bool DG = false>
 __global__ void __launch_bounds__(256) wgrad_ct_dma_kernel(const CtsParams p) {
   constexpr int VB = 32, SUBS = TV / 32, NCH = MC + 8 * NS, A_BYTES = MC * TV * VB, STAGE = NCH * TV * VB, RING = 3;
   constexpr int NI = NCH * SUBS;
@@ -1310,12 +1380,33 @@ __global__ void __launch_bounds__(256) wgrad_ct_dma_kernel(const CtsParams p) {
   const u32x4_t ones = u32x4_t{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
   const bool want_b = p.dbpart != nullptr;
 
+  // DG: A fragments of the dgrad weight [k group][Cin][8]: K step ks = 2 sub + (co >> 5), row i of this wave's column block c <-> ci = 32 (wave >> 1) +
+  // 8 (i >> 2) + 4 c + (i & 3), so that lane row g ends with the 8 consecutive channels 32 (wave >> 1) + 8 g .. of its voxel
+  static_assert(!DG || (MC == 4 && NS == 4 && TV == 32), "the fused dgrad exists for the 64 -> 64 instance");
+  constexpr int DKS = DG ? 2 * 8 : 1;
+  u32x4_t wdg[DKS][DG ? 2 : 1];
+  const __amdgpu_buffer_rsrc_t rs_dx = __builtin_amdgcn_make_buffer_rsrc(DG ? p.dx : nullptr, 0, (int)0xFFFFFFF0u, 0x00020000);
+  if constexpr (DG) {
+    const uint16_t* __restrict__ wT = reinterpret_cast<const uint16_t*>(p.wT);
+#pragma unroll
+    for (int ks = 0; ks < DKS; ++ks)
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+        wdg[ks][c] = *reinterpret_cast<const u32x4_t*>(wT + ((size_t)(4 * ks + g) * (16 * MC) + 32 * (wave >> 1) + 8 * (i >> 2) + 4 * c + (i & 3)) * 8);
+    __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));        // the ring's counted waits below start from an empty queue
+  }
+
   const int nst = grp < nblocks ? (nblocks - grp + groups - 1) / groups : 0;
 #pragma unroll
   for (int s = 0; s < RING - 1; ++s)
     if (s < nst) issue(grp + s * groups, s);
   for (int s = 0; s < nst; ++s) {
-    if (nst - 1 - s >= 1) __builtin_amdgcn_s_waitcnt(vmcnt_imm(IPW));     // block s + 1 may stay in flight
+    // VMEM retires in order.  Behind the requests of block s sit those of block s + 1 (IPW) and, with DG, the dx stores of blocks s - 2 and s - 1 (one per
+    // lane each, none before block 0): allowing IPW + 1 outstanding from s = 1 on leaves the newer store in flight and still implies block s has landed.
+    if (nst - 1 - s >= 1) {                                               // block s + 1 may stay in flight
+      if (DG && s >= 1) __builtin_amdgcn_s_waitcnt(vmcnt_imm(IPW + 1));
+      else __builtin_amdgcn_s_waitcnt(vmcnt_imm(IPW));
+    }
     else __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
     __syncthreads();
     if (s + RING - 1 < nst) issue(grp + (s + RING - 1) * groups, (s + RING - 1) % RING);
@@ -1349,6 +1440,26 @@ __global__ void __launch_bounds__(256) wgrad_ct_dma_kernel(const CtsParams p) {
           if (want_b) accb[ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ones), __builtin_bit_cast(bf16x8_t, gf), accb[ns], 0, 0, 0);
         }
       }
+    }
+    if constexpr (DG) {
+      f32x4_t dacc[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
+      const int vrow = ((wave & 1) * 16 + i) * VB + (g & 1) * 16;     // this lane's voxel in a chunk plane, the half of the chunk's 16 channels it reads
+#pragma unroll
+      for (int ks = 0; ks < DKS; ++ks) {   // k = sub * 64 + co: sub = ks >> 1, channels 32 (ks & 1) + 8 g .. + 7 = chunk 2 (ks & 1) + (g >> 1), half g & 1
+        const u32x4_t bf = *reinterpret_cast<const u32x4_t*>(st + A_BYTES + (((ks >> 1) * NS + 2 * (ks & 1) + (g >> 1)) * TV * VB + vrow));
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+          dacc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wdg[ks][c]), __builtin_bit_cast(bf16x8_t, bf), dacc[c], 0, 0, 0);
+      }
+      const int64_t v = (int64_t)(grp + s * groups) * TV + (wave & 1) * 16 + i;
+      float val[2][4];
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) val[c][r] = dacc[c][r] + 0.f;   // (pw_kernel adds its absent bias the same way)
+      const u32x4_t o = u32x4_t{pack_bf16x2(val[0][0], val[0][1]), pack_bf16x2(val[0][2], val[0][3]), pack_bf16x2(val[1][0], val[1][1]), pack_bf16x2(val[1][2], val[1][3])};
+      // every lane stores, every block: the ring's wait counts on it (a voxel past the end goes beyond the buffer range and is dropped)
+      __builtin_amdgcn_raw_buffer_store_b128(o, rs_dx, (int)(v < voxels ? ((uint32_t)v * (uint32_t)p.dx_ld + 32u * (wave >> 1) + 8u * g) * 2u : ~0u), 0, 0);
     }
   }
   // partial slab [grp][sub][Cin][Cout]: this wave's two sub-positions
@@ -1619,10 +1730,35 @@ extern "C" int bpx_conv3d_wgrad_db2(int dtype, int N, int D, int H, int W, bpx_t
   return run_wgrad(fn, dtype, p, taps, ws_d, ws_bytes, (hipStream_t)stream);
 }
 
-extern "C" int bpx_convT3d_k2s2_wgrad(int dtype, int N, int D, int H, int W, int sz, bpx_tensor x, bpx_tensor dy, float* dw_d, float* db_d,
-                                      void* ws_d, int64_t ws_bytes, bpx_stream_t stream) {
-  BPX_CHECK(x.cs == 0 && dy.cs == 0, "bpx_convT3d_k2s2_wgrad: chunk-planar tensors (cs != 0) are not accepted here");
-  const char* fn = "bpx_convT3d_k2s2_wgrad";
+namespace {
+int g_ct_bwd = 1;     // bpx_debug_set_convt_bwd: 1 = bpx_convT3d_k2s2_bwd forms dx inside the weight-gradient kernel where an instance exists, 0 = never
+
+int g_ct_bwd_launches = 0;   // one-pass launches so far (bpx_debug_convt_bwd_launches: tests tell the instance from its fall-back)
+
+// The operands of the input gradient that bpx_convT3d_k2s2_bwd hands to the weight-gradient launch.  `fused` is the launch's answer: the ONE place that
+// decides (in ct_wgrad_impl, where the tile / streaming instance is chosen) also tells the caller whether dx is still to be computed.
+struct CtDgrad { bpx_tensor dx; const void* wT; bool fused; };
+
+// wgrad_ct_kernel<2, 2, 2, DG>: the tile kernel must already be the 32 -> 32 two-chunk instance (one workgroup holds every channel); dx dense rows of 32
+// channels it can reach with 32-bit byte offsets and 16-byte stores
+inline bool ct_dg_ok(int N, int D, int H, int W, const bpx_tensor& x, const bpx_tensor& dy, const CtDgrad* dg) {
+  if (dg == nullptr || !g_ct_bwd || dg->dx.ptr == nullptr || dg->wT == nullptr) return false;
+  const bpx_tensor& dx = dg->dx;
+  return x.C == 32 && dy.C == 32 && dx.C == 32 && dx.cs == 0 && dx.ld >= dx.C && (dx.ld & 7) == 0 && (dy.ld & 7) == 0 &&
+         (((uintptr_t)dx.ptr | (uintptr_t)dg->wT | (uintptr_t)dy.ptr) & 15) == 0 && (int64_t)N * D * H * W * dx.ld * 2 < (1ll << 31);
+}
+
+// wgrad_ct_dma_kernel<4, 4, 32, .., DG>: the streaming kernel must already be the 64 -> 64 instance; the same conditions on dx
+inline bool cts_dg_ok(int64_t voxels, const bpx_tensor& x, const bpx_tensor& dy, const CtDgrad* dg) {
+  if (dg == nullptr || !g_ct_bwd || dg->dx.ptr == nullptr || dg->wT == nullptr) return false;
+  const bpx_tensor& dx = dg->dx;
+  return x.C == 64 && dy.C == 64 && dx.C == 64 && dx.cs == 0 && dx.ld >= dx.C && (dx.ld & 7) == 0 &&
+         (((uintptr_t)dx.ptr | (uintptr_t)dg->wT) & 15) == 0 && voxels * dx.ld * 2 < (1ll << 31);
+}
+
+int ct_wgrad_impl(const char* fn, int dtype, int N, int D, int H, int W, int sz, bpx_tensor x, bpx_tensor dy, float* dw_d, float* db_d,
+                  void* ws_d, int64_t ws_bytes, bpx_stream_t stream, CtDgrad* dg) {
+  BPX_CHECK(x.cs == 0 && dy.cs == 0, "%s: chunk-planar tensors (cs != 0) are not accepted here", fn);
   BPX_CHECK(dtype == BPX_BF16 || dtype == BPX_F32 || dtype == BPX_MIX16, "%s: dtype must be BF16, F32 or MIX16 (x fp16, dy bf16)", fn);
   const bool mix = dtype == BPX_MIX16;
   if (mix) dtype = BPX_BF16;
@@ -1646,6 +1782,12 @@ extern "C" int bpx_convT3d_k2s2_wgrad(int dtype, int N, int D, int H, int W, int
     q.dbpart = db_d ? q.part + (size_t)q.groups * nsub * x.C * dy.C : nullptr;
     hipStream_t s = (hipStream_t)stream;
     if (cts == 1) { if (mix) wgrad_ct_dma_kernel<2, 2, 64, true><<<q.groups, 256, 0, s>>>(q); else wgrad_ct_dma_kernel<2, 2, 64, false><<<q.groups, 256, 0, s>>>(q); }
+    else if (cts_dg_ok(q.voxels, x, dy, dg)) {                        // 64 -> 64: dx rides along (see the kernel)
+      q.dx = dg->dx.ptr; q.dx_ld = dg->dx.ld; q.wT = dg->wT;
+      if (mix) wgrad_ct_dma_kernel<4, 4, 32, true, true><<<q.groups, 256, 0, s>>>(q); else wgrad_ct_dma_kernel<4, 4, 32, false, true><<<q.groups, 256, 0, s>>>(q);
+      dg->fused = true;
+      ++g_ct_bwd_launches;
+    }
     else { if (mix) wgrad_ct_dma_kernel<4, 4, 32, true><<<q.groups, 256, 0, s>>>(q); else wgrad_ct_dma_kernel<4, 4, 32, false><<<q.groups, 256, 0, s>>>(q); }
     BPX_LAUNCH_CHECK(fn);
     return finish_wgrad(fn, ReduceJob{q.part, dw_d, q.groups, nsub, x.C, dy.C, (int64_t)dy.C * nsub, nsub, 1, 0, q.dbpart, db_d, 0}, s);
@@ -1665,7 +1807,13 @@ extern "C" int bpx_convT3d_k2s2_wgrad(int dtype, int N, int D, int H, int W, int
     const int nchunks = x.C / (16 * mc), nb = dy.C / (16 * c.ns);
     dim3 grid((unsigned)(((c.groups + 7) & ~7) * nchunks * nb));
     hipStream_t s = (hipStream_t)stream;
-    if (mc == 2) wgrad_ct_kernel<2, 2, 2><<<grid, 256, 0, s>>>(p);      // (ct_mc: sz == 2 and 32-channel output blocks only)
+    if (mc == 2 && ct_dg_ok(N, D, H, W, x, dy, dg)) {                  // (nchunks = nb = 1) dx rides along: see the kernel
+      p.dx = dg->dx.ptr; p.dx_ld = dg->dx.ld; p.wT = dg->wT;
+      wgrad_ct_kernel<2, 2, 2, true><<<grid, 256, 0, s>>>(p);
+      dg->fused = true;
+      ++g_ct_bwd_launches;
+    }
+    else if (mc == 2) wgrad_ct_kernel<2, 2, 2><<<grid, 256, 0, s>>>(p);      // (ct_mc: sz == 2 and 32-channel output blocks only)
     else if (sz == 2) { if (c.ns == 2) wgrad_ct_kernel<2, 2><<<grid, 256, 0, s>>>(p); else wgrad_ct_kernel<1, 2><<<grid, 256, 0, s>>>(p); }
     else { if (c.ns == 2) wgrad_ct_kernel<2, 1><<<grid, 256, 0, s>>>(p); else wgrad_ct_kernel<1, 1><<<grid, 256, 0, s>>>(p); }
     BPX_LAUNCH_CHECK(fn);
@@ -1686,6 +1834,25 @@ extern "C" int bpx_convT3d_k2s2_wgrad(int dtype, int N, int D, int H, int W, int
   }
   return 0;
 }
+
+}  // namespace
+
+extern "C" int bpx_convT3d_k2s2_wgrad(int dtype, int N, int D, int H, int W, int sz, bpx_tensor x, bpx_tensor dy, float* dw_d, float* db_d,
+                                      void* ws_d, int64_t ws_bytes, bpx_stream_t stream) {
+  return ct_wgrad_impl("bpx_convT3d_k2s2_wgrad", dtype, N, D, H, W, sz, x, dy, dw_d, db_d, ws_d, ws_bytes, stream, nullptr);
+}
+
+// Both gradients of the transposed conv from one pass over dy where the weight-gradient kernel has an instance for it; everywhere else the two
+// launches of bpx_convT3d_k2s2_wgrad and bpx_convT3d_k2s2_dgrad, in that order: every shape those two accept is accepted here.
+extern "C" int bpx_convT3d_k2s2_bwd(int dtype, int N, int D, int H, int W, int sz, bpx_tensor x, bpx_tensor dy, const void* w_packed_T_d, bpx_tensor dx,
+                                    float* dw_d, float* db_d, void* ws_d, int64_t ws_bytes, bpx_stream_t stream) {
+  CtDgrad dg{dx, w_packed_T_d, false};
+  if (ct_wgrad_impl("bpx_convT3d_k2s2_bwd", dtype, N, D, H, W, sz, x, dy, dw_d, db_d, ws_d, ws_bytes, stream, &dg) != 0) return 1;
+  if (dg.fused) return 0;
+  return bpx_convT3d_k2s2_dgrad(dtype == BPX_MIX16 ? BPX_BF16 : dtype, N, D, H, W, sz, dy, w_packed_T_d, dx, stream);
+}
+extern "C" int bpx_debug_set_convt_bwd(int on) { g_ct_bwd = on ? 1 : 0; return 0; }
+extern "C" int bpx_debug_convt_bwd_launches(void) { return g_ct_bwd_launches; }
 
 extern "C" int bpx_debug_set_wgrad_k1(int on) { g_k1_dma = (on == 1 || on == 3 || on == 7) ? 1 : 0; g_ct_dma = (on == 1 || on == 5 || on == 7) ? 1 : 0; g_ct_dma_all = on == 7; return 0; }
 extern "C" int bpx_debug_set_wgrad_cap(int percent) { g_cap_pct = percent > 0 ? percent : 100; return 0; }

@@ -1207,11 +1207,10 @@ class ResUNetEngine:
             dec_out, dup_feat = ctx["dec_out"], dfeat
             wsn = lib.bpx_convT3d_k2s2_wgrad_workspace(B, D0, H0, W0, cfg.post_up, fm[0], fm[0])
             ws = self._workspace(wsn, dev)
-            L.check(lib.bpx_convT3d_k2s2_wgrad(self.bdt, B, D0, H0, W0, cfg.post_up, L.tview(dec_out), L.tview(dup_feat), G["post_upsampling.weight"].data_ptr(),
-                                               G["post_upsampling.bias"].data_ptr(), ws.data_ptr(), ws.numel(), st))
             dfeat = torch.empty((B, D0, H0, W0, fm[0]), dtype=T, device=dev)
             wt = self._pack(P["post_upsampling.weight"], L.PK_CT_T if cfg.post_up == 2 else L.PK_CT4_T, fm[0], fm[0], False)
-            L.check(lib.bpx_convT3d_k2s2_dgrad(self.gdt, B, D0, H0, W0, cfg.post_up, L.tview(dup_feat), wt.data_ptr(), L.tview(dfeat), st))
+            L.check(lib.bpx_convT3d_k2s2_bwd(self.bdt, B, D0, H0, W0, cfg.post_up, L.tview(dec_out), L.tview(dup_feat), wt.data_ptr(), L.tview(dfeat),
+                                             G["post_upsampling.weight"].data_ptr(), G["post_upsampling.bias"].data_ptr(), ws.data_ptr(), ws.numel(), st))
             self._keep.append(dup_feat)
         # ---- decoder (blocks list: enc 0..Lv-1, bottleneck, dec j=0..Lv-1 for levels Lv-1..0) -------
         dskip: List[Optional[torch.Tensor]] = [None] * Lv      # d(concat) leaves the decoder block as two dense tensors
@@ -1229,11 +1228,11 @@ class ResUNetEngine:
             dUp = L.tview(dup)
             wsn = lib.bpx_convT3d_k2s2_wgrad_workspace(B, Sl[0], Sl[1], Sl[2], szl, Cup, Cup)
             ws = self._workspace(wsn, dev)
-            L.check(lib.bpx_convT3d_k2s2_wgrad(self.bdt, B, Sl[0], Sl[1], Sl[2], szl, L.tview(x_in), dUp, G[wk].data_ptr(), G[bk].data_ptr(),
-                                               ws.data_ptr(), ws.numel(), st))
             dxin = torch.empty((B,) + Sl + (Cup,), dtype=T, device=dev)
             wt = self._pack(P[wk], L.PK_CT_T if szl == 2 else L.PK_CT4_T, Cup, Cup, False)
-            L.check(lib.bpx_convT3d_k2s2_dgrad(self.gdt, B, Sl[0], Sl[1], Sl[2], szl, dUp, wt.data_ptr(), L.tview(dxin), st))
+            # dW, db and dx_in; at the 32 -> 32 level of a large volume from ONE pass over dUp (wgrad_ct_kernel<.., DG>), else the two kernels
+            L.check(lib.bpx_convT3d_k2s2_bwd(self.bdt, B, Sl[0], Sl[1], Sl[2], szl, L.tview(x_in), dUp, wt.data_ptr(), L.tview(dxin),
+                                             G[wk].data_ptr(), G[bk].data_ptr(), ws.data_ptr(), ws.numel(), st))
             dOut = L.tview(dxin)
             keep.append(dxin)
         # ---- bottleneck -------------------------------------------------------------------------

@@ -242,11 +242,10 @@ class UNetEngine(ResUNetEngine):
             keep.append(dup)
             Dl, Hl, Wl = S[i + 1]
             ws = self._workspace(lib.bpx_convT3d_k2s2_wgrad_workspace(B, Dl, Hl, Wl, zd[i], Cl, Cup), dev)
-            L.check(lib.bpx_convT3d_k2s2_wgrad(self.bdt, B, Dl, Hl, Wl, zd[i], L.tview(x_low), L.tview(dup), G[f"{pre}.0.weight"].data_ptr(),
-                                               G[f"{pre}.0.bias"].data_ptr(), ws.data_ptr(), ws.numel(), st))
             dlow = torch.empty((B, Dl, Hl, Wl, Cl), dtype=T, device=dev)
             wt = self._pack(Pw[f"{pre}.0.weight"], L.PK_CT_T if zd[i] == 2 else L.PK_CT4_T, Cl, Cup, False)
-            L.check(lib.bpx_convT3d_k2s2_dgrad(self.gdt, B, Dl, Hl, Wl, zd[i], L.tview(dup), wt.data_ptr(), L.tview(dlow), st))
+            L.check(lib.bpx_convT3d_k2s2_bwd(self.bdt, B, Dl, Hl, Wl, zd[i], L.tview(x_low), L.tview(dup), wt.data_ptr(), L.tview(dlow),
+                                             G[f"{pre}.0.weight"].data_ptr(), G[f"{pre}.0.bias"].data_ptr(), ws.data_ptr(), ws.numel(), st))
             dA = L.tview(dlow)
             keep.append(dlow)
         # ---- bottleneck ---------------------------------------------------------------------------------------------

@@ -295,6 +295,14 @@ int64_t bpx_convT3d_k2s2_wgrad_workspace(int N, int D, int H, int W, int sz, int
 int bpx_convT3d_k2s2_wgrad(int dtype, int N, int D, int H, int W, int sz, bpx_tensor x, bpx_tensor dy,
                            float* dw_d /* (Cin,Cout,sz,2,2), overwritten */, float* db_d /* accumulated */,
                            void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
+/* Both gradients of the layer in one call: dx as bpx_convT3d_k2s2_dgrad (w_packed_T_d: BPX_PK_CT_T / BPX_PK_CT4_T, bf16 for BPX_MIX16), dw_d and
+ * db_d as bpx_convT3d_k2s2_wgrad (same workspace, same deferral), bit for bit.  For 32 -> 32 channels, sz = 2, >= 262144 input voxels, bf16 /
+ * MIX16, dense dx the weight-gradient kernel forms dx from the dy tiles it has staged and dy is read once; every other shape runs the two
+ * kernels one after the other. */
+int bpx_convT3d_k2s2_bwd(int dtype, int N, int D, int H, int W, int sz, bpx_tensor x, bpx_tensor dy, const void* w_packed_T_d,
+                         bpx_tensor dx, float* dw_d, float* db_d, void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
+int bpx_debug_set_convt_bwd(int on); /* test / A-B hook: 1 (default) = bpx_convT3d_k2s2_bwd uses its one-pass instance where it applies, 0 = always the two kernels; same bits */
+int bpx_debug_convt_bwd_launches(void); /* test hook: how many calls of bpx_convT3d_k2s2_bwd have taken the one-pass instance so far (host-side count, graph replays not included) */
 
 /* InstanceNorm3d(affine, eps) == GroupNorm with G = C (blocks.py:2122-2125).  Reduces the partials
  * written by a producer kernel to bpx_norm_rec[n*out_ld + out_off + c]; groups < C gives GroupNorm(groups).
