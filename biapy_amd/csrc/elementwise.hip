@@ -3006,6 +3006,8 @@ extern "C" int bpx_maxpool3d_bwd(int dtype, int N, int D, int H, int W, int sz, 
   const char* fn = "bpx_maxpool3d_bwd";
   BPX_CHECK(x.ptr && dy.ptr && dx.ptr, "%s: null pointer", fn);
   BPX_CHECK(sz == 1 || sz == 2, "%s: z stride must be 1 or 2 (got %d)", fn, sz);
+  // (the kernel walks whole windows: a trailing plane / row / column would keep whatever dx held and lose the addend there)
+  BPX_CHECK(D % sz == 0 && H % 2 == 0 && W % 2 == 0, "%s: extents must be divisible by the window (%d,2,2) (got %d,%d,%d)", fn, sz, D, H, W);
   BPX_CHECK(x.C == dy.C && x.C == dx.C && x.C % 16 == 0, "%s: channel mismatch", fn);
   int kpl = (dtype == BPX_BF16 || dtype == BPX_MIX16) ? 8 : 4;
   int64_t total = (int64_t)N * (D / sz) * (H / 2) * (W / 2) * (x.C / kpl);
@@ -3045,6 +3047,8 @@ extern "C" int bpx_maxpool3d_bwd_r1(int dtype, int N, int D, int H, int W, int s
   const int xcs = x.cs ? (int)x.cs : 16;
   BPX_CHECK(x.ptr && dy.ptr && dx.ptr && addend.ptr && img_d && dw_d && ws_d, "%s: null pointer", fn);
   BPX_CHECK(x.C == dy.C && x.C == dx.C && x.C == addend.C, "%s: channel mismatch", fn);
+  BPX_CHECK(sz == 1 || sz == 2, "%s: z stride must be 1 or 2 (got %d)", fn, sz);
+  BPX_CHECK(D % sz == 0 && H % 2 == 0 && W % 2 == 0, "%s: extents must be divisible by the window (%d,2,2) (got %d,%d,%d)", fn, sz, D, H, W);
   const int64_t need = bpx_maxpool3d_bwd_r1_workspace(dtype, N, D, H, W, sz, x.C);
   BPX_CHECK(need > 0, "%s: unsupported here (16 channels, 16-bit storage): use bpx_maxpool3d_bwd and bpx_conv1x1_c1_wgrad", fn);
   BPX_CHECK(ws_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", fn, (long long)ws_bytes, (long long)need);

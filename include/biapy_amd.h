@@ -316,7 +316,8 @@ int bpx_norm_finalize(float* stats_part_d, int N, int tiles, int C, int64_t coun
  *   bpx_norm_channel_sums     : a producer's partials [N][tiles][2][C] (CONSUMED like in bpx_norm_finalize) -> per-channel totals
  *                               sums_d[(n*out_ld + out_off + c)*2 + {0, 1}] (double): each producer fills its columns of one (N, out_ld, 2) array
  *   bpx_groupnorm_finalize    : the records of all C channels from those totals (group statistics = fixed-order sums of the group's channels)
- *   bpx_groupnorm_bwd_finalize: bpx_norm_bwd_finalize for the same layout: sums_d = per-channel totals of {S1 = sum g, S2 = sum g*xhat}
+ *   bpx_groupnorm_bwd_finalize: bpx_norm_bwd_finalize for the same layout: sums_d = per-channel totals of {S1 = sum g, S2 = sum g*xhat};
+ *                               like it, it ADDS to what dgamma_d / dbeta_d hold (either may be null)
  * The reference's "gn" (nn.GroupNorm(out_channels, num_groups=8), blocks.py:2122-2125) raises a TypeError; what it means - GroupNorm(8, C) -
  * is what these implement, checked against torch.nn.GroupNorm. */
 int bpx_norm_channel_sums(float* stats_part_d, int N, int tiles, int C, double* sums_d, int out_ld, int out_off, bpx_stream_t stream);
@@ -331,7 +332,8 @@ int bpx_tensor_stats_tiles(int64_t voxels);
 /* Backward of InstanceNorm (groups == C) / GroupNorm(groups) (blocks.py:2117-2125) given the per-channel partials from
  * bpx_conv3d_dgrad / bpx_norm_act_bwd (S1 = sum g, S2 = sum g*xhat with the group's statistics in rec_d):
  *   coef[n*C+c] = {a, b, c0} with dx = a*g + b*t + c0 ;  dgamma[c] += sum_n S2 ; dbeta[c] += sum_n S1
- * (sums over the samples in a fixed order by one thread per channel: deterministic).  Channels per group: 1, 2, 4, 8, 16, 32, 64;
+ * (sums over the samples in a fixed order by one thread per channel: deterministic).  dgamma_d / dbeta_d are ADDED to, never overwritten: the
+ * caller zeroes them (or lets several layers that share a parameter accumulate); either may be null.  Channels per group: 1, 2, 4, 8, 16, 32, 64;
  * count_per_channel = voxels per sample. */
 int bpx_norm_bwd_finalize(float* red_part_d /* consumed, see bpx_norm_finalize */, int N, int tiles, int C, int64_t count_per_channel,
                           const bpx_norm_rec* rec_d, const float* gamma_d, float* dgamma_d, float* dbeta_d, int groups,
@@ -339,7 +341,9 @@ int bpx_norm_bwd_finalize(float* red_part_d /* consumed, see bpx_norm_finalize *
 /* The same inside a bpx_wgrad_defer_begin / _flush window, one block per (channel block, sample): coef_d is complete when the call's kernel is; the
  * sums over the samples that dgamma / dbeta need are queued with the window's weight-gradient reductions and arrive at the flush (sample order,
  * fixed: bit-reproducible).  The first partial row of every sample is overwritten with that sample's totals: red_part_d must stay untouched
- * until the flush.  Outside a window (or for N = 1) it is bpx_norm_bwd_finalize. */
+ * until the flush.  The flush ADDS the sums to what dgamma_d / dbeta_d hold then, as the plain entry does at once.  dbeta_d == dgamma_d + C (the
+ * engines' gradient slab) is one reduction over 2 C columns, any other pair two; either may be null.  Outside a window (or for N = 1) it is
+ * bpx_norm_bwd_finalize. */
 int bpx_norm_bwd_finalize_deferred(float* red_part_d /* consumed, see bpx_norm_finalize */, int N, int tiles, int C, int64_t count_per_channel,
                           const bpx_norm_rec* rec_d, const float* gamma_d, float* dgamma_d, float* dbeta_d, int groups,
                           bpx_nbwd_coef* coef_d, bpx_stream_t stream);
@@ -435,7 +439,8 @@ int bpx_gate_mlp_bwd(const float* dpart_d, int N, int tiles, int C, int64_t voxe
 int bpx_maxpool3d_fwd(int dtype, int N, int D, int H, int W, int sz, bpx_tensor x, bpx_tensor y, float* stats_part_d,
                       bpx_stream_t stream);
 int bpx_maxpool3d_stats_tiles(int dtype, int D, int H, int W, int sz, int C);
-/* dx = addend + scatter(dy to the first maximal element of each window) */
+/* dx = addend + scatter(dy to the first maximal element of each window); addend may be dx itself (in place) or null.  D % sz, H % 2 and W % 2 must be
+ * 0, as in bpx_maxpool3d_fwd: the call is refused otherwise (a trailing plane / row / column of dx would stay unwritten). */
 int bpx_maxpool3d_bwd(int dtype, int N, int D, int H, int W, int sz, bpx_tensor x, bpx_tensor dy, bpx_tensor addend,
                       bpx_tensor dx, bpx_stream_t stream);
 /* The same (addend required) with the rank-1 shortcut weight gradient of the first residual block riding along (round 6): dw_d[co] (16, 1, 1, 1, 1) =

@@ -1,11 +1,12 @@
 """The conv kernels element by element against float64 (tests/conv_bounds.py): every forward route of bpx_conv3d_fwd / _fwd_pool at f32, bf16
 and f16, batch independence of a sample's bits, the first-layer / 1x1 / transposed-conv forwards at f16, the input gradient at f32, bf16
-and MIX16 and the fused backward's g.  Each row records max(|got - ref| / bound) and the position of its worst element."""
+and MIX16 with its S1 / S2 rows, and the fused backward's g, S1 / S2 rows, dW and db.  Each row records max(|got - ref| / bound) and the position of its worst element."""
 import pytest
 import torch
 
 import conv_bounds as CB
 import kernel_checks
+import norm_bounds as NB
 
 pytestmark = pytest.mark.gpu
 
@@ -252,10 +253,20 @@ def test_conv3d_dgrad_elementwise(row, mode):
     finally:
         lib.bpx_debug_set_conv_ws(0)
     ref, bound = CB.dgrad_reference(dy.to(DEV), w.to(DEV), gk, t=t.to(DEV) if norm else None, rec=rec.to(DEV) if norm else None, act=act)
-    _check([CB.compare(f"dgrad[{name} {mode} B{B} {(D, H, W)} dy{Cdy}->g{Cg} norm{int(norm)} act{act} planar{int(planar)}].g", out, ref, bound)])
+    tag = f"dgrad[{name} {mode} B{B} {(D, H, W)} dy{Cdy}->g{Cg} norm{int(norm)} act{act} planar{int(planar)}]"
+    rows = [CB.compare(tag + ".g", out, ref, bound)]
+    if norm:
+        # S1 = sum g, S2 = sum g xhat: the kernels sum the fp32 product acc * act'(u) BEFORE it is rounded to the storage type (conv3_kernel,
+        # conv3_lean_kernel: s1 += v, s2 += v * xh), so the terms carry the bound of the fp32 value - dgrad_reference with an fp32 store; xhat is
+        # (t - mean) rstd in fp32 from the stored t (norm_bounds.xhat_terms).  One row per tile: a lane sums its tile_vox / 64 <= 8 voxels, 16
+        # lanes in 4 butterfly levels, the 4 waves in a chain of 3: 8 + 7.  The rows are summed here in fp64.
+        _, pre = CB.dgrad_reference(dy.to(DEV), w.to(DEV), gk, t=t.to(DEV), rec=rec.to(DEV), act=act, out_kind="f32")
+        s, sb = NB.red_reference(ref, pre, t.to(DEV), rec, 8 + 7)
+        rows.append(CB.compare(tag + ".red", red.double().sum(1), s, sb, axes="nkc"))
+    _check(rows)
 
 
-# ---- fused backward: its g output -----------------------------------------------------------------------------------------------------
+# ---- fused backward: g, the S1 / S2 rows, dW and db --------------------------------------------------------------------------------------------
 # (dtype, B, S, Ct, Cdy) - every instance bpx_conv3d_bwd_fused_supported admits, each serial and role-split where that form exists
 BWD_CASES = [(r, rs) for r in CB.BWD_FUSED_ROWS for rs in ((0, 3) if r[4] == 16 else (0,))]
 
@@ -289,7 +300,26 @@ def test_conv3d_bwd_fused_g_elementwise(row, rs):
     finally:
         lib.bpx_debug_set_bwd_rs(kernel_checks.RS_DEFAULT)
     ref, bound = CB.dgrad_reference(dy.to(DEV), w.to(DEV), "bf16", t=t.to(DEV), rec=rec.to(DEV), act=1)
-    _check([CB.compare(f"bwd_fused[dt{dtc} B{B} {(D, H, W)} dy{Cdy}->t{Ct} rs{rs}].g", out, ref, bound)])
+    tag = f"bwd_fused[dt{dtc} B{B} {(D, H, W)} dy{Cdy}->t{Ct} rs{rs}]"
+    rows = [CB.compare(tag + ".g", out, ref, bound)]
+    # S1 / S2 as in the input-gradient test (the fp32 product is summed, xhat in fp32).  One row per workgroup (or per D wave, or per tile): a lane
+    # keeps its sums over the tiles of a sample its workgroup walks - at most every 4x4x16 tile of the sample, 4 voxels per lane each - then 4
+    # butterfly levels and a chain of 3 over the waves.
+    tps = -(-D // 4) * -(-H // 4) * -(-W // 16)
+    _, pre = CB.dgrad_reference(dy.to(DEV), w.to(DEV), "bf16", t=t.to(DEV), rec=rec.to(DEV), act=1, out_kind="f32")
+    s, sb = NB.red_reference(ref, pre, t.to(DEV), rec, 4 * tps + 7)
+    rows.append(CB.compare(tag + ".red", red.double().sum(1), s, sb, axes="nkc"))
+    # dW[co][ci][tap] = sum_v a[v + tap][ci] dy[v][co], a = ELU(scale t + shift) rounded to a bf16 MFMA operand, and db = sum_v dy: one partial slab
+    # per workgroup column (G of them: the workspace holds G (27 Ct + 1) Cdy floats).  A workgroup walks a contiguous share of its XCD's
+    # ceil(T / 8) tiles, at most ceil(ceil(T / 8) / (G / 8)) + 1 of them, 256 voxels each, one rounding per product; the waves' accumulators meet in
+    # at most 7 additions (8 waves in the role-split form); db sums one partial per thread and up to 512 of them in sequence; the reduction over
+    # the slabs is wgrad_reduce_kernel's G + 3 (conv_bounds.wgrad_chains).
+    G = ws.numel() // ((27 * Ct + 1) * Cdy * 4)
+    T = B * tps
+    slab = (-(-(-(-T // 8)) // max(1, G // 8)) + 1) * 256
+    wref, wbound, dbr, dbb = CB.wgrad_reference(t.to(DEV), dy.to(DEV), 3, "bf16", rec=rec.to(DEV), act=1, chains=(slab + 7 + G + 3, slab + 512 + G + 3))
+    rows += [CB.compare(tag + ".dw", dw, wref, wbound, axes="oikyx"), CB.compare(tag + ".db", db, dbr, dbb, axes="o")]
+    _check(rows)
 
 
 # ---- other forward entry points at f16 ---------------------------------------------------------------------------------------------
