@@ -1,11 +1,32 @@
-"""Segmentation losses / metrics of the binary (1-channel) head on the device.
+"""Segmentation losses / metrics on the device: the binary (1-channel) head, and heads of 2..8 channels.
 
 Mirrors ``biapy/engine/metrics.py``: ``CrossEntropyLoss_wrapper`` (:493-586; the default ``LOSS.TYPE = "CE"`` on one output
 channel is ``BCEWithLogitsLoss``), ``DiceLoss`` (:726-762, ``batch_dice=True``, smooth 1e-5), ``DiceCELoss`` (:764-973,
 binary case: ``w_ce * BCE + w_dice * (1 - Dice)``) and ``jaccard_index`` (:138-232, threshold 0.5).  One streaming HIP kernel
 produces every sum the four need (``bpx_seg_loss_sums``); the backward is one more pass (``bpx_seg_loss_bwd``).  Round 6: the multi-class
 case of ``CrossEntropyLoss_wrapper`` (``num_classes > 2``: softmax cross entropy over 3..8 class channels with ``ignore_index`` and the "manual"
-class weights) and the confusion counts of the multi-class IoU run on the device too (``bpx_softmax_ce_*``); ``DiceCELoss`` stays binary.
+class weights) and the confusion counts of the multi-class IoU run on the device too (``bpx_softmax_ce_*``).
+
+Dice and Dice + CE on heads of 2..8 channels (``bpx_dice_*``, csrc/losses.hip: sums, finish, backward - three launches per loss call whatever N,
+``batch_dice`` or the CE weight are, no host read-back).  Logits are ``(N, C, *space)`` fp32; ``C = 1`` keeps the one-channel path above, more than
+8 channels raise ``NotImplementedError``.  The target's shape chooses the mode:
+
+* CHANNEL mode, ``target.shape == logits.shape``: ``p = sigmoid(z)`` per channel, ``I[n,c] = sum_v p t``, ``P = sum_v p``, ``T = sum_v t``
+  (``batch_dice=True`` sums them over ``n`` as well), ``dice = (2 I + s) / (P + T + s)``, ``loss = 1 - mean(dice)`` over ``c`` and - per sample - over
+  ``n``.  This is ``oracle.loss_oracle.dice``, which is PINNED to the reference's ``DiceLoss``.  ``DiceCELoss`` here is
+  ``w_ce * BCEWithLogits(mean over all elements) + w_dice * dice`` = ``oracle.loss_oracle.dice_ce``.
+* CLASS mode, the target is a label map ``(N, 1, *space)`` or ``(N, *space)`` of class ids as floats: ``p = softmax_c(z)``, ``t = one-hot(label)``.
+  A voxel counts if its label is not ``ignore_index`` and lies in ``[0, C)``; uncounted voxels leave all of ``I``, ``P``, ``T`` and the CE sums.  The
+  same Dice formula over all ``C`` classes (a class absent from the labels contributes ``s / (P + s)``); the CE term is the softmax cross entropy of
+  ``CrossEntropyLoss_wrapper`` (``class_weights`` on the CE term only, ``ignore_index = -1`` meaning -100);
+  ``loss = w_ce * CE + w_dice * (1 - mean dice)``.  A term whose weight is 0 is not formed: an all-ignored batch with ``w_ce = 0`` gives a finite
+  value, with ``w_ce != 0`` NaN as torch does.  PRODUCT-DEFINED, PARITY-UNPINNED: ``oracle/`` restates only the sigmoid ``DiceLoss``, so this mode
+  is checked against its own fp64 statement (tests/loss_bounds.py) and fp64 autograd, not against the reference's values.
+
+Gradient, with ``U = P + T``, ``M`` the number of dice terms averaged (``C``, or ``N C`` per sample), ``a0[c] = (2 I_c + s) / (M (U_c + s)^2)`` and
+``a1[c] = a0[c] - 2 / (M (U_c + s))``: class mode ``dz[v,c] = w_dice g p_c (a[c; t_vc] - sum_k p_k a[k; t_vk])`` on counted voxels
+(``a[c; t] = a1[c]`` where ``t = 1``, ``a0[c]`` where ``t = 0``) plus the CE gradient, 0 on uncounted voxels; channel mode
+``dz = g (w_dice a p (1 - p) + w_ce (p - t) / numel)`` with ``a = a0 + t (a1 - a0)``.
 """
 from __future__ import annotations
 
@@ -73,13 +94,21 @@ class BCEWithLogitsLoss(torch.nn.Module):
 
 
 class DiceLoss(torch.nn.Module):
-    """metrics.py:726-762, one-channel head: ``batch_dice=True`` (sums over batch and space) and ``batch_dice=False`` (Dice per sample, then the mean)."""
+    """metrics.py:726-762: ``batch_dice=True`` (sums over batch and space) and ``batch_dice=False`` (Dice per sample, then the mean).  One channel:
+    the binary passes; 2..8 channels: the multi-channel passes (module docstring: channel mode for a target of the logits' shape, class mode for a
+    label map, where ``ignore_index = -1`` means -100)."""
 
-    def __init__(self, batch_dice: bool = True, smooth: float = 1e-5):
+    def __init__(self, batch_dice: bool = True, smooth: float = 1e-5, *, ignore_index: int = -1):
         super().__init__()
         self.batch_dice, self.smooth = bool(batch_dice), smooth
+        self.ignore_index = ignore_index if ignore_index != -1 else -100
 
     def forward(self, logits, target):
+        logits = _single_pred(logits, "DiceLoss")
+        if _multi_channel(logits):
+            loss = _DiceFn.apply(logits, target, None, 0.0, 1.0, float(self.smooth), self.batch_dice, self.ignore_index)
+            self._dice_sums_d = _last_dice_sums            # last_label_faults(self)
+            return loss
         if self.batch_dice:
             return _SegLossFn.apply(logits, target, 0.0, 1.0, self.smooth)
         # batch_dice=False (:749-751): the sums stay per sample, the loss is 1 - mean_n dice_n = mean_n (1 - dice_n): the same fused passes once per
@@ -88,14 +117,39 @@ class DiceLoss(torch.nn.Module):
 
 
 class DiceCELoss(torch.nn.Module):
-    """Binary case of metrics.py:764-973: ``w_ce * BCEWithLogits + w_dice * DiceLoss``."""
+    """metrics.py:764-973.  One channel: ``w_ce * BCEWithLogits + w_dice * DiceLoss`` (the binary passes; ``batch_dice`` must stay True there).
+    2..8 channels: the multi-channel passes (module docstring) - ``class_rebalance="manual"`` passes ``class_weights`` to the class mode's CE term.
+    A dict prediction is read at ``"pred"``; a list of predictions (deep supervision) is refused."""
 
-    def __init__(self, w_ce: float = 1.0, w_dice: float = 1.0, smooth: float = 1e-5):
+    def __init__(self, w_ce: float = 1.0, w_dice: float = 1.0, smooth: float = 1e-5, *, num_classes: int = 2, ndim: int = 3, batch_dice: bool = True,
+                 class_rebalance: str = "none", class_weights=(), ignore_index: int = -1):
         super().__init__()
         self.w_ce, self.w_dice, self.smooth = float(w_ce), float(w_dice), float(smooth)
+        self.num_classes, self.ndim, self.batch_dice, self.class_rebalance = int(num_classes), ndim, bool(batch_dice), class_rebalance
+        self.ignore_index = ignore_index if ignore_index != -1 else -100
+        if class_rebalance not in ("none", "manual"):
+            raise NotImplementedError(f"biapy_amd.losses.DiceCELoss: class_rebalance={class_rebalance!r} is not built ('none' or 'manual' with class_weights)")
+        self.class_weights = torch.tensor(list(class_weights), dtype=torch.float32) if class_rebalance == "manual" else None
 
     def forward(self, logits, target):
-        return _SegLossFn.apply(logits, target, self.w_ce, self.w_dice, self.smooth)
+        logits = _single_pred(logits, "DiceCELoss")
+        if not _multi_channel(logits):
+            if not self.batch_dice or self.class_weights is not None:
+                raise NotImplementedError("biapy_amd.losses.DiceCELoss: the one-channel case sums Dice over the batch and takes no class weights")
+            return _SegLossFn.apply(logits, target, self.w_ce, self.w_dice, self.smooth)
+        if target.shape != logits.shape and self.num_classes > 2 and self.num_classes != logits.shape[1] <= DICE_MAXC:
+            raise ValueError(f"DiceCELoss(num_classes={self.num_classes}) got logits of {logits.shape[1]} class channels")
+        w = self.class_weights
+        if w is not None:
+            if target.shape == logits.shape:
+                raise NotImplementedError("biapy_amd.losses.DiceCELoss: class weights belong to the class mode (label-map target)")
+            if w.numel() != logits.shape[1]:
+                raise ValueError(f"{w.numel()} class weights for {logits.shape[1]} class channels")
+            if w.device != logits.device and logits.is_cuda:
+                w = self.class_weights = w.to(logits.device)
+        loss = _DiceFn.apply(logits, target, w, self.w_ce, self.w_dice, self.smooth, self.batch_dice, self.ignore_index)
+        self._dice_sums_d = _last_dice_sums                # last_label_faults(self)
+        return loss
 
 
 @torch.no_grad()
@@ -198,6 +252,105 @@ class _SoftmaxCEFn(torch.autograd.Function):
         L.check(lib.bpx_softmax_ce_bwd(z.data_ptr(), t.data_ptr(), N, C, z.numel() // (N * C), ignore_index, w.data_ptr() if has_w else None,
                                        s.data_ptr(), g.data_ptr(), dz.data_ptr(), L.stream_ptr()))
         return dz.to(dtype), None, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Dice / Dice + CE on 2..8 channels (module docstring): bpx_dice_sums -> bpx_dice_finish -> bpx_dice_bwd
+# ---------------------------------------------------------------------------------------------------------------------------
+def _single_pred(y_pred, who: str):
+    pd = y_pred["pred"] if isinstance(y_pred, dict) and "pred" in y_pred else y_pred
+    if isinstance(pd, (list, tuple)):
+        raise NotImplementedError(f"biapy_amd.losses.{who}: a list of predictions (deep supervision) is not built; use the reference loss")
+    return pd
+
+
+def _multi_channel(logits: torch.Tensor) -> bool:
+    return logits.dim() >= 3 and logits.shape[1] != 1
+
+
+def _prep_dice(logits: torch.Tensor, target: torch.Tensor):
+    """(z, t, class_mode): channel mode for a target of the logits' shape, class mode for a label map."""
+    if logits.dim() < 3 or not 2 <= logits.shape[1] <= 8:
+        raise NotImplementedError("biapy_amd.losses: the multi-channel Dice losses take 2..8 channels; use the reference loss beyond that")
+    class_mode = target.shape != logits.shape
+    if class_mode:
+        if target.dim() == logits.dim() - 1:
+            target = target.unsqueeze(1)
+        if target.dim() != logits.dim() or target.shape[0] != logits.shape[0] or target.shape[1] != 1 or target.shape[2:] != logits.shape[2:]:
+            raise ValueError(f"target shape {tuple(target.shape)} matches neither the logits {tuple(logits.shape)} (channel mode) nor their label map (class mode)")
+    if not logits.is_cuda:
+        raise RuntimeError("biapy_amd.losses run on the MI355X only (logits are on %s); there is no CPU path" % logits.device)
+    return logits.contiguous().to(torch.float32), target.contiguous().to(torch.float32), class_mode      # class ids as floats (exact below 2^24)
+
+
+# the layout csrc/losses.hip writes (DICE_MAXC, DR_*, DICE_COEF_* there; tests/test_dice_losses_cpu.py compares the two files): a row of sums is
+# {I[8], P[8], T[8], CE sum, weight sum, labels out of range, counted voxels}, the coefficients are a head of 8 floats and 16 per group
+DICE_MAXC = 8
+DR_I, DR_P, DR_T, DR_CE, DR_W, DR_FAULT, DR_CNT = 0, DICE_MAXC, 2 * DICE_MAXC, 3 * DICE_MAXC, 3 * DICE_MAXC + 1, 3 * DICE_MAXC + 2, 3 * DICE_MAXC + 3
+DICE_ROW, DICE_COEF_HEAD, DICE_COEF_GROUP = 3 * DICE_MAXC + 4, 8, 2 * DICE_MAXC
+assert lib.bpx_dice_row() == DICE_ROW, "biapy_amd.losses and csrc/losses.hip disagree about the row of Dice sums"
+
+_last_dice_sums = None     # the sums of the latest multi-channel Dice call of any loss object (device tensor; read only when asked)
+
+
+def _dice_sums(z, t, class_mode, weight, w_ce, w_dice, smooth, batch_dice, ignore_index):
+    """(batch totals as a float64 device tensor of bpx_dice_row() columns, the backward's coefficients, the loss as a 0-d float32 device tensor)."""
+    global _last_dice_sums
+    N, C = z.shape[0], z.shape[1]
+    vox = z.numel() // (N * C)
+    nb, row = lib.bpx_dice_blocks(vox), lib.bpx_dice_row()
+    part = torch.empty((N * nb, row), dtype=torch.float32, device=z.device)
+    L.check(lib.bpx_dice_sums(z.data_ptr(), t.data_ptr(), N, C, vox, int(class_mode), ignore_index, L.ptr(weight), int(w_ce != 0.0), part.data_ptr(),
+                              L.stream_ptr()))
+    sums = torch.empty(row, dtype=torch.float64, device=z.device)
+    coef = torch.empty(DICE_COEF_HEAD + DICE_COEF_GROUP * (1 if batch_dice else N), dtype=torch.float32, device=z.device)
+    loss = torch.empty((), dtype=torch.float32, device=z.device)
+    L.check(lib.bpx_dice_finish(part.data_ptr(), N, C, vox, int(class_mode), int(batch_dice), w_ce, w_dice, smooth, sums.data_ptr(), coef.data_ptr(),
+                                loss.data_ptr(), L.stream_ptr()))
+    _last_dice_sums = sums
+    return sums, coef, loss
+
+
+class _DiceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, weight, w_ce, w_dice, smooth, batch_dice, ignore_index):
+        z, t, class_mode = _prep_dice(logits, target)
+        if weight is not None and not class_mode:
+            raise NotImplementedError("biapy_amd.losses: class weights belong to the class mode (label-map target)")
+        _, coef, loss = _dice_sums(z, t, class_mode, weight, w_ce, w_dice, smooth, batch_dice, ignore_index)
+        ctx.save_for_backward(z, t, coef, weight if weight is not None else z.new_empty(0))
+        ctx.cfg = (class_mode, batch_dice, ignore_index, weight is not None, logits.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        z, t, coef, w = ctx.saved_tensors
+        class_mode, batch_dice, ignore_index, has_w, dtype = ctx.cfg
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.to(torch.float32).contiguous()
+        N, C = z.shape[0], z.shape[1]
+        dz = torch.empty_like(z)
+        L.check(lib.bpx_dice_bwd(z.data_ptr(), t.data_ptr(), N, C, z.numel() // (N * C), int(class_mode), int(batch_dice), ignore_index,
+                                 w.data_ptr() if has_w else None, coef.data_ptr(), g.data_ptr(), dz.data_ptr(), L.stream_ptr()))
+        return dz.to(dtype), None, None, None, None, None, None, None
+
+
+@torch.no_grad()
+def soft_dice_per_class(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
+    """``(C,)`` float32 device tensor of the soft Dice per class / channel over the batch, ``(2 I + 1e-5) / (P + T + 1e-5)``, from the sums pass of
+    the multi-channel Dice losses (either mode) - for logging; nothing is read back."""
+    z, t, class_mode = _prep_dice(_single_pred(logits, "soft_dice_per_class"), target)
+    s, _, _ = _dice_sums(z, t, class_mode, None, 0.0, 1.0, 1e-5, True, ignore_index)
+    C = z.shape[1]
+    return ((2.0 * s[DR_I:DR_I + C] + 1e-5) / (s[DR_P:DR_P + C] + s[DR_T:DR_T + C] + 1e-5)).to(torch.float32)
+
+
+def last_label_faults(loss_module=None) -> int:
+    """Labels outside ``[0, C)`` other than ``ignore_index`` that a multi-channel Dice call met (they are left out of every sum, like ignored voxels;
+    channel mode: none).  ``loss_module``: a ``DiceLoss`` / ``DiceCELoss`` object - ITS latest call; without it the latest call of any of them,
+    ``soft_dice_per_class`` included.  The count rides with the sums on the device; THIS call reads it back (one sync) - the train step never does."""
+    sums = _last_dice_sums if loss_module is None else getattr(loss_module, "_dice_sums_d", None)
+    return 0 if sums is None else int(sums[DR_FAULT].item())
 
 
 class CrossEntropyLoss_wrapper(torch.nn.Module):

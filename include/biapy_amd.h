@@ -550,6 +550,29 @@ int bpx_softmax_ce_sums(const float* logits_d, const float* target_d, int N, int
 int bpx_softmax_ce_finish(const float* partials_d, int N, int64_t voxels, double* sums_d, float* loss_d, bpx_stream_t stream);
 int bpx_softmax_ce_bwd(const float* logits_d, const float* target_d, int N, int C, int64_t voxels, int ignore_index, const float* class_w_d,
                        const double* sums_d, const float* gup_d, float* dlogits_d, bpx_stream_t stream);
+/* Dice and Dice + cross-entropy losses of heads with 2..8 channels (biapy_amd/losses.py states the definitions; csrc/losses.hip).  logits (N, C, voxels)
+ * fp32 planar.  class_mode != 0: target (N, 1, voxels) class ids as floats, p = softmax over the channels, a voxel counts if its label is not
+ * ignore_index and lies in [0, C), class_w_d (C floats or NULL) weighs the cross-entropy term only.  class_mode == 0: target (N, C, voxels),
+ * p = sigmoid per channel, the CE term is BCEWithLogits averaged over all elements, class_w_d must be NULL.  Three launches per loss, no atomics,
+ * no host read-back; 16-byte loads where voxels % 4 == 0 and the pointers are 16-byte aligned, dword loads otherwise.
+ *   bpx_dice_sums  : partials_d[N * bpx_dice_blocks(voxels)][bpx_dice_row()], one row per (sample, block):
+ *                    {I[8] = sum p t, P[8] = sum p, T[8] = sum t, sum w nll (class) | sum bce (channel), sum w, labels outside [0, C) other than
+ *                    ignore_index, counted voxels}; with_ce == 0 leaves the CE columns 0
+ *   bpx_dice_finish: sums_d[bpx_dice_row()] = the batch totals (double, fixed order); with U = P + T per class of the batch (batch_dice != 0) or of
+ *                    every sample, and M = C or N C dice terms:  loss_d = w_ce CE + w_dice (1 - sum (2 I + smooth) / (U + smooth) / M), a term whose
+ *                    weight is 0 is not formed;  coef_d[8 + 16 G] floats, G = 1 or N groups: coef[0] = w_ce / (sum w | N C voxels) (0 for w_ce == 0),
+ *                    group g at coef + 8 + 16 g: a0[8] = w_dice (2 I + s) / (M (U + s)^2), a1[8] = a0 - 2 w_dice / (M (U + s))
+ *   bpx_dice_bwd   : class:   dlogits[c] = gup_d[0] (p_c (A_c - sum_k p_k A_k) + coef[0] w[y] (p_c - [c == y])), A_c = a1[c] where c == y, else a0[c];
+ *                             0 on uncounted voxels
+ *                    channel: dlogits[c] = gup_d[0] (A_c p_c (1 - p_c) + coef[0] (p_c - t_c)), A_c = a0[c] + t_c (a1[c] - a0[c]) */
+int bpx_dice_blocks(int64_t voxels);
+int bpx_dice_row(void);
+int bpx_dice_sums(const float* logits_d, const float* target_d, int N, int C, int64_t voxels, int class_mode, int ignore_index, const float* class_w_d,
+                  int with_ce, float* partials_d, bpx_stream_t stream);
+int bpx_dice_finish(const float* partials_d, int N, int C, int64_t voxels, int class_mode, int batch_dice, double w_ce, double w_dice, double smooth,
+                    double* sums_d, float* coef_d, float* loss_d, bpx_stream_t stream);
+int bpx_dice_bwd(const float* logits_d, const float* target_d, int N, int C, int64_t voxels, int class_mode, int batch_dice, int ignore_index,
+                 const float* class_w_d, const float* coef_d, const float* gup_d, float* dlogits_d, bpx_stream_t stream);
 /*   bpx_chan_loss_finish  : loss_d = sum_c weights_d[c] * (fixed-order double sum of channel c's partials) / (N * voxels)
  *   bpx_chan_loss_bwd_fused: bpx_chan_loss_bwd with coef[c] = gup_d[0] * weights_d[c] / (N * voxels) formed in the kernel. */
 int bpx_chan_loss_finish(const float* partials_d, int N, int C, int64_t voxels, const float* weights_d, float* loss_d, bpx_stream_t stream);
