@@ -1936,6 +1936,36 @@ __global__ void __launch_bounds__(256) cast_kernel(const TS* __restrict__ s, TD*
 }
 
 // ------------------------------------------------------------------------------------------------
+// image of 1 .. 16 channels -> the first block's 16-channel NDHWC input (bpx_image_pack16)
+// ------------------------------------------------------------------------------------------------
+// One thread per 16-byte piece of a voxel's 16 output channels (two pieces in the 16-bit modes, four in f32): consecutive lanes store consecutive
+// 16 bytes, so every store instruction fills whole 128-byte lines.  A piece above the image's channels is zeros and loads nothing.  blockIdx.y is the
+// sample, the grid strides over the voxels of one sample; every offset is 64-bit.  The values round as cast_kernel's do (ElemTraits<T>::st).
+template <typename T> __device__ __forceinline__ u32x4_t pack16_as_cast(const float* f) { return pack16<T>(f); }
+template <> __device__ __forceinline__ u32x4_t pack16_as_cast<uint16_t>(const float* f) {
+  u32x4_t v;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = (uint32_t)f32_to_bf16(f[2 * i]) | ((uint32_t)f32_to_bf16(f[2 * i + 1]) << 16);
+  return v;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) image_pack16_kernel(const float* __restrict__ img, int64_t vox, int C, int64_t stride_n, int64_t stride_v,
+                                                           int64_t stride_c, T* __restrict__ out) {
+  constexpr int KPL = ElemTraits<T>::KPL, PPV = 16 / KPL, VPB = 256 / PPV;   // channels per piece, pieces per voxel, voxels per block and step
+  const int q = threadIdx.x % PPV, c0 = q * KPL;
+  const float* src = img + (int64_t)blockIdx.y * stride_n + (int64_t)c0 * stride_c;
+  u32x4_t* dst = reinterpret_cast<u32x4_t*>(out + (int64_t)blockIdx.y * vox * 16) + q;
+  const int64_t step = (int64_t)gridDim.x * VPB;
+  for (int64_t v = (int64_t)blockIdx.x * VPB + threadIdx.x / PPV; v < vox; v += step) {
+    float f[KPL];
+#pragma unroll
+    for (int e = 0; e < KPL; ++e) f[e] = c0 + e < C ? src[v * stride_v + (int64_t)e * stride_c] : 0.f;
+    dst[v * PPV] = pack16_as_cast<T>(f);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // lane-layout self test (one wave)
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) selftest_kernel(float* __restrict__ out) {
@@ -3370,6 +3400,26 @@ extern "C" int bpx_cast(int src_dtype, const void* src_d, int dst_dtype, void* d
   else if (src_dtype == BPX_F32 && dst_dtype == BPX_F16) cast_kernel<float, f16_t><<<grid_for(n), 256, 0, s>>>((const float*)src_d, (f16_t*)dst_d, n);
   else if (src_dtype == BPX_BF16 && dst_dtype == BPX_F32) cast_kernel<uint16_t, float><<<grid_for(n), 256, 0, s>>>((const uint16_t*)src_d, (float*)dst_d, n);
   else BPX_FAIL("%s: unsupported conversion %d -> %d", fn, src_dtype, dst_dtype);
+  BPX_LAUNCH_CHECK(fn);
+  return 0;
+}
+
+extern "C" int bpx_image_pack16(int dtype, int N, int64_t voxels, int C, const float* img_d, int64_t stride_n, int64_t stride_v, int64_t stride_c,
+                                void* out16_d, bpx_stream_t stream) {
+  const char* fn = "bpx_image_pack16";
+  BPX_CHECK(img_d && out16_d, "%s: null pointer", fn);
+  BPX_CHECK(C >= 1 && C <= 16, "%s: 1 <= C <= 16 channels (got %d)", fn, C);
+  BPX_CHECK(N >= 0 && N <= 65535 && voxels >= 0, "%s: bad shape (N = %d, voxels = %lld)", fn, N, (long long)voxels);
+  BPX_CHECK(stride_n >= 0 && stride_v >= 0 && stride_c >= 0, "%s: negative stride", fn);
+  BPX_CHECK(((uintptr_t)out16_d & 15) == 0 && ((uintptr_t)img_d & 3) == 0, "%s: the output must be 16-byte aligned, the image 4-byte", fn);
+  if (N == 0 || voxels == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const int ppv = dtype == BPX_F32 ? 4 : 2;   // 16-byte pieces per voxel
+  dim3 grid((unsigned)std::min<int64_t>(cdiv64(voxels * ppv, 256), std::max<int64_t>(1, 256 * 16 / N)), (unsigned)N);
+  if (dtype == BPX_F32) image_pack16_kernel<float><<<grid, 256, 0, s>>>(img_d, voxels, C, stride_n, stride_v, stride_c, (float*)out16_d);
+  else if (dtype == BPX_BF16) image_pack16_kernel<uint16_t><<<grid, 256, 0, s>>>(img_d, voxels, C, stride_n, stride_v, stride_c, (uint16_t*)out16_d);
+  else if (dtype == BPX_F16) image_pack16_kernel<f16_t><<<grid, 256, 0, s>>>(img_d, voxels, C, stride_n, stride_v, stride_c, (f16_t*)out16_d);
+  else BPX_FAIL("%s: unsupported storage dtype %d", fn, dtype);
   BPX_LAUNCH_CHECK(fn);
   return 0;
 }

@@ -23,6 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import contextlib
 import ctypes as C
+import math
 
 import torch
 
@@ -101,8 +102,15 @@ class NetConfig:
             self.true_feature_maps = tuple(fm)
             fm = [(c + 15) // 16 * 16 for c in fm]
             self.feature_maps = fm
-        if self.in_ch != 1 and self.in_ch % 16:
-            raise NotImplementedError("input channels must be 1 or a multiple of 16")
+        # Images of 2 to 15 channels (RGB, two stains, image + prior) run zero-padded to 16 channels, as the widths above do: `in_ch` becomes what
+        # the kernels see, `true_in_ch` what the image and the first block's two input weights have (pad_input_channels / unpad_input_grads
+        # below; bpx_image_pack16 writes the padded tensor).  Exact: the padded channels are zeros read through zero weight columns.
+        self.true_in_ch = None
+        if 2 <= self.in_ch <= 15:
+            self.true_in_ch, self.in_ch = int(self.in_ch), 16
+        elif self.in_ch != 1 and self.in_ch % 16:
+            raise NotImplementedError(f"input channels must be 1 to 16 or a multiple of 16 (got {self.in_ch}): only images of up to 15 channels are "
+                                      f"zero-padded (to 16)")
         if self.post_up not in (0, 1, 2):
             raise NotImplementedError("post up-sampling: z factor 1 or 2 (y / x factor 2)")
         if sum(self.out_channels) > 8:
@@ -232,6 +240,37 @@ def unpad_channel_grads(G: Dict[str, torch.Tensor], plan) -> Dict[str, torch.Ten
     for k, g in G.items():
         s0, s1 = plan.get(k, (None, None))
         out[k] = _unpad_dim(_unpad_dim(g, 0, s0), 1, s1)
+    return out
+
+
+def input_pad_keys(P: Dict[str, torch.Tensor]) -> List[str]:
+    """The parameters whose dim 1 is the image's channels: the first block's 3x3x3 weight and, in the residual network, its shortcut."""
+    k = block_keys("down_path.0", True)
+    return [n for n in (k["w1"], k["wsc"]) if n in P]
+
+
+def pad_input_channels(P: Dict[str, torch.Tensor], cin: int) -> Dict[str, torch.Tensor]:
+    """Parameters with the input-channel dimension of the first block's weights zero-padded to ``cin`` (NetConfig.true_in_ch -> in_ch); every
+    other entry is the caller's own tensor.  The padded weights are views of one zero-filled scratch: one fill and one copy per weight."""
+    Q = dict(P)
+    keys = input_pad_keys(P)
+    shapes = [(P[n].shape[0], cin) + tuple(P[n].shape[2:]) for n in keys]
+    offs, tot = [], 0
+    for sh in shapes:
+        offs.append(tot)
+        tot += (math.prod(sh) + 63) // 64 * 64            # keep every weight 256-byte aligned
+    flat = P[keys[0]].new_zeros(tot)
+    for n, sh, o in zip(keys, shapes, offs):
+        Q[n] = flat[o:o + math.prod(sh)].view(sh)
+        Q[n][:, :P[n].shape[1]].copy_(P[n])
+    return Q
+
+
+def unpad_input_grads(G: Dict[str, torch.Tensor], c: int) -> Dict[str, torch.Tensor]:
+    """The first ``c`` input-channel columns of the padded gradients (the others belong to weights that do not exist)."""
+    out = dict(G)
+    for n in input_pad_keys(G):
+        out[n] = G[n][:, :c].contiguous()
     return out
 
 
@@ -740,6 +779,20 @@ class ResUNetEngine:
             self._pack_versions[key] = stamp
         return out
 
+    def _pack_image16(self, x: torch.Tensor, st) -> torch.Tensor:
+        """x: the (B, C, D, H, W) fp32 image of a zero-padded-input network (NetConfig.true_in_ch), planar or the channels-last view
+        to_pytorch_format and the sliding-window predictor pass -> the dense (B, D, H, W, 16) tensor of the storage type the first block
+        reads (bpx_image_pack16: one pass, the conversion included).  Any other stride pattern is made planar first."""
+        B, Cin, D, H, W = x.shape
+        vox = D * H * W
+        if x.permute(0, 2, 3, 4, 1).is_contiguous():
+            sv, sc = Cin, 1
+        else:
+            x, sv, sc = x.contiguous(), 1, vox
+        out = torch.empty((B, D, H, W, 16), dtype=self.dtype, device=x.device)
+        L.check(lib.bpx_image_pack16(self.dt, B, vox, Cin, x.data_ptr(), Cin * vox, sv, sc, out.data_ptr(), st))
+        return out
+
     # ------------------------------------------------------------------------------------------
     def _res_block_fwd(self, P, blk: _Blk, B, img: Optional[torch.Tensor], st, cache: bool, want_out_stats: bool, pool=None):
         """Runs one residual block. Returns partial stats (part, tiles) of the block output if requested.
@@ -804,7 +857,8 @@ class ResUNetEngine:
     # ------------------------------------------------------------------------------------------
     def forward(self, P: Dict[str, torch.Tensor], x: Optional[torch.Tensor], head_act: int = 0, save: bool = False, cache_weights: bool = False,
                 x_ndhwc: Optional[torch.Tensor] = None, want_dx: bool = False):
-        """x: (B,C,Z,Y,X) fp32 with channels_last_3d strides (or any layout for C == 1).  Returns logits
+        """x: (B,C,Z,Y,X) fp32 with channels_last_3d strides (or any layout for C == 1; planar or channels-last for the 2 to 15 channels of a
+        zero-padded image, NetConfig.true_in_ch).  Returns logits
         (B,sum(out_ch),Z,Y,X) fp32 in channels-first planar layout, and the saved context (or None).
         ``x_ndhwc``: the input already as a dense (B,Z,Y,X,C) tensor of the storage dtype (``x`` is then ignored); ``want_dx``: the
         backward also returns the gradient of that tensor under the key "__dx__" (super-resolution pre-up-sampling, resunet_sr)."""
@@ -835,7 +889,7 @@ class ResUNetEngine:
             else:
                 self._bn_steps += 1
         plan = self._pad_plan
-        if plan is not None or any(needs_lift(w) for w in P.values()):
+        if plan is not None or cfg.true_in_ch is not None or any(needs_lift(w) for w in P.values()):
             # 2D / anisotropic levels: zero-padded 3x3x3 weights.  Inference keeps the lifted copies while the parameters
             # are unchanged, so that the packed-operand cache (keyed by storage) keeps hitting.
             vers = (_WEIGHTS_EPOCH[0],) + tuple((w.data_ptr(), w._version) for w in P.values())
@@ -843,10 +897,11 @@ class ResUNetEngine:
             if cache_weights and hit is not None and hit[0] == vers:
                 P = hit[1]
             else:
-                P = lift_params(P if plan is None else pad_channels(P, plan))
+                P = P if plan is None else pad_channels(P, plan)
+                P = lift_params(P if cfg.true_in_ch is None else pad_input_channels(P, cfg.in_ch))
                 self._lift_cache = (vers, P) if cache_weights else None
         B, Cin, D0, H0, W0 = x.shape
-        assert Cin == cfg.in_ch, f"expected {cfg.in_ch} input channels, got {Cin}"
+        assert Cin == (cfg.true_in_ch or cfg.in_ch), f"expected {cfg.true_in_ch or cfg.in_ch} input channels, got {Cin}"
         Lv = cfg.depth
         div = 2 ** Lv
         zdiv = 1
@@ -867,6 +922,8 @@ class ResUNetEngine:
             x_ndhwc = None
         elif x_ndhwc is not None:
             img = None
+        elif cfg.true_in_ch is not None:
+            img, x_ndhwc = None, self._pack_image16(x, st)
         else:
             img = None
             xin = x.permute(0, 2, 3, 4, 1).contiguous()
@@ -1160,6 +1217,8 @@ class ResUNetEngine:
             return G
         if self._pad_plan is not None:                        # zero-padded widths: the parameters' own rows / columns of the padded gradients
             G = unpad_channel_grads(G, self._pad_plan)
+        if self.cfg.true_in_ch is not None:                   # zero-padded image: the real input channels' columns of the first block's two weights
+            G = unpad_input_grads(G, self.cfg.true_in_ch)
         return unlift_grads(G, P)                            # after the flush: it is the flush that writes the conv gradients
 
     def _backward(self, P: Dict[str, torch.Tensor], ctx, dlogits: torch.Tensor, on_last_block) -> Dict[str, torch.Tensor]:

@@ -306,8 +306,11 @@ class DataParallelTrainStep:
         if [id(p) for p in params] != [id(p) for p in self.params]:
             return False
         from .engine import needs_lift
-        if getattr(getattr(inner, "cfg", None), "true_feature_maps", None) is not None or any(needs_lift(p) for p in params):
-            return False      # zero-padded widths / 2D or anisotropic kernels: the engine's flat gradient slab has the lifted shapes, not the parameters'
+        cfg = getattr(inner, "cfg", None)
+        if getattr(cfg, "true_feature_maps", None) is not None or getattr(cfg, "true_in_ch", None) is not None or any(needs_lift(p) for p in params):
+            # zero-padded widths / a zero-padded image (2 to 15 channels: the first block's two input weights have 16 input-channel columns in the
+            # slab) / 2D or anisotropic kernels: the engine's flat gradient slab has the padded or lifted shapes, not the parameters'
+            return False
         first = [n.startswith("down_path.0.") for n in names]
         k = sum(first)
         return 0 < k < len(names) and all(first[:k]) and not any(first[k:])      # the first block's parameters are a prefix of the slab

@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib as L
-from .engine import NetConfig, ResUNetEngine, _recs, _Stats, lift_params, unlift_grads
+from .engine import NetConfig, ResUNetEngine, _recs, _Stats, lift_params, pad_input_channels, unlift_grads, unpad_input_grads
 
 lib = L.lib
 
@@ -52,8 +52,11 @@ class UNetEngine(ResUNetEngine):
         self.ndim = ndim
         self.nconvs = nconvs
 
-    # ---- parameters: 2D weights are lifted to one-z-slice 3D weights (engine.lift_params) -----------------------------------
+    # ---- parameters: 2D weights are lifted to one-z-slice 3D weights (engine.lift_params); the first convolution of a network whose image is
+    # zero-padded to 16 channels (NetConfig.true_in_ch) gets zero input-channel columns (engine.pad_input_channels) ------------------------
     def _lift(self, P: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        if self.cfg.true_in_ch is not None:
+            P = pad_input_channels(P, self.cfg.in_ch)
         return lift_params(P) if self.ndim == 2 else P
 
     # ---- forward ------------------------------------------------------------------------------------------------------
@@ -96,7 +99,7 @@ class UNetEngine(ResUNetEngine):
         if self.ndim == 2:
             x = x.unsqueeze(2)
         B, Cin, D0, H0, W0 = x.shape
-        assert Cin == cfg.in_ch, f"expected {cfg.in_ch} input channels, got {Cin}"
+        assert Cin == (cfg.true_in_ch or cfg.in_ch), f"expected {cfg.true_in_ch or cfg.in_ch} input channels, got {Cin}"
         Lv = cfg.depth
         zd = cfg.z_down if self.ndim == 3 else (1,) * Lv
         zdiv = 1
@@ -110,6 +113,8 @@ class UNetEngine(ResUNetEngine):
         Pw = self._lift(P)
         if Cin == 1:
             img, cur = x.reshape(B, D0, H0, W0).contiguous(), None
+        elif cfg.true_in_ch is not None:
+            img, cur = None, self._pack_image16(x, st)
         else:
             img = None
             xin = x.permute(0, 2, 3, 4, 1).contiguous()
@@ -213,6 +218,8 @@ class UNetEngine(ResUNetEngine):
         with self._backward_pass(defer=False):
             G = self._grad_slab(Pw, dlogits.device)        # in the LIFTED shapes, un-lifted at the end
             self._backward(Pw, G, ctx, dlogits)
+        if self.cfg.true_in_ch is not None:
+            G = unpad_input_grads(G, self.cfg.true_in_ch)
         return unlift_grads(G, P)   # gradients in the shapes of the module's parameters
 
     def _backward(self, Pw, G, ctx, dlogits: torch.Tensor) -> None:

@@ -502,6 +502,12 @@ int bpx_upsample_c1_bwd(int dtype, int N, int D, int H, int W, int fz, int fy, i
 
 /* dtype conversion helpers (NDHWC, strided channel slices) */
 int bpx_cast(int src_dtype, const void* src_d, int dst_dtype, void* dst_d, int64_t n, bpx_stream_t stream);
+/* An fp32 image of C channels (1 <= C <= 16), element (n, v, c) at img_d[n*stride_n + v*stride_v + c*stride_c] (strides in elements, 64-bit), as
+ * the dense (N, voxels, 16) tensor of the storage dtype (BPX_F32 / BPX_BF16 / BPX_F16) the first block of a network with a zero-padded input reads:
+ * channels C .. 15 are written as zero, the others round as bpx_cast rounds.  Planar (N, C, voxels): stride_v = 1, stride_c = voxels;
+ * channels-last (N, voxels, C): stride_v = C, stride_c = 1.  out16_d is 16-byte aligned; N <= 65535. */
+int bpx_image_pack16(int dtype, int N, int64_t voxels, int C, const float* img_d, int64_t stride_n, int64_t stride_v, int64_t stride_c,
+                     void* out16_d, bpx_stream_t stream);
 
 /* ---- binary segmentation loss (1-channel head) ---------------------------------------------------------------------------
  * Replaces biapy/engine/metrics.py:493-586 (CrossEntropyLoss_wrapper -> BCEWithLogitsLoss), :726-762 (DiceLoss, batch_dice),
