@@ -1,0 +1,234 @@
+// What sits between `backward` and the end of `optimizer.step()` in the reference loop (biapy/engine/train_engine.py:166-177), for a step that is
+// replayed from a HIP graph and therefore may hold no host value that changes from step to step:
+//   * the global gradient norm and torch's clip coefficient (`clip_grad_norm_`, norm_type 2) as two device floats;
+//   * the Adam / AdamW update of elementwise.hip with beta1 read from device memory (OneCycleLR cycles it every step) and the gradient scaled by
+//     a device float first (the clip coefficient), the product stored back so that `p.grad` holds what `clip_grad_norm_` leaves.
+#include <algorithm>
+
+#include "bpx_common.h"
+
+namespace {
+
+// The chunking of adam_multi_kernel (elementwise.hip): a block takes 4096 consecutive elements of one tensor, 64 tensors to a launch.
+constexpr int OPT_CHUNK = 4096, OPT_MAX = 64;
+struct OptBatch { bpx_adam_tensor t[OPT_MAX]; int first_chunk[OPT_MAX + 1]; int count; };
+struct OptSteps { float* step[256]; int count; };
+
+// block-uniform search: tensor k owns chunks [first_chunk[k], first_chunk[k + 1])
+__device__ __forceinline__ int opt_owner(const OptBatch& b) {
+  int lo = 0, hi = b.count;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int)blockIdx.x >= b.first_chunk[mid]) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// Sum over the 256 threads of a block in a FIXED order (a tree over thread indices): the result does not depend on scheduling, two runs agree bit
+// for bit.  Valid in thread 0.
+__device__ __forceinline__ double opt_block_sum(double v, double* sh) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+#pragma unroll
+  for (int w = 128; w >= 1; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// ------------------------------------------------------------------------------------------------
+// Global gradient norm.  Pass 1: one double per 4096-element chunk, sum of g^2 in fp64 (thread t takes elements t, t + 256, ... of the chunk -
+// four consecutive ones per turn where the gradient is 16-byte aligned - then the tree above).  Pass 2 (one block): the partials in a fixed order.
+// No atomics.  fp64: the order of a sum of n non-negative doubles moves it by at most ~n 2^-53 relative, so only the final rounding to float can
+// differ from any other fp64 evaluation.  A NaN gradient gives a NaN norm and a NaN coefficient, as torch does (error_if_nonfinite=False).
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) grad_sq_partials_kernel(const OptBatch b, double* __restrict__ partials) {
+  __shared__ double sh[256];
+  const int k = opt_owner(b);
+  const int64_t off = (int64_t)((int)blockIdx.x - b.first_chunk[k]) * OPT_CHUNK;
+  const int64_t left = b.t[k].numel - off;
+  const int n = (int)(left < OPT_CHUNK ? left : OPT_CHUNK);
+  const float* __restrict__ g = b.t[k].g + off;
+  double acc = 0.0;
+  if (((uintptr_t)g & 15) == 0) {
+    const int n4 = n >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      const f32x4_t gv = reinterpret_cast<const f32x4_t*>(g)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc += (double)gv[e] * (double)gv[e];
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) acc += (double)g[i] * (double)g[i];
+  } else {
+    for (int i = threadIdx.x; i < n; i += 256) acc += (double)g[i] * (double)g[i];
+  }
+  const double s = opt_block_sum(acc, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// out[0] = ||g||_2, out[1] = min(1, max_norm / (out[0] + 1e-6)) - `clip_grad_norm_`'s coefficient.  The comparison (not fminf) keeps a NaN.
+__global__ void __launch_bounds__(256) grad_norm_finish_kernel(const double* __restrict__ partials, int64_t n, double max_norm, float* __restrict__ out) {
+  __shared__ double sh[256];
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) acc += partials[i];
+  const double s = opt_block_sum(acc, sh);
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(s);
+    const float c = (float)(max_norm / ((double)norm + 1e-6));
+    out[0] = norm;
+    out[1] = c > 1.0f ? 1.0f : c;
+  }
+}
+
+int64_t opt_total_chunks(int count, const bpx_adam_tensor* tensors) {
+  int64_t chunks = 0;
+  for (int k = 0; k < count; ++k) chunks += cdiv64(tensors[k].numel, OPT_CHUNK);
+  return chunks;
+}
+
+}  // namespace
+
+extern "C" int64_t bpx_grad_norm_workspace(int count, const bpx_adam_tensor* tensors) {
+  if (count < 0 || (count > 0 && tensors == nullptr)) return -1;
+  for (int k = 0; k < count; ++k)
+    if (tensors[k].numel < 0 || tensors[k].numel >= ((int64_t)1 << 40)) return -1;
+  return std::max<int64_t>(opt_total_chunks(count, tensors), 1) * (int64_t)sizeof(double);
+}
+
+extern "C" int bpx_grad_norm(int count, const bpx_adam_tensor* tensors, double max_norm, void* workspace_d, int64_t workspace_bytes, float* out_d,
+                             bpx_stream_t stream) {
+  const char* fn = "bpx_grad_norm";
+  BPX_CHECK(count >= 0 && (count == 0 || tensors != nullptr), "%s: bad tensor list", fn);
+  BPX_CHECK(workspace_d && out_d, "%s: null pointer", fn);
+  BPX_CHECK(((uintptr_t)workspace_d & 7) == 0, "%s: the workspace must be 8-byte aligned", fn);
+  for (int k = 0; k < count; ++k)
+    BPX_CHECK(tensors[k].numel >= 0 && tensors[k].numel < ((int64_t)1 << 40) && (tensors[k].numel == 0 || tensors[k].g), "%s: tensor %d has a null gradient or a bad size", fn, k);
+  const int64_t total = opt_total_chunks(count, tensors);
+  BPX_CHECK(workspace_bytes >= std::max<int64_t>(total, 1) * (int64_t)sizeof(double), "%s: workspace of %lld bytes, %lld needed", fn,
+            (long long)workspace_bytes, (long long)(std::max<int64_t>(total, 1) * (int64_t)sizeof(double)));
+  hipStream_t s = (hipStream_t)stream;
+  double* partials = (double*)workspace_d;
+  int64_t done = 0;
+  for (int base = 0; base < count; base += OPT_MAX) {
+    OptBatch b{};
+    b.count = std::min(OPT_MAX, count - base);
+    int64_t chunks = 0;
+    for (int k = 0; k < b.count; ++k) {
+      b.t[k] = tensors[base + k];
+      b.first_chunk[k] = (int)chunks;
+      chunks += cdiv64(b.t[k].numel, OPT_CHUNK);
+      BPX_CHECK(chunks < (1ll << 30), "%s: too many elements in one launch", fn);
+    }
+    b.first_chunk[b.count] = (int)chunks;
+    if (chunks > 0) grad_sq_partials_kernel<<<(unsigned)chunks, 256, 0, s>>>(b, partials + done);
+    done += chunks;
+  }
+  grad_norm_finish_kernel<<<1, 256, 0, s>>>(partials, done, max_norm, out_d);
+  BPX_LAUNCH_CHECK(fn);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// adam_multi_kernel (elementwise.hip: the arithmetic, its order and its types are torch's fused kernel's) with two hyper-parameters on the device:
+//   beta1_d  : a DOUBLE (torch holds the betas as host doubles; OneCycleLR's 0.8999999999999999 is not a float), NULL = the host argument;
+//   gscale_d : a float the gradient is multiplied by first - a plain fp32 product, what `g.mul_(coef)` of clip_grad_norm_ computes - and the
+//              product is stored back to .g; NULL = the gradient as it is (and .g is not written).
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+__global__ void __launch_bounds__(256) adam_dev_kernel(const OptBatch b, const float* __restrict__ lr_d, double lr_h, const double* __restrict__ beta1_d,
+                                                       double beta1_h, double beta2, double eps, double wd, int decoupled,
+                                                       const float* __restrict__ gscale_d) {
+  const int k = opt_owner(b);
+  const bpx_adam_tensor t = b.t[k];
+  const int64_t off = (int64_t)((int)blockIdx.x - b.first_chunk[k]) * OPT_CHUNK;
+  const int n = (int)(t.numel - off < OPT_CHUNK ? t.numel - off : OPT_CHUNK);
+  const double lr = lr_d ? (double)*lr_d : lr_h;
+  const double beta1 = beta1_d ? *beta1_d : beta1_h;
+  const bool scale = gscale_d != nullptr;
+  const float gs = scale ? *gscale_d : 1.0f;
+  const double step = (double)*t.step + 1.0;
+  const float bc1 = (float)(1.0 - pow(beta1, step)), bc2s = (float)sqrt(1.0 - pow(beta2, step));
+  const float step_size = (float)(lr / (double)bc1);
+  const double omb1 = 1.0 - beta1, omb2 = 1.0 - beta2;
+  float* __restrict__ p = t.p + off;
+  float* __restrict__ g = const_cast<float*>(t.g) + off;
+  float* __restrict__ m = t.m + off;
+  float* __restrict__ v = t.v + off;
+  auto upd = [&](float& pf, float gf, float& mf, float& vf) {
+    if (wd != 0.0) { if (decoupled) pf = (float)((double)pf - lr * wd * (double)pf); else gf = (float)((double)gf + (double)pf * wd); }
+    mf = (float)(beta1 * (double)mf + omb1 * (double)gf);
+    vf = (float)(beta2 * (double)vf + omb2 * (double)gf * (double)gf);
+    const float denom = (float)((double)(sqrtf(vf) / bc2s) + eps);
+    pf -= step_size * mf / denom;
+  };
+  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+  if (vec) {
+    const int n4 = n >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      const f32x4_t pv = reinterpret_cast<f32x4_t*>(p)[i], mv = reinterpret_cast<f32x4_t*>(m)[i], vv = reinterpret_cast<f32x4_t*>(v)[i];
+      f32x4_t gv = reinterpret_cast<const f32x4_t*>(g)[i];
+      if (scale) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gv[e] = gv[e] * gs;
+        reinterpret_cast<f32x4_t*>(g)[i] = gv;
+      }
+      float pe[4], me[4], ve[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { pe[e] = pv[e]; me[e] = mv[e]; ve[e] = vv[e]; upd(pe[e], gv[e], me[e], ve[e]); }
+      reinterpret_cast<f32x4_t*>(p)[i] = f32x4_t{pe[0], pe[1], pe[2], pe[3]};
+      reinterpret_cast<f32x4_t*>(m)[i] = f32x4_t{me[0], me[1], me[2], me[3]};
+      reinterpret_cast<f32x4_t*>(v)[i] = f32x4_t{ve[0], ve[1], ve[2], ve[3]};
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) {
+      float gf = g[i];
+      if (scale) { gf = gf * gs; g[i] = gf; }
+      upd(p[i], gf, m[i], v[i]);
+    }
+  } else {
+    for (int i = threadIdx.x; i < n; i += 256) {
+      float gf = g[i];
+      if (scale) { gf = gf * gs; g[i] = gf; }
+      upd(p[i], gf, m[i], v[i]);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) adam_dev_step_inc_kernel(const OptSteps s) {
+  if ((int)threadIdx.x < s.count) *s.step[threadIdx.x] += 1.f;
+}
+
+}  // namespace
+
+extern "C" int bpx_adam_step_dev(int count, const bpx_adam_tensor* tensors, const float* lr_d, double lr, const double* beta1_d, double beta1,
+                                 double beta2, double eps, double weight_decay, int decoupled, const float* gscale_d, bpx_stream_t stream) {
+  const char* fn = "bpx_adam_step_dev";
+  BPX_CHECK(count >= 0 && (count == 0 || tensors != nullptr), "%s: bad tensor list", fn);
+  BPX_CHECK(((uintptr_t)beta1_d & 7) == 0 && ((uintptr_t)gscale_d & 3) == 0 && ((uintptr_t)lr_d & 3) == 0, "%s: misaligned device scalar", fn);
+  hipStream_t s = (hipStream_t)stream;
+  for (int k = 0; k < count; ++k)
+    BPX_CHECK(tensors[k].p && tensors[k].g && tensors[k].m && tensors[k].v && tensors[k].step && tensors[k].numel >= 0 &&
+              tensors[k].numel < ((int64_t)1 << 40), "%s: tensor %d has a null pointer or a bad size", fn, k);
+  for (int base = 0; base < count; base += OPT_MAX) {
+    OptBatch b{};
+    b.count = std::min(OPT_MAX, count - base);
+    int64_t chunks = 0;
+    for (int k = 0; k < b.count; ++k) {
+      b.t[k] = tensors[base + k];
+      b.first_chunk[k] = (int)chunks;
+      chunks += cdiv64(b.t[k].numel, OPT_CHUNK);
+      BPX_CHECK(chunks < (1ll << 30), "%s: too many elements in one launch", fn);
+    }
+    b.first_chunk[b.count] = (int)chunks;
+    if (chunks > 0)
+      adam_dev_kernel<<<(unsigned)chunks, 256, 0, s>>>(b, lr_d, lr, beta1_d, beta1, beta2, eps, weight_decay, decoupled, gscale_d);
+  }
+  for (int base = 0; base < count; base += 256) {   // after every update launch: the updates read the old step
+    OptSteps st{};
+    st.count = std::min(256, count - base);
+    for (int k = 0; k < st.count; ++k) st.step[k] = tensors[base + k].step;
+    adam_dev_step_inc_kernel<<<1, 256, 0, s>>>(st);
+  }
+  BPX_LAUNCH_CHECK(fn);
+  return 0;
+}

@@ -36,31 +36,48 @@ class _LrTensors:
     tensors before capture: PyTorch's schedulers update tensor learning rates in place (``lr_scheduler._update_param_group_val``),
     and a caller (or one of the reference's warm-up schedules) that ASSIGNS ``group["lr"] = value`` is caught by ``sync()``,
     which every replay calls: the value is copied into the captured tensor and the tensor is put back.
-    ``weight_decay`` and the betas stay compile-time constants of the captured step."""
+    ``weight_decay``, ``eps`` and ``beta2`` stay compile-time constants of the captured step.
+
+    ``beta1`` has a device copy as well - a 0-d float64 tensor per group (``beta1s``; None for a group without betas), float64 because torch keeps
+    the betas as host doubles and OneCycleLR (``cycle_momentum``, its default) assigns a new one every step.  ``group["betas"]`` itself stays a
+    tuple of Python floats, which is what torch's own step and ``optim._group_ok`` expect; ``sync()`` fills the device copy when the first beta
+    differs from the value it last saw (``beta1_moved`` then says so) and launches nothing otherwise.  The package's Adam / AdamW step reads
+    it (``GraphedTrainStep``); torch's own captured step cannot."""
 
     def __init__(self, optimizer: torch.optim.Optimizer, device):
         self.opt = optimizer
-        self.lrs = []
+        self.lrs, self.beta1s, self._b1 = [], [], []
+        self.beta1_moved = False
         for g in optimizer.param_groups:
             lr = g["lr"]
             if not torch.is_tensor(lr) or lr.device != torch.device(device) or lr.dtype != torch.float32 or lr.numel() != 1:
                 lr = torch.tensor(float(lr), dtype=torch.float32, device=device)      # also a host / fp64 tensor lr: the captured kernels read a device float
                 g["lr"] = lr
             self.lrs.append(lr)
+            b1 = float(g["betas"][0]) if "betas" in g else None
+            self._b1.append(b1)
+            self.beta1s.append(None if b1 is None else torch.tensor(b1, dtype=torch.float64, device=device))
 
     def sync(self) -> None:
-        for g, t in zip(self.opt.param_groups, self.lrs):
+        for i, (g, t) in enumerate(zip(self.opt.param_groups, self.lrs)):
             cur = g["lr"]
             if cur is not t:
                 t.fill_(float(cur))                    # host scalar -> device tensor, no synchronisation
                 g["lr"] = t
+            if self._b1[i] is not None:
+                b1 = float(g["betas"][0])
+                if b1 != self._b1[i]:
+                    self.beta1s[i].fill_(b1)           # a Python float is a double: the device copy is exact
+                    self._b1[i] = b1
+                    self.beta1_moved = True
 
 
-def _opt_step(optimizer) -> None:
-    """``optimizer.step()``; Adam / AdamW through ``bpx_adam_step`` once their state exists (optim.py)."""
+def _opt_step(optimizer, **kw) -> bool:
+    """[``clip_grad_norm_`` ->] ``optimizer.step()``; Adam / AdamW through ``bpx_adam_step`` / ``bpx_adam_step_dev`` once their state exists
+    (optim.py)."""
     from .optim import step
 
-    step(optimizer)
+    return step(optimizer, **kw)
 
 
 def _bump() -> None:
@@ -99,10 +116,16 @@ class GraphedTrainStep:
 
     ``x`` / ``target`` are copied into static device buffers (pass ``None`` to reuse what is already there); the returned loss
     is a static tensor that the next call overwrites.
+
+    ``max_grad_norm > 0``: ``clip_grad_norm_(parameters, max_grad_norm)`` between ``backward`` and ``opt.step()``, as the reference loop does for
+    ``TRAIN.GRADIENT_CLIP_NORM`` (train_engine.py:166-172); ``grad_norm`` then holds ``[total_norm, coefficient]`` of the last step (two device
+    floats, static memory).  An Adam / AdamW that ``optim.fused_step`` reproduces reads ``beta1`` from device memory (``device_betas`` is True then),
+    so a scheduler that moves it every step (OneCycleLR) is followed; for any other optimizer ``beta1`` is a constant of the captured step and a
+    call after it moved raises.
     """
 
     def __init__(self, model: torch.nn.Module, loss_fn: Callable, optimizer: torch.optim.Optimizer, x: torch.Tensor,
-                 target: torch.Tensor, warmup: int = 3):
+                 target: torch.Tensor, warmup: int = 3, max_grad_norm: float = 0.0):
         if not x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs CUDA/HIP tensors")
         for g in optimizer.param_groups:
@@ -112,13 +135,23 @@ class GraphedTrainStep:
         self.x, self.target = x.clone(), target.clone()
         self._lr = _LrTensors(optimizer, x.device)
         self._out = None
+        self.max_grad_norm = float(max_grad_norm or 0.0)
+        self.grad_norm = torch.zeros(2, dtype=torch.float32, device=x.device) if self.max_grad_norm > 0 else None
+        from .optim import supports
+
+        self.device_betas = supports(optimizer)
+        kw = {}
+        if self.max_grad_norm > 0:
+            kw.update(max_norm=self.max_grad_norm, norm_out=self.grad_norm)
+        if self.device_betas:
+            kw.update(beta1_d=self._lr.beta1s)
 
         def eager():
             optimizer.zero_grad(set_to_none=True)
             self._out = model(self.x)
             loss = loss_fn(self._out, self.target)
             loss.backward()
-            _opt_step(optimizer)
+            self._fused = _opt_step(optimizer, **kw)
             return loss
 
         self.eager = eager
@@ -129,6 +162,7 @@ class GraphedTrainStep:
             self.loss = eager()
         torch.cuda.synchronize()
         _bump()
+        self.device_betas = self.device_betas and self._fused      # fused_step declined the tensors: torch's own step was captured, beta1 a constant
 
     @property
     def outputs(self) -> torch.Tensor:
@@ -141,7 +175,11 @@ class GraphedTrainStep:
         if target is not None:
             self.target.copy_(target, non_blocking=True)
         self._lr.sync()
+        if self._lr.beta1_moved and not self.device_betas:
+            raise RuntimeError("group['betas'][0] changed, but the captured optimizer step holds beta1 as a constant (device_betas is False: only an "
+                               "Adam / AdamW that optim.fused_step reproduces reads it from the device)")
         self.graph.replay()
+        self.opt._opt_called = True                    # as optimizer.step() records: a scheduler stepped after the replay does not warn
         _bump()                                        # parameters changed without a version bump: packed-weight caches are stale
         return self.loss
 

@@ -8,12 +8,19 @@ and three launches of 45 us; ``bpx_adam_step`` uses 4096-element blocks (two lau
 maximize, host-side ``step`` counters, tensor-valued betas / eps / weight decay, registered step hooks, state not yet initialised, non-fp32 or
 non-contiguous tensors, sparse gradients, a missing gradient) - decided for every group before the first launch, so a step is never half done:
 the caller then runs ``optimizer.step()`` itself.
+
+Two things a captured step may not hold as host constants go through ``csrc/optim.hip`` (``max_norm`` / ``beta1_d``, both off by default, in which
+case nothing above changes): gradient clipping - ``bpx_grad_norm`` over ALL groups leaves ``[total_norm, coefficient]`` on the device, every group's
+``bpx_adam_step_dev`` launch multiplies its gradients by that coefficient and stores the product, so ``p.grad`` afterwards is what
+``clip_grad_norm_`` leaves - and a ``beta1`` that a scheduler moves every step (``OneCycleLR``, ``cycle_momentum``), read as a device double.
 """
 from __future__ import annotations
 
 import os
+from typing import Optional, Sequence
 
 import torch
+from torch.nn.utils import clip_grad_norm_
 
 from . import _lib as L
 
@@ -55,9 +62,30 @@ def _has_step_hooks(opt) -> bool:
                 or getattr(O, "_global_optimizer_pre_hooks", None) or getattr(O, "_global_optimizer_post_hooks", None))
 
 
+def supports(optimizer) -> bool:
+    """What can be told before any state exists: an Adam / AdamW without amsgrad / maximize / step hooks is what ``fused_step`` reproduces."""
+    if not _ENABLED or type(optimizer) not in (torch.optim.Adam, torch.optim.AdamW) or _has_step_hooks(optimizer):
+        return False
+    return not any(g.get("amsgrad", False) or g.get("maximize", False) or g.get("differentiable", False) for g in optimizer.param_groups)
+
+
+def _tensor_list(optimizer, ps):
+    arr = (L.AdamTensor * len(ps))()
+    for i, p in enumerate(ps):
+        s = optimizer.state[p]
+        arr[i].p, arr[i].g, arr[i].m, arr[i].v = p.data_ptr(), p.grad.data_ptr(), s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr()
+        arr[i].step, arr[i].numel = s["step"].data_ptr(), p.numel()
+    return arr
+
+
 @torch.no_grad()
-def fused_step(optimizer: torch.optim.Optimizer) -> bool:
-    """One optimizer step through ``bpx_adam_step``; False (nothing done) when the optimizer is not an Adam(W) this kernel reproduces."""
+def fused_step(optimizer: torch.optim.Optimizer, *, max_norm: Optional[float] = None, beta1_d: Optional[Sequence[torch.Tensor]] = None,
+               norm_out: Optional[torch.Tensor] = None) -> bool:
+    """One optimizer step through ``bpx_adam_step``; False (nothing done) when the optimizer is not an Adam(W) this kernel reproduces.
+
+    ``max_norm``: ``clip_grad_norm_(all parameters, max_norm)`` first (one norm over all groups, every group's launch reads the same
+    coefficient); ``norm_out`` (2 device floats, optional) receives ``[total_norm, coefficient]``.  ``beta1_d``: one 0-d float64 device tensor
+    per param group, read by the kernel in place of ``group["betas"][0]``."""
     if not _ENABLED or type(optimizer) not in (torch.optim.Adam, torch.optim.AdamW):
         return False
     if _has_step_hooks(optimizer):            # hooks hang on optimizer.step(): torch's own path runs them
@@ -65,26 +93,54 @@ def fused_step(optimizer: torch.optim.Optimizer) -> bool:
     groups = optimizer.param_groups
     if not all(_group_ok(optimizer, g) for g in groups):     # every refusal is decided BEFORE the first launch: no partial step
         return False
+    clip = max_norm is not None
+    if beta1_d is not None:
+        beta1_d = list(beta1_d)
+        if len(beta1_d) != len(groups) or any(not (torch.is_tensor(b) and b.is_cuda and b.dtype == torch.float64 and b.numel() == 1) for b in beta1_d):
+            return False
+    if clip and norm_out is not None and not (norm_out.is_cuda and norm_out.dtype == torch.float32 and norm_out.numel() == 2 and norm_out.is_contiguous()):
+        return False
     st = L.stream_ptr()
-    for g in groups:
+    if clip:
+        every = [p for g in groups for p in g["params"]]
+        if not every:
+            return False
+        arr = _tensor_list(optimizer, every)
+        nbytes = lib.bpx_grad_norm_workspace(len(every), arr)
+        if nbytes < 0:
+            raise L.BpxError("bpx_grad_norm_workspace: bad tensor list")
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=every[0].device)
+        if norm_out is None:
+            norm_out = torch.empty(2, dtype=torch.float32, device=every[0].device)
+        L.check(lib.bpx_grad_norm(len(every), arr, float(max_norm), ws.data_ptr(), nbytes, norm_out.data_ptr(), st))
+    for k, g in enumerate(groups):
         decoupled = 1 if isinstance(optimizer, torch.optim.AdamW) or g.get("decoupled_weight_decay", False) else 0
         ps = [p for p in g["params"]]
         if not ps:
             continue
-        arr = (L.AdamTensor * len(ps))()
-        for i, p in enumerate(ps):
-            s = optimizer.state[p]
-            arr[i].p, arr[i].g, arr[i].m, arr[i].v = p.data_ptr(), p.grad.data_ptr(), s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr()
-            arr[i].step, arr[i].numel = s["step"].data_ptr(), p.numel()
+        arr = _tensor_list(optimizer, ps)
         lr = g["lr"]
         lr_d, lr_h = (lr.data_ptr(), 0.0) if torch.is_tensor(lr) and lr.is_cuda else (None, float(lr))
         b1, b2 = g["betas"]
-        L.check(lib.bpx_adam_step(len(ps), arr, lr_d, lr_h, float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), decoupled, st))
+        if clip or beta1_d is not None:
+            L.check(lib.bpx_adam_step_dev(len(ps), arr, lr_d, lr_h, None if beta1_d is None else beta1_d[k].data_ptr(), float(b1), float(b2),
+                                          float(g["eps"]), float(g["weight_decay"]), decoupled, norm_out.data_ptr() + 4 if clip else None, st))
+        else:
+            L.check(lib.bpx_adam_step(len(ps), arr, lr_d, lr_h, float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), decoupled, st))
     optimizer._opt_called = True             # what lr_scheduler's wrapper of optimizer.step() records (its "scheduler before optimizer" warning reads it)
     return True
 
 
-def step(optimizer: torch.optim.Optimizer) -> None:
-    """``optimizer.step()``, through the HIP kernel where it applies."""
-    if not fused_step(optimizer):
-        optimizer.step()
+def step(optimizer: torch.optim.Optimizer, *, max_norm: Optional[float] = None, beta1_d: Optional[Sequence[torch.Tensor]] = None,
+         norm_out: Optional[torch.Tensor] = None) -> bool:
+    """[``clip_grad_norm_(parameters, max_norm)`` ->] ``optimizer.step()``, through the HIP kernels where they apply (True); torch's own otherwise
+    (False: the first step of a fresh optimizer, for one - its state does not exist yet)."""
+    if fused_step(optimizer, max_norm=max_norm, beta1_d=beta1_d, norm_out=norm_out):
+        return True
+    if max_norm is not None:
+        total = clip_grad_norm_([p for g in optimizer.param_groups for p in g["params"]], max_norm=max_norm)
+        if norm_out is not None:
+            norm_out[0].copy_(total)
+            norm_out[1].copy_(torch.clamp(max_norm / (total + 1e-6), max=1.0))
+    optimizer.step()
+    return False

@@ -25,8 +25,17 @@ What is different, because the step is ~10 ms on an MI355X and a host round trip
     the model in training mode (``to_pytorch_format`` -> model -> no resize, no training-time activation:
     ``base_workflow.py:855-892`` with ``ce_sigmoid`` / ``ce_softmax`` / ``linear`` heads, :1427; or a loss that applies the model's head
     activations inside its own kernel, ``losses.InstanceChannelsLoss`` built with the same list) - anything else, a ragged last
-    batch, gradient clipping, per-step schedulers, several losses or a memory bank run the eager step.  The optimizer's ``lr``
-    is turned into a device scalar so that scheduler updates between epochs reach the captured optimizer step.
+    batch, several losses or a memory bank run the eager step.  The optimizer's ``lr`` is turned into a device scalar so that
+    scheduler updates reach the captured optimizer step;
+  * in a single process ``TRAIN.GRADIENT_CLIP_NORM > 0`` and the schedules that move the learning rate inside the epoch
+    (``onecycle``; ``warmupcosine`` / ``warmupreduceonplateau``) stay on the replayed step: the gradient norm, the clip
+    coefficient and the scaling are device work inside the captured step (``optim.fused_step(max_norm=...)``), a float that
+    ``adjust_learning_rate`` assigns before the step reaches the captured ``lr`` through ``_LrTensors.sync()``, and
+    ``OneCycleLR.step()`` runs after the replay - its ``lr`` fills the device scalar in place and the ``beta1`` it assigns
+    (``cycle_momentum``) reaches a device double the captured Adam / AdamW step reads (another optimizer class under a
+    momentum-cycling one-cycle schedule keeps the eager step).  The ``lr`` meter of such an epoch costs no read-back per step:
+    the warm-up schedules' host value is taken right after ``adjust_learning_rate``, a one-cycle ``lr`` is accumulated on the
+    device and read once at the end.  With a process group of more than one rank these configurations keep the eager step.
 Contrastive memory banks stay on the reference's loop (``NotImplementedError`` here, as the model classes raise for ``contrast``).
 """
 from __future__ import annotations
@@ -243,11 +252,20 @@ def train_one_epoch(
     per_step_sched = sched_name == "onecycle" and any(isinstance(s, OneCycleLR) for s in schedulers if s is not None)
     capturable = all(g.get("capturable", False) for o in optimizers for g in o.param_groups)
     single = len(optimizers) == 1 and len(loss_names) == 1
-    can_graph = (device.type == "cuda" and capturable and single and clip <= 0 and not per_step_sched and not per_iter_warmup
+    in_epoch = clip > 0 or per_step_sched or per_iter_warmup          # clipping / an lr that moves inside the epoch: replayed in ONE process only
+    # OneCycleLR's cycle_momentum assigns a new beta1 every step: only the package's Adam / AdamW step reads it from the device
+    moving_beta1 = per_step_sched and any(isinstance(s, OneCycleLR) and s.cycle_momentum for s in schedulers)
+    if moving_beta1 and single:
+        from .optim import supports
+        betas_ok = supports(optimizers[0]) and all(getattr(s, "use_beta1", True) for s in schedulers if isinstance(s, OneCycleLR))
+    else:
+        betas_ok = True
+    can_graph = (device.type == "cuda" and capturable and single and not (in_epoch and _world() > 1) and betas_ok
                  and _graphable_model(inner, loss_function))
     if graph == "on" and not can_graph:
         raise ValueError("graph='on' needs a CUDA/HIP device, a biapy_amd model with training-time-linear heads (or a loss fusing them), ONE capturable "
-                         "optimizer and loss, no gradient clipping and no per-step scheduler")
+                         "optimizer and loss; with more than one rank also no gradient clipping and no per-step or per-iteration schedule; under a "
+                         "one-cycle schedule that cycles the momentum an Adam / AdamW without amsgrad, maximize or step hooks")
     use_graph = can_graph and graph in ("on", "auto")
 
     model.train(True)
@@ -258,15 +276,32 @@ def train_one_epoch(
         opt.zero_grad()
     win = _Window(len(loss_names), device)
     lr_sum = [0.0] * len(optimizers)
+    lr_dev = [None] * len(optimizers)                                  # a device-scalar lr is summed on the device: one read at the end
     lr_cnt = 0
     gstep, gshape = None, None
     step = -1
+
+    def sample_lr():
+        """One sample of every optimizer's max lr for the epoch's meter; a device-scalar lr is summed on the device (no read-back per step)."""
+        nonlocal lr_cnt
+        for i, opt in enumerate(optimizers):
+            lrs = [g["lr"] for g in opt.param_groups]
+            if any(torch.is_tensor(v) and v.is_cuda for v in lrs):
+                cur = lrs[0] if len(lrs) == 1 else torch.stack([torch.as_tensor(v, dtype=torch.float32, device=device).reshape(()) for v in lrs]).max()
+                if lr_dev[i] is None:
+                    lr_dev[i] = torch.zeros((), dtype=torch.float64, device=device)
+                lr_dev[i] += cur.detach().reshape(())                  # one small launch
+            else:
+                lr_sum[i] += max(float(v) for v in lrs)
+        lr_cnt += 1
+
     n_steps = len(data_loader) if hasattr(data_loader, "__len__") else 0
     for step, (batch, targets) in enumerate(data_loader):
         if per_iter_warmup:                                            # per-iteration schedules (train_engine.py:118-121)
             for sched, opt in zip(schedulers, optimizers):
                 if sched is not None and hasattr(sched, "adjust_learning_rate"):
                     sched.adjust_learning_rate(opt, step / max(n_steps, 1) + epoch)
+            sample_lr()                                                # HERE: an assigned float is still a host value (no read-back)
         targets = prepare_targets(targets, batch)
         if patch_size and tuple(batch.shape[1:-1]) != tuple(patch_size[:-1]):
             raise ValueError(
@@ -277,16 +312,25 @@ def train_one_epoch(
         if use_graph:
             x = to_pytorch_format(batch, device)
             if gstep is None:
-                gstep, gshape = _graph_step(inner, model, loss_function, optimizers[0], x, targets)
+                gstep, gshape = _graph_step(inner, model, loss_function, optimizers[0], x, targets, clip)
                 if gstep is None:                                      # the loss function is not a plain tensor loss: eager epoch
                     use_graph = False
+                elif moving_beta1 and not getattr(gstep, "device_betas", False):
+                    # optim.fused_step declined the tensors at capture (a parameter without a gradient, non-contiguous or non-fp32 state):
+                    # torch's own step was captured with beta1 as a constant, which a momentum-cycling one-cycle schedule would outrun
+                    if graph == "on":
+                        raise ValueError("graph='on': the captured optimizer step cannot follow the beta1 that the one-cycle schedule cycles "
+                                         "(optim.fused_step declined this optimizer's tensors)")
+                    gstep, use_graph = None, False
             if use_graph:
                 if (tuple(x.shape), tuple(targets.shape)) == gshape:
                     losses = [gstep(x, targets)]
                     outputs = gstep.outputs
                 else:                                                  # ragged last batch: same three phases, eagerly
-                    loss, outputs = _eager_step(inner, loss_function, optimizers[0], x, targets)
+                    loss, outputs = _eager_step(inner, loss_function, optimizers[0], x, targets, clip)
                     losses = [loss]
+                if per_step_sched and isinstance(schedulers[0], OneCycleLR):
+                    schedulers[0].step()                               # after the replay, and after a ragged last batch
                 if metric_function is not None:
                     metric_function(outputs, targets, metric_logger=logger)
         if not use_graph:
@@ -306,10 +350,8 @@ def train_one_epoch(
                     schedulers[i].step()
                 optimizers[i].zero_grad()
         win.add(losses)
-        if per_step_sched or per_iter_warmup:                          # the learning rate moves inside the epoch: sample it per step
-            for i, opt in enumerate(optimizers):
-                lr_sum[i] += max(float(g["lr"]) for g in opt.param_groups)
-            lr_cnt += 1
+        if per_step_sched and not per_iter_warmup:                     # one-cycle: the learning rate of the NEXT step, sampled per step
+            sample_lr()
         if win.pending >= sync_every:
             win.flush(logger, loss_names, log_writer)
             if verbose:
@@ -322,7 +364,8 @@ def train_one_epoch(
         name = lr_names[i] if i < len(lr_names) else f"lr_{i}"
         m = SmoothedValue(window_size=1, fmt="{value:.6f}")
         if lr_cnt:
-            m.total, m.count, m.last = lr_sum[i], lr_cnt, lr_sum[i] / lr_cnt
+            total = lr_sum[i] + (float(lr_dev[i]) if lr_dev[i] is not None else 0.0)
+            m.total, m.count, m.last = total, lr_cnt, total / lr_cnt
         else:
             lr = max(float(g["lr"]) for g in opt.param_groups)         # constant inside the epoch: one read (a device scalar under graphs)
             m.total, m.count, m.last = lr * steps_done, steps_done, lr
@@ -334,11 +377,11 @@ def train_one_epoch(
     return {k: meter.global_avg for k, meter in logger.meters.items()}, step
 
 
-def _graph_step(inner, model, loss_function, optimizer, x, t):
-    """The captured step of (model, loss, optimizer, shapes), built once and cached on the model across epochs."""
+def _graph_step(inner, model, loss_function, optimizer, x, t, clip=0.0):
+    """The captured step of (model, loss, optimizer, shapes, clip norm), built once and cached on the model across epochs."""
     from . import graphs
 
-    key = (id(optimizer), id(loss_function), tuple(x.shape), tuple(t.shape), _world())
+    key = (id(optimizer), id(loss_function), tuple(x.shape), tuple(t.shape), _world(), float(clip))
     cached = getattr(inner, "_bpx_graph_step", None)
     if cached is not None and cached[0] == key:                        # later epochs replay the graphs captured in the first one
         return cached[1], (tuple(x.shape), tuple(t.shape))
@@ -356,7 +399,7 @@ def _graph_step(inner, model, loss_function, optimizer, x, t):
     if multi:
         gstep = graphs.DataParallelTrainStep(inner, loss_function, optimizer, x, t, broadcast_parameters=False)
     else:
-        gstep = graphs.GraphedTrainStep(inner, loss_function, optimizer, x, t)
+        gstep = graphs.GraphedTrainStep(inner, loss_function, optimizer, x, t, max_grad_norm=clip)
     _restore(inner, optimizer, snap)
     inner._bpx_graph_step = (key, gstep)
     return gstep, (tuple(x.shape), tuple(t.shape))
@@ -410,7 +453,7 @@ def _restore(model, optimizer, snap) -> None:
     torch.cuda.synchronize()
 
 
-def _eager_step(model, loss_function, optimizer, x, t):
+def _eager_step(model, loss_function, optimizer, x, t, clip=0.0):
     """One eager step for a batch the captured graphs do not fit (ragged last batch); gradients averaged over the ranks.
     Replays do not depend on ``p.grad`` (the graphs hold raw addresses), so dropping the gradients here is safe."""
     optimizer.zero_grad(set_to_none=True)                              # p.grad may still alias a graph's private gradient buffers
@@ -426,6 +469,8 @@ def _eager_step(model, loss_function, optimizer, x, t):
         for g in grads:
             g.copy_(pack[off:off + g.numel()].view_as(g))
             off += g.numel()
+    if clip > 0:
+        clip_grad_norm_([p for g in optimizer.param_groups for p in g["params"]], max_norm=clip)
     optimizer.step()
     optimizer.zero_grad(set_to_none=True)
     return loss, outputs.detach()

@@ -171,6 +171,20 @@ typedef struct bpx_adam_tensor {
 int bpx_adam_step(int count, const bpx_adam_tensor* tensors, const float* lr_d, double lr, double beta1, double beta2, double eps,
                   double weight_decay, int decoupled, bpx_stream_t stream);
 
+/* Global L2 norm of the gradients (`.g`, `.numel` of every entry; the other fields are not read) of `count` tensors - every param group of an
+ * optimizer in ONE list - and the coefficient of torch's clip_grad_norm_ (norm_type 2, error_if_nonfinite False), both left on the device:
+ *   out_d[0] = (float)sqrt(sum g^2)      out_d[1] = min(1.0f, (float)(max_norm / ((double)out_d[0] + 1e-6)))
+ * The squares are summed in fp64 in a fixed order (one double per 4096-element chunk, then one block over the chunks; no atomics): two calls agree
+ * bit for bit.  A NaN gradient gives NaN for both.  workspace_d: bpx_grad_norm_workspace bytes (8-byte aligned, device), -1 for a bad list. */
+int64_t bpx_grad_norm_workspace(int count, const bpx_adam_tensor* tensors);
+int bpx_grad_norm(int count, const bpx_adam_tensor* tensors, double max_norm, void* workspace_d, int64_t workspace_bytes, float* out_d,
+                  bpx_stream_t stream);
+/* bpx_adam_step with hyper-parameters that change between the replays of a captured step: beta1_d (device DOUBLE, as torch keeps the betas;
+ * NULL = the host argument) and gscale_d (device float, NULL = none): every gradient element is first multiplied by it - one fp32 product - and the
+ * product is stored back to `.g`, which is what clip_grad_norm_ leaves in p.grad.  Same arithmetic, order and types otherwise. */
+int bpx_adam_step_dev(int count, const bpx_adam_tensor* tensors, const float* lr_d, double lr, const double* beta1_d, double beta1, double beta2,
+                      double eps, double weight_decay, int decoupled, const float* gscale_d, bpx_stream_t stream);
+
 /* Conv3d k=3 "same" + bias (biapy/models/blocks.py:154-157), implicit GEMM on MFMA with an
  * LDS-staged input halo.  Fusions:
  *   prologue : x <- act(scale*x+shift) with in_norm_d[n*Cin+c]  (the InstanceNorm+ELU that
