@@ -56,6 +56,7 @@ _SIGS = {
     "bpx_grad_norm_workspace": ([_i, _vp], _i64),
     "bpx_grad_norm": ([_i, _vp, C.c_double, _vp, _i64, _vp, _vp], _i),
     "bpx_adam_step_dev": ([_i, _vp, _vp, C.c_double, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _i, _vp, _vp], _i),
+    "bpx_sgd_step": ([_i, _vp, _vp, C.c_double, _vp, C.c_double, C.c_double, C.c_double, _i, _vp, _vp], _i),
     "bpx_scan_blocks": ([_i64], _i),
     "bpx_select_workspace": ([], _i64),
     "bpx_select_kth_f32": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),

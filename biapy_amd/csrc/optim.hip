@@ -2,7 +2,10 @@
 // replayed from a HIP graph and therefore may hold no host value that changes from step to step:
 //   * the global gradient norm and torch's clip coefficient (`clip_grad_norm_`, norm_type 2) as two device floats;
 //   * the Adam / AdamW update of elementwise.hip with beta1 read from device memory (OneCycleLR cycles it every step) and the gradient scaled by
-//     a device float first (the clip coefficient), the product stored back so that `p.grad` holds what `clip_grad_norm_` leaves.
+//     a device float first (the clip coefficient), the product stored back so that `p.grad` holds what `clip_grad_norm_` leaves;
+//   * the SGD update (momentum, dampening, Nesterov, weight decay) in the fp32 arithmetic and order of torch's `_multi_tensor_sgd`, one pass over
+//     parameter, gradient and momentum buffer, with `lr`, the momentum (OneCycleLR cycles it on an SGD) and the clip coefficient read from
+//     device memory.
 #include <algorithm>
 
 #include "bpx_common.h"
@@ -228,6 +231,125 @@ extern "C" int bpx_adam_step_dev(int count, const bpx_adam_tensor* tensors, cons
     st.count = std::min(256, count - base);
     for (int k = 0; k < st.count; ++k) st.step[k] = tensors[base + k].step;
     adam_dev_step_inc_kernel<<<1, 256, 0, s>>>(st);
+  }
+  BPX_LAUNCH_CHECK(fn);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// SGD.  torch's `_multi_tensor_sgd` as ONE pass: every foreach op of it is an fp32 operation with its scalar rounded to float once, and so is
+// every line below - products and sums are kept apart (no contraction), so each rounds as the foreach op it stands for:
+//   d = g + wd * p                      (WD)
+//   b = b * mom;  b = b + (1 - dampening) * d;  u = b        (MODE 1)      u = d + mom * b   (MODE 2, Nesterov)      u = d   (MODE 0: no buffer)
+//   p = p + (-lr) * u
+// lr_d (float), momentum_d (DOUBLE: the scheduler assigns host doubles; rounded to float here) and gscale_d (float; g = g * gscale first, one fp32
+// product, stored back) are read from device memory when not NULL.  No atomics, nothing depends on scheduling.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+template <int MODE, bool WD>
+__device__ __forceinline__ void sgd_update(float& p, float g, float& b, float nlr, float mom, float omd, float wd) {
+#pragma clang fp contract(off)
+  float d = g;
+  if (WD) { const float t = wd * p; d = g + t; }
+  float u = d;
+  if (MODE != 0) {
+    float bb = b * mom;
+    const float t = omd * d;
+    bb = bb + t;
+    b = bb;
+    if (MODE == 2) { const float t2 = mom * bb; u = d + t2; } else u = bb;
+  }
+  const float t3 = nlr * u;
+  p = p + t3;
+}
+
+template <int MODE, bool WD>
+__global__ void __launch_bounds__(256) sgd_kernel(const OptBatch b, const float* __restrict__ lr_d, float lr_h, const double* __restrict__ mom_d,
+                                                  float mom_h, float omd, float wd, const float* __restrict__ gscale_d) {
+  const int k = opt_owner(b);
+  const bpx_adam_tensor t = b.t[k];
+  const int64_t off = (int64_t)((int)blockIdx.x - b.first_chunk[k]) * OPT_CHUNK;
+  const int n = (int)(t.numel - off < OPT_CHUNK ? t.numel - off : OPT_CHUNK);
+  const float nlr = -(lr_d ? *lr_d : lr_h);
+  const float mom = mom_d ? (float)*mom_d : mom_h;
+  const bool scale = gscale_d != nullptr;
+  const float gs = scale ? *gscale_d : 1.0f;
+  float* __restrict__ p = t.p + off;
+  float* __restrict__ g = const_cast<float*>(t.g) + off;
+  float* __restrict__ m = MODE != 0 ? t.m + off : nullptr;
+  auto one = [&](int i) {
+    float gf = g[i];
+    if (scale) { gf = gf * gs; g[i] = gf; }
+    float pf = p[i], bf = 0.f;
+    if (MODE != 0) bf = m[i];
+    sgd_update<MODE, WD>(pf, gf, bf, nlr, mom, omd, wd);
+    p[i] = pf;
+    if (MODE != 0) m[i] = bf;
+  };
+  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m) & 15) == 0);
+  if (vec) {
+    const int n4 = n >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      f32x4_t pv = reinterpret_cast<f32x4_t*>(p)[i], gv = reinterpret_cast<const f32x4_t*>(g)[i], mv = {0.f, 0.f, 0.f, 0.f};
+      if (MODE != 0) mv = reinterpret_cast<f32x4_t*>(m)[i];
+      if (scale) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gv[e] = gv[e] * gs;
+        reinterpret_cast<f32x4_t*>(g)[i] = gv;
+      }
+      float pe[4], me[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { pe[e] = pv[e]; me[e] = mv[e]; sgd_update<MODE, WD>(pe[e], gv[e], me[e], nlr, mom, omd, wd); }
+      reinterpret_cast<f32x4_t*>(p)[i] = f32x4_t{pe[0], pe[1], pe[2], pe[3]};
+      if (MODE != 0) reinterpret_cast<f32x4_t*>(m)[i] = f32x4_t{me[0], me[1], me[2], me[3]};
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) one(i);
+  } else {
+    for (int i = threadIdx.x; i < n; i += 256) one(i);
+  }
+}
+
+}  // namespace
+
+extern "C" int bpx_sgd_step(int count, const bpx_adam_tensor* tensors, const float* lr_d, double lr, const double* momentum_d, double momentum,
+                            double dampening, double weight_decay, int nesterov, const float* gscale_d, bpx_stream_t stream) {
+  const char* fn = "bpx_sgd_step";
+  BPX_CHECK(count >= 0 && (count == 0 || tensors != nullptr), "%s: bad tensor list", fn);
+  BPX_CHECK(((uintptr_t)momentum_d & 7) == 0 && ((uintptr_t)gscale_d & 3) == 0 && ((uintptr_t)lr_d & 3) == 0, "%s: misaligned device scalar", fn);
+  const bool use_mom = momentum_d != nullptr || momentum != 0.0;
+  BPX_CHECK(!nesterov || use_mom, "%s: Nesterov momentum needs a momentum", fn);
+  for (int k = 0; k < count; ++k) {
+    BPX_CHECK(tensors[k].p && tensors[k].g && tensors[k].numel >= 0 && tensors[k].numel < ((int64_t)1 << 40),
+              "%s: tensor %d has a null pointer or a bad size", fn, k);
+    BPX_CHECK(!use_mom || tensors[k].m, "%s: tensor %d has no momentum buffer, and momentum is in use", fn, k);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int mode = !use_mom ? 0 : (nesterov ? 2 : 1);
+  const bool has_wd = weight_decay != 0.0;
+  const float lr_h = (float)lr, mom_h = (float)momentum, omd = (float)(1.0 - dampening), wd = (float)weight_decay;
+  for (int base = 0; base < count; base += OPT_MAX) {
+    OptBatch b{};
+    b.count = std::min(OPT_MAX, count - base);
+    int64_t chunks = 0;
+    for (int k = 0; k < b.count; ++k) {
+      b.t[k] = tensors[base + k];
+      b.first_chunk[k] = (int)chunks;
+      chunks += cdiv64(b.t[k].numel, OPT_CHUNK);
+      BPX_CHECK(chunks < (1ll << 30), "%s: too many elements in one launch", fn);
+    }
+    b.first_chunk[b.count] = (int)chunks;
+    if (chunks == 0) continue;
+#define BPX_SGD_LAUNCH(M, W) sgd_kernel<M, W><<<(unsigned)chunks, 256, 0, s>>>(b, lr_d, lr_h, momentum_d, mom_h, omd, wd, gscale_d)
+    switch (mode * 2 + (has_wd ? 1 : 0)) {
+      case 0: BPX_SGD_LAUNCH(0, false); break;
+      case 1: BPX_SGD_LAUNCH(0, true); break;
+      case 2: BPX_SGD_LAUNCH(1, false); break;
+      case 3: BPX_SGD_LAUNCH(1, true); break;
+      case 4: BPX_SGD_LAUNCH(2, false); break;
+      default: BPX_SGD_LAUNCH(2, true); break;
+    }
+#undef BPX_SGD_LAUNCH
   }
   BPX_LAUNCH_CHECK(fn);
   return 0;

@@ -8,7 +8,8 @@ The reference has no equivalent (its step is ``base_workflow.py:1068-1137`` + ``
 an addition of the MI355X path, used by ``bench.py`` and offered to callers who train on fixed-size patches - which is what
 BiaPy does (``DATA.PATCH_SIZE`` is fixed per run, ``TRAIN.BATCH_SIZE`` with ``drop_last``).
 
-Constraints (those of ``torch.cuda.graphs``): static shapes; the optimizer must be built with ``capturable=True``; no host
+Constraints (those of ``torch.cuda.graphs``): static shapes; the optimizer must be built with ``capturable=True`` (or be a ``torch.optim.SGD``
+that ``optim.supports_sgd`` accepts: its step is the package's own kernel, torch's cannot be captured with a device ``lr``); no host
 synchronisation inside the step; no autograd graph of an earlier eager backward may still be referenced when a graphed step is
 built (``del loss`` first - the constructors raise a ``RuntimeError`` otherwise, see ``_warm``).  ``GraphedTrainStep`` is single-process; ``DataParallelTrainStep`` is the multi-GPU form
 (one process per GPU): the same two replays with ONE flat-gradient RCCL all-reduce between them.
@@ -42,11 +43,14 @@ class _LrTensors:
     the betas as host doubles and OneCycleLR (``cycle_momentum``, its default) assigns a new one every step.  ``group["betas"]`` itself stays a
     tuple of Python floats, which is what torch's own step and ``optim._group_ok`` expect; ``sync()`` fills the device copy when the first beta
     differs from the value it last saw (``beta1_moved`` then says so) and launches nothing otherwise.  The package's Adam / AdamW step reads
-    it (``GraphedTrainStep``); torch's own captured step cannot."""
+    it (``GraphedTrainStep``); torch's own captured step cannot.
+
+    ``momenta`` is the same for ``group["momentum"]`` (an SGD: OneCycleLR cycles it in place of beta1): a 0-d float64 tensor per group whose
+    momentum is greater than 0, None otherwise, filled by ``sync()`` when the value differs from the one last seen.  ``bpx_sgd_step`` reads it."""
 
     def __init__(self, optimizer: torch.optim.Optimizer, device):
         self.opt = optimizer
-        self.lrs, self.beta1s, self._b1 = [], [], []
+        self.lrs, self.beta1s, self._b1, self.momenta, self._mom = [], [], [], [], []
         self.beta1_moved = False
         for g in optimizer.param_groups:
             lr = g["lr"]
@@ -57,6 +61,10 @@ class _LrTensors:
             b1 = float(g["betas"][0]) if "betas" in g else None
             self._b1.append(b1)
             self.beta1s.append(None if b1 is None else torch.tensor(b1, dtype=torch.float64, device=device))
+            mom = g.get("momentum", None)
+            mom = float(mom) if mom is not None and not torch.is_tensor(mom) and mom > 0 else None
+            self._mom.append(mom)
+            self.momenta.append(None if mom is None else torch.tensor(mom, dtype=torch.float64, device=device))
 
     def sync(self) -> None:
         for i, (g, t) in enumerate(zip(self.opt.param_groups, self.lrs)):
@@ -70,14 +78,37 @@ class _LrTensors:
                     self.beta1s[i].fill_(b1)           # a Python float is a double: the device copy is exact
                     self._b1[i] = b1
                     self.beta1_moved = True
+            if self._mom[i] is not None:
+                mom = float(g["momentum"])
+                if mom != self._mom[i]:
+                    self.momenta[i].fill_(mom)
+                    self._mom[i] = mom
 
 
 def _opt_step(optimizer, **kw) -> bool:
-    """[``clip_grad_norm_`` ->] ``optimizer.step()``; Adam / AdamW through ``bpx_adam_step`` / ``bpx_adam_step_dev`` once their state exists
-    (optim.py)."""
+    """[``clip_grad_norm_`` ->] ``optimizer.step()``; Adam / AdamW through ``bpx_adam_step`` / ``bpx_adam_step_dev`` and SGD through
+    ``bpx_sgd_step`` once their state exists (optim.py)."""
     from .optim import step
 
     return step(optimizer, **kw)
+
+
+_SGD_NOT_READY = ("torch's own SGD step cannot be captured (it reads the device lr back to the host) and the package's step (optim.fused_sgd_step) "
+                  "declined this optimizer after the warm-up: with momentum it needs one warm-up step for torch to create the momentum buffers and "
+                  "one more of its own (warmup >= 2 for an optimizer without state), and fp32 contiguous CUDA parameters that all receive gradients")
+
+
+def _capturable(optimizer) -> bool:
+    """True: an SGD whose step is the package's kernel; False: an optimizer built with capturable=True; ValueError otherwise."""
+    from .optim import supports_sgd
+
+    if supports_sgd(optimizer):
+        return True
+    for g in optimizer.param_groups:
+        if not g.get("capturable", False):
+            raise ValueError("build the optimizer with capturable=True to capture its step (a torch.optim.SGD without maximize, differentiable, step "
+                             "hooks or tensor hyper-parameters needs no such key)")
+    return False
 
 
 def _bump() -> None:
@@ -121,16 +152,16 @@ class GraphedTrainStep:
     ``TRAIN.GRADIENT_CLIP_NORM`` (train_engine.py:166-172); ``grad_norm`` then holds ``[total_norm, coefficient]`` of the last step (two device
     floats, static memory).  An Adam / AdamW that ``optim.fused_step`` reproduces reads ``beta1`` from device memory (``device_betas`` is True then),
     so a scheduler that moves it every step (OneCycleLR) is followed; for any other optimizer ``beta1`` is a constant of the captured step and a
-    call after it moved raises.
+    call after it moved raises.  A ``torch.optim.SGD`` that ``optim.supports_sgd`` accepts needs no ``capturable`` key: its captured step is
+    ``bpx_sgd_step``, which reads ``lr``, the momentum (``device_momentum`` is True then) and the clip coefficient from the device; if that step
+    declined the optimizer on the last warm-up step the constructor raises ``ValueError`` before anything is captured.
     """
 
     def __init__(self, model: torch.nn.Module, loss_fn: Callable, optimizer: torch.optim.Optimizer, x: torch.Tensor,
                  target: torch.Tensor, warmup: int = 3, max_grad_norm: float = 0.0):
         if not x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs CUDA/HIP tensors")
-        for g in optimizer.param_groups:
-            if not g.get("capturable", False):
-                raise ValueError("build the optimizer with capturable=True to capture its step")
+        sgd = _capturable(optimizer)
         self.model, self.loss_fn, self.opt = model, loss_fn, optimizer
         self.x, self.target = x.clone(), target.clone()
         self._lr = _LrTensors(optimizer, x.device)
@@ -145,6 +176,8 @@ class GraphedTrainStep:
             kw.update(max_norm=self.max_grad_norm, norm_out=self.grad_norm)
         if self.device_betas:
             kw.update(beta1_d=self._lr.beta1s)
+        if sgd:
+            kw.update(momentum_d=self._lr.momenta)
 
         def eager():
             optimizer.zero_grad(set_to_none=True)
@@ -155,7 +188,11 @@ class GraphedTrainStep:
             return loss
 
         self.eager = eager
+        self._fused = False
         _warm(eager, warmup)
+        if sgd and not self._fused:                    # before any capture begins: torch's SGD step never enters one
+            raise ValueError("GraphedTrainStep: " + _SGD_NOT_READY)
+        self.device_momentum = sgd                     # the captured SGD step reads group["momentum"] from the device (OneCycleLR cycles it)
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
@@ -241,13 +278,15 @@ class DataParallelTrainStep:
         if graph:
             if not x.is_cuda:
                 raise RuntimeError("graph=True needs CUDA/HIP tensors")
-            for g in optimizer.param_groups:
-                if not g.get("capturable", False):
-                    raise ValueError("build the optimizer with capturable=True to capture its step")
+            sgd = _capturable(optimizer)
+        else:
+            sgd = False
         if self.world > 1 and broadcast_parameters:                      # DDP's construction-time broadcast from rank 0
             broadcast_parameters_from_rank0(self.params, group)
         self.x, self.target = x.clone(), target.clone()
         self._lr = _LrTensors(optimizer, dev) if graph else None
+        self._sgd = sgd
+        self._opt_kw = dict(momentum_d=self._lr.momenta) if sgd else {}
         self._out = None
         inv = 1.0 / self.world
         if overlap and self._overlap_ok(model, x):
@@ -271,7 +310,7 @@ class DataParallelTrainStep:
         def update():
             if self.world > 1:
                 self.flat_grad.mul_(inv)
-            _opt_step(optimizer)
+            _opt_step(optimizer, **self._opt_kw)
 
         self._fwd_bwd, self._update = fwd_bwd, update
         self.graphs = None
@@ -312,6 +351,7 @@ class DataParallelTrainStep:
                     update()
 
             _warm(eager, warmup, side)
+            self._check_sgd_ready()
             g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(g1, stream=side, capture_error_mode="thread_local"):
                 self.loss = fwd_bwd_adopt() if self.adopted else fwd_bwd()
@@ -402,7 +442,7 @@ class DataParallelTrainStep:
         def update():
             if self.world > 1:
                 self.flat_grad.mul_(inv)
-            _opt_step(optimizer)
+            _opt_step(optimizer, **self._opt_kw)
 
         def eager():
             loss = fwd_bwd()
@@ -419,6 +459,7 @@ class DataParallelTrainStep:
         side = torch.cuda.Stream()
         with torch.no_grad():
             _warm(eager, warmup, side)
+            self._check_sgd_ready()
             g1a, g1b, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             # what torch.cuda.graph does on entry and this raw capture_begin does not: collect unreachable cycles NOW, so that no earlier
             # graph, event or tensor (a previous step object, say) is destroyed by a garbage-collection pass inside the capture
@@ -454,6 +495,14 @@ class DataParallelTrainStep:
         self._check_views()
         self.graphs = (g1a, g1b, g2)
         _bump()
+
+    def _check_sgd_ready(self) -> None:
+        """Before any capture begins: the optimizer phase of an SGD must be the package's step (torch's cannot be captured with a device lr)."""
+        if self._sgd:
+            from .optim import sgd_ready
+
+            if not sgd_ready(self.opt):
+                raise ValueError("DataParallelTrainStep: " + _SGD_NOT_READY)
 
     def _adopted_flat(self) -> Optional[torch.Tensor]:
         """The gradients as one flat tensor if they are consecutive contiguous fp32 views of one allocation, in parameter order."""

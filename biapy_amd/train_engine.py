@@ -32,8 +32,9 @@ What is different, because the step is ~10 ms on an MI355X and a host round trip
     coefficient and the scaling are device work inside the captured step (``optim.fused_step(max_norm=...)``), a float that
     ``adjust_learning_rate`` assigns before the step reaches the captured ``lr`` through ``_LrTensors.sync()``, and
     ``OneCycleLR.step()`` runs after the replay - its ``lr`` fills the device scalar in place and the ``beta1`` it assigns
-    (``cycle_momentum``) reaches a device double the captured Adam / AdamW step reads (another optimizer class under a
-    momentum-cycling one-cycle schedule keeps the eager step).  The ``lr`` meter of such an epoch costs no read-back per step:
+    (``cycle_momentum``) reaches a device double the captured Adam / AdamW step reads - on a ``torch.optim.SGD`` it is ``group["momentum"]``
+    that cycles, and the captured ``bpx_sgd_step`` reads that (another optimizer class under a momentum-cycling one-cycle schedule keeps
+    the eager step).  The ``lr`` meter of such an epoch costs no read-back per step:
     the warm-up schedules' host value is taken right after ``adjust_learning_rate``, a one-cycle ``lr`` is accumulated on the
     device and read once at the end.  With a process group of more than one rank these configurations keep the eager step.
 Contrastive memory banks stay on the reference's loop (``NotImplementedError`` here, as the model classes raise for ``contrast``).
@@ -250,14 +251,18 @@ def train_one_epoch(
             return to_pytorch_format(targets, device)
 
     per_step_sched = sched_name == "onecycle" and any(isinstance(s, OneCycleLR) for s in schedulers if s is not None)
-    capturable = all(g.get("capturable", False) for o in optimizers for g in o.param_groups)
+    from .optim import supports, supports_sgd
+    # an SGD the package's own step reproduces needs no capturable key: bpx_sgd_step reads lr, momentum and clip coefficient from the device
+    capturable = all(supports_sgd(o) or all(g.get("capturable", False) for g in o.param_groups) for o in optimizers)
     single = len(optimizers) == 1 and len(loss_names) == 1
     in_epoch = clip > 0 or per_step_sched or per_iter_warmup          # clipping / an lr that moves inside the epoch: replayed in ONE process only
-    # OneCycleLR's cycle_momentum assigns a new beta1 every step: only the package's Adam / AdamW step reads it from the device
+    # OneCycleLR's cycle_momentum assigns a new beta1 (an SGD: momentum) every step: only the package's Adam / AdamW / SGD steps read it from the device
     moving_beta1 = per_step_sched and any(isinstance(s, OneCycleLR) and s.cycle_momentum for s in schedulers)
     if moving_beta1 and single:
-        from .optim import supports
-        betas_ok = supports(optimizers[0]) and all(getattr(s, "use_beta1", True) for s in schedulers if isinstance(s, OneCycleLR))
+        if supports_sgd(optimizers[0]):
+            betas_ok = all(not torch.is_tensor(g["momentum"]) and g["momentum"] > 0 for g in optimizers[0].param_groups)
+        else:
+            betas_ok = supports(optimizers[0]) and all(getattr(s, "use_beta1", True) for s in schedulers if isinstance(s, OneCycleLR))
     else:
         betas_ok = True
     can_graph = (device.type == "cuda" and capturable and single and not (in_epoch and _world() > 1) and betas_ok
@@ -265,7 +270,9 @@ def train_one_epoch(
     if graph == "on" and not can_graph:
         raise ValueError("graph='on' needs a CUDA/HIP device, a biapy_amd model with training-time-linear heads (or a loss fusing them), ONE capturable "
                          "optimizer and loss; with more than one rank also no gradient clipping and no per-step or per-iteration schedule; under a "
-                         "one-cycle schedule that cycles the momentum an Adam / AdamW without amsgrad, maximize or step hooks")
+                         "one-cycle schedule that cycles the momentum an Adam / AdamW without amsgrad, maximize or step hooks, or an SGD with "
+                         "momentum > 0 in every group; an SGD (exactly torch.optim.SGD, no maximize, differentiable, step hooks or tensor "
+                         "hyper-parameters) counts as capturable")
     use_graph = can_graph and graph in ("on", "auto")
 
     model.train(True)
@@ -312,12 +319,18 @@ def train_one_epoch(
         if use_graph:
             x = to_pytorch_format(batch, device)
             if gstep is None:
-                gstep, gshape = _graph_step(inner, model, loss_function, optimizers[0], x, targets, clip)
+                try:
+                    gstep, gshape = _graph_step(inner, model, loss_function, optimizers[0], x, targets, clip)
+                except ValueError:                                     # the package's SGD step declined the optimizer's tensors after the warm-up
+                    if graph == "on" or not supports_sgd(optimizers[0]):
+                        raise
+                    gstep, gshape = None, None
                 if gstep is None:                                      # the loss function is not a plain tensor loss: eager epoch
                     use_graph = False
-                elif moving_beta1 and not getattr(gstep, "device_betas", False):
+                elif moving_beta1 and not (getattr(gstep, "device_betas", False) or getattr(gstep, "device_momentum", False)):
                     # optim.fused_step declined the tensors at capture (a parameter without a gradient, non-contiguous or non-fp32 state):
                     # torch's own step was captured with beta1 as a constant, which a momentum-cycling one-cycle schedule would outrun
+                    # (an SGD never gets here: its captured step is bpx_sgd_step, which reads the momentum from the device, or nothing is captured)
                     if graph == "on":
                         raise ValueError("graph='on': the captured optimizer step cannot follow the beta1 that the one-cycle schedule cycles "
                                          "(optim.fused_step declined this optimizer's tensors)")
@@ -396,10 +409,14 @@ def _graph_step(inner, model, loss_function, optimizer, x, t, clip=0.0):
     if multi and not isinstance(model, torch.nn.parallel.DistributedDataParallel):
         graphs.broadcast_parameters_from_rank0(inner.parameters())     # a DDP wrap has done this already
     snap = _snapshot(inner, optimizer)                                 # capture warms up with real optimizer steps: undo them
-    if multi:
-        gstep = graphs.DataParallelTrainStep(inner, loss_function, optimizer, x, t, broadcast_parameters=False)
-    else:
-        gstep = graphs.GraphedTrainStep(inner, loss_function, optimizer, x, t, max_grad_norm=clip)
+    try:
+        if multi:
+            gstep = graphs.DataParallelTrainStep(inner, loss_function, optimizer, x, t, broadcast_parameters=False)
+        else:
+            gstep = graphs.GraphedTrainStep(inner, loss_function, optimizer, x, t, max_grad_norm=clip)
+    except ValueError:                                                 # raised before any capture (an SGD the package's step declined): the warm-up ran
+        _restore(inner, optimizer, snap)
+        raise
     _restore(inner, optimizer, snap)
     inner._bpx_graph_step = (key, gstep)
     return gstep, (tuple(x.shape), tuple(t.shape))

@@ -184,6 +184,15 @@ int bpx_grad_norm(int count, const bpx_adam_tensor* tensors, double max_norm, vo
  * product is stored back to `.g`, which is what clip_grad_norm_ leaves in p.grad.  Same arithmetic, order and types otherwise. */
 int bpx_adam_step_dev(int count, const bpx_adam_tensor* tensors, const float* lr_d, double lr, const double* beta1_d, double beta1, double beta2,
                       double eps, double weight_decay, int decoupled, const float* gscale_d, bpx_stream_t stream);
+/* torch.optim.SGD's step (`_multi_tensor_sgd`) in ONE pass over parameter, gradient and momentum buffer (`.m`; `.v` / `.step` are not read), in its
+ * fp32 arithmetic and order, every scalar rounded to float once as a foreach op rounds its alpha:
+ *   d = g + wd * p (weight_decay != 0);  b = b * mom, b = b + (1 - dampening) * d;  u = nesterov ? d + mom * b : b;  p = p + (-lr) * u.
+ * Without momentum (momentum_d NULL and momentum 0) `.m` may be NULL, no buffer is touched and u = d.  lr_d (float), momentum_d (DOUBLE, rounded
+ * to float by the kernel) and gscale_d (float: g = g * gscale first, one fp32 product, stored back to `.g`) are device scalars that override their
+ * host arguments when not NULL; a NULL gscale_d leaves `.g` unwritten.  The first step of a fresh torch optimizer (buffer = gradient) is the
+ * caller's: with dampening 0 a zeroed buffer gives the same.  No atomics: two runs agree bit for bit. */
+int bpx_sgd_step(int count, const bpx_adam_tensor* tensors, const float* lr_d, double lr, const double* momentum_d, double momentum,
+                 double dampening, double weight_decay, int nesterov, const float* gscale_d, bpx_stream_t stream);
 
 /* Conv3d k=3 "same" + bias (biapy/models/blocks.py:154-157), implicit GEMM on MFMA with an
  * LDS-staged input halo.  Fusions:
