@@ -57,6 +57,10 @@ _SIGS = {
     "bpx_grad_norm": ([_i, _vp, C.c_double, _vp, _i64, _vp, _vp], _i),
     "bpx_adam_step_dev": ([_i, _vp, _vp, C.c_double, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _i, _vp, _vp], _i),
     "bpx_sgd_step": ([_i, _vp, _vp, C.c_double, _vp, C.c_double, C.c_double, C.c_double, _i, _vp, _vp], _i),
+    "bpx_aug_draw": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "bpx_aug_mean_blocks": ([_i64], _i),
+    "bpx_aug_mean": ([_vp, _i, _i64, _vp, _vp, _vp], _i),
+    "bpx_aug_apply": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_uint64, _f, _i, _vp, _vp, _vp], _i),
     "bpx_scan_blocks": ([_i64], _i),
     "bpx_select_workspace": ([], _i64),
     "bpx_select_kth_f32": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),
@@ -213,6 +217,13 @@ class BnEvalJob(C.Structure):
     """bpx_bn_eval_job (include/biapy_amd.h)."""
     _fields_ = [("gamma_d", C.c_void_p), ("beta_d", C.c_void_p), ("running_mean_d", C.c_void_p), ("running_var_d", C.c_void_p), ("out_d", C.c_void_p),
                 ("C", C.c_int32), ("eps", C.c_float)]
+
+
+class AugCfg(C.Structure):
+    """bpx_aug_cfg (include/biapy_amd.h)."""
+    _fields_ = [("seed", C.c_uint64), ("thr", C.c_uint64), ("enable", C.c_uint32), ("box_lo", C.c_int32), ("box_hi", C.c_int32),
+                ("c_lo", C.c_float), ("c_hi", C.c_float), ("b_lo", C.c_float), ("b_hi", C.c_float), ("s_lo", C.c_float), ("s_hi", C.c_float),
+                ("f_lo", C.c_float), ("f_hi", C.c_float)]
 
 
 class AdamTensor(C.Structure):

@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "bpx_common.h"
+#include "philox.h"
 
 namespace {
 
@@ -641,17 +642,7 @@ __global__ void __launch_bounds__(256) norm_act_bwd_kernel(const T* __restrict__
 // value the caller bumps once per forward (a captured graph then draws a new mask at every replay).  mask_io (tests): mode 1 = read the
 // keep flags from it instead of drawing them, mode 2 = also write the drawn flags to it.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// philox4x32_10: philox.h (shared with augment.hip)
 struct DropArgs { float p; uint32_t thr; uint64_t seed; const uint64_t* counter; uint32_t site; uint8_t* mask; int mask_mode; };
 // keep flags of the KPL consecutive elements starting at linear element index e0 (a multiple of 4)
 template <int KPL>

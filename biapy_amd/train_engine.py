@@ -37,6 +37,10 @@ What is different, because the step is ~10 ms on an MI355X and a host round trip
     the eager step).  The ``lr`` meter of such an epoch costs no read-back per step:
     the warm-up schedules' host value is taken right after ``adjust_learning_rate``, a one-cycle ``lr`` is accumulated on the
     device and read once at the end.  With a process group of more than one rank these configurations keep the eager step.
+  * ``augment=`` (``augment.DeviceAugmenter``, default ``None`` = nothing changes): the batch, moved to ``device``, and the targets
+    ``prepare_targets`` returned are augmented together on the device right after the ``DATA.PATCH_SIZE`` check; the replayed step, the eager
+    step and the ragged last batch train on the augmented pair and ``metric_function`` sees the augmented targets.  The augmenter's launches
+    run eagerly ahead of the replay (the captured step is untouched); ``evaluate`` takes no augmenter.
 Contrastive memory banks stay on the reference's loop (``NotImplementedError`` here, as the model classes raise for ``contrast``).
 """
 from __future__ import annotations
@@ -229,6 +233,7 @@ def train_one_epoch(
     *,
     graph: str = "auto",
     sync_every: int = 10,
+    augment=None,
 ) -> Tuple[Dict[str, float], int]:
     if memory_bank is not None:
         raise NotImplementedError("contrastive training (memory_bank) stays on the reference's train_one_epoch")
@@ -315,6 +320,8 @@ def train_one_epoch(
                 "Trying to input data with different shape than 'DATA.PATCH_SIZE'. Check your configuration."
                 f" Input: {batch.shape[1:-1]} vs PATCH_SIZE: {patch_size[:-1]}"
             )
+        if augment is not None:                                        # device augmentation: eager launches ahead of the (replayed or eager) step
+            batch, targets = augment(batch.to(device, non_blocking=True).to(torch.float32), targets)
         outputs = None
         if use_graph:
             x = to_pytorch_format(batch, device)

@@ -650,6 +650,65 @@ int bpx_tta_orient(const float* in_d, int Z, int Y, int X, int C, const int* per
 int bpx_tta_accumulate(const float* pred_d, int Z, int Y, int X, int C, const int* perm, const int* sign, int mode, int first,
                        int count_if_last, float* acc_d, bpx_stream_t stream);
 
+/* ---- training-time augmentation on the device (biapy_amd/augment.py states the semantics; csrc/augment.hip) -------------------
+ * Flips, rot90 over (Y, X), contrast, brightness, Gaussian noise and cutout of a float32 (B,Z,Y,X,C) image batch, 1 <= C <= 16, and its
+ * (B,Z,Y,X,Ct) float32 / uint8 target, 1 <= Ct <= 8, in one gather pass.  The draws of a call live in one RECORD of 32 four-byte words
+ * per sample:
+ *   word 0       flags: bit 0 zflip, 1 vflip (Y), 2 hflip (X); bits 3-4 k of rot90; bit 5 contrast, 6 brightness, 7 noise fired;
+ *                bits 8-10 number of cutout boxes (0..4)
+ *   word 1       a, the contrast factor (float)          word 2   b, the brightness offset (float)
+ *   word 3       s, the noise standard deviation (float)  word 4   m, the sample mean (float; written by bpx_aug_mean)
+ *   words 5-6    the counter value the call drew with, low and high          word 7   reserved, 0
+ *   words 8-31   four boxes z0, y0, x0, dz, dy, dx (int32) in OUTPUT coordinates */
+#define BPX_AUG_REC_WORDS 32
+#define BPX_AUG_MAX_BOXES 4
+#define BPX_AUG_F_ZFLIP 0x1u
+#define BPX_AUG_F_VFLIP 0x2u
+#define BPX_AUG_F_HFLIP 0x4u
+#define BPX_AUG_K_SHIFT 3
+#define BPX_AUG_F_CONTRAST 0x20u
+#define BPX_AUG_F_BRIGHTNESS 0x40u
+#define BPX_AUG_F_NOISE 0x80u
+#define BPX_AUG_NBOX_SHIFT 8
+#define BPX_AUG_W_FLAGS 0
+#define BPX_AUG_W_A 1
+#define BPX_AUG_W_B 2
+#define BPX_AUG_W_S 3
+#define BPX_AUG_W_M 4
+#define BPX_AUG_W_CTR 5
+#define BPX_AUG_W_BOX 8
+/* which transforms a bpx_aug_draw may fire (bpx_aug_cfg.enable) */
+#define BPX_AUG_EN_ROT90 0x1u
+#define BPX_AUG_EN_ZFLIP 0x2u
+#define BPX_AUG_EN_VFLIP 0x4u
+#define BPX_AUG_EN_HFLIP 0x8u
+#define BPX_AUG_EN_CONTRAST 0x10u
+#define BPX_AUG_EN_BRIGHTNESS 0x20u
+#define BPX_AUG_EN_NOISE 0x40u
+#define BPX_AUG_EN_CUTOUT 0x80u
+typedef struct {
+  uint64_t seed;          /* Philox key */
+  uint64_t thr;           /* floor(da_prob * 2^32): a transform fires when its 32-bit word is below it (compared in 64 bits) */
+  uint32_t enable;        /* BPX_AUG_EN_* */
+  int32_t box_lo, box_hi; /* number of cutout boxes, 1 <= box_lo <= box_hi <= 4 */
+  float c_lo, c_hi;       /* contrast: a = 1 + uniform */
+  float b_lo, b_hi;       /* brightness offset */
+  float s_lo, s_hi;       /* noise standard deviation */
+  float f_lo, f_hi;       /* cutout extent as a fraction of each axis, in (0, 1] */
+} bpx_aug_cfg;
+/*   bpx_aug_draw  : fills records_d[B][32] (word 4 = 0) from Philox4x32-10(key = seed, counter = (sample, stream, state_d[0] low, high)) and then
+ *                   adds 1 to state_d[0], the augmenter's counter; state_d[1] is a ticket the blocks of the launch count themselves on (0 between
+ *                   launches).  One launch, nothing is read back: capturable, a replay draws anew.
+ *   bpx_aug_mean  : records_d[b][4] = float(fp64 sum of sample b / n), n = elements per sample; ws_d: B * bpx_aug_mean_blocks(n) doubles; fixed
+ *                   summation order (two launches, no atomics)
+ *   bpx_aug_apply : out = the augmented pair as augment.py defines it; t_dtype BPX_F32 or BPX_U8; out-of-place only.  Y != X: rot90 records with an
+ *                   odd k are applied with that bit cleared.  cval / mask_too: the cutout value of the image / whether boxes also zero the target. */
+int bpx_aug_draw(const bpx_aug_cfg* cfg, int B, int Z, int Y, int X, uint64_t* state_d, uint32_t* records_d, bpx_stream_t stream);
+int bpx_aug_mean_blocks(int64_t n);
+int bpx_aug_mean(const float* x_d, int B, int64_t n, double* ws_d, uint32_t* records_d, bpx_stream_t stream);
+int bpx_aug_apply(const float* x_d, const void* t_d, int t_dtype, int B, int Z, int Y, int X, int C, int Ct, const uint32_t* records_d, uint64_t seed,
+                  float cval, int mask_too, float* x_out_d, void* t_out_d, bpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
