@@ -2161,72 +2161,6 @@ extern "C" int bpx_batchnorm_eval_records(int count, const bpx_bn_eval_job* jobs
 
 
 // ------------------------------------------------------------------------------------------------
-// Adam / AdamW step over a list of parameter tensors (torch.optim.Adam(W), capturable: `step` is a device float per tensor).
-// The math and its order are those of torch's fused kernel (torch/optim/adam.py `_fused_adam` -> fused_adam_utils.cuh):
-//   AdamW: p -= lr * wd * p          Adam: g += wd * p
-//   m = m + (g - m) * (1 - b1)       v = b2 * v + (1 - b2) * g * g
-//   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps),   t = step + 1
-// Why not torch's own launch: its multi-tensor kernel hands one 64 K-element chunk to a 512-thread block - the 6.7 M parameters of cfg 2
-// are ~200 blocks on 256 CUs, three launches of 45 us (188 MB of traffic at 1.4 TB/s).  Here a block takes 4096 elements.
-// `step` is read by every block of a tensor, so it is incremented by a second (one-block) launch after the update.
-// ------------------------------------------------------------------------------------------------
-constexpr int ADAM_CHUNK = 4096, ADAM_MAX = 64;
-struct AdamBatch { bpx_adam_tensor t[ADAM_MAX]; int first_chunk[ADAM_MAX + 1]; int count; };
-struct AdamSteps { float* step[256]; int count; };
-
-__global__ void __launch_bounds__(256) adam_multi_kernel(const AdamBatch b, const float* __restrict__ lr_d, double lr_h, double beta1, double beta2,
-                                                         double eps, double wd, int decoupled) {
-  int lo = 0, hi = b.count;                          // block-uniform search: tensor k owns chunks [first_chunk[k], first_chunk[k + 1])
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((int)blockIdx.x >= b.first_chunk[mid]) lo = mid; else hi = mid;
-  }
-  const bpx_adam_tensor t = b.t[lo];
-  const int64_t off = (int64_t)((int)blockIdx.x - b.first_chunk[lo]) * ADAM_CHUNK;
-  const int n = (int)(t.numel - off < ADAM_CHUNK ? t.numel - off : ADAM_CHUNK);
-  // The types below are those of torch's fused kernel (ATen/native/cuda/fused_adam_utils.cuh): hyper-parameters are DOUBLES (0.999 is not 0.999f:
-  // 1 - beta2 differs by 1.3e-5 relative), a double times a float is evaluated in double and rounded to float at the assignment; the bias
-  // corrections are computed in double and handed on as floats.
-  const double lr = lr_d ? (double)*lr_d : lr_h;
-  const double step = (double)*t.step + 1.0;
-  const float bc1 = (float)(1.0 - pow(beta1, step)), bc2s = (float)sqrt(1.0 - pow(beta2, step));
-  const float step_size = (float)(lr / (double)bc1);
-  const double omb1 = 1.0 - beta1, omb2 = 1.0 - beta2;
-  float* __restrict__ p = t.p + off;
-  const float* __restrict__ g = t.g + off;
-  float* __restrict__ m = t.m + off;
-  float* __restrict__ v = t.v + off;
-  auto upd = [&](float& pf, float gf, float& mf, float& vf) {
-    if (wd != 0.0) { if (decoupled) pf = (float)((double)pf - lr * wd * (double)pf); else gf = (float)((double)gf + (double)pf * wd); }
-    mf = (float)(beta1 * (double)mf + omb1 * (double)gf);
-    vf = (float)(beta2 * (double)vf + omb2 * (double)gf * (double)gf);
-    const float denom = (float)((double)(sqrtf(vf) / bc2s) + eps);
-    pf -= step_size * mf / denom;
-  };
-  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
-  if (vec) {
-    const int n4 = n >> 2;
-    for (int i = threadIdx.x; i < n4; i += 256) {
-      const f32x4_t pv = reinterpret_cast<f32x4_t*>(p)[i], mv = reinterpret_cast<f32x4_t*>(m)[i], vv = reinterpret_cast<f32x4_t*>(v)[i];
-      const f32x4_t gv = reinterpret_cast<const f32x4_t*>(g)[i];
-      float pe[4], me[4], ve[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { pe[e] = pv[e]; me[e] = mv[e]; ve[e] = vv[e]; upd(pe[e], gv[e], me[e], ve[e]); }
-      reinterpret_cast<f32x4_t*>(p)[i] = f32x4_t{pe[0], pe[1], pe[2], pe[3]};
-      reinterpret_cast<f32x4_t*>(m)[i] = f32x4_t{me[0], me[1], me[2], me[3]};
-      reinterpret_cast<f32x4_t*>(v)[i] = f32x4_t{ve[0], ve[1], ve[2], ve[3]};
-    }
-    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) upd(p[i], g[i], m[i], v[i]);
-  } else {
-    for (int i = threadIdx.x; i < n; i += 256) upd(p[i], g[i], m[i], v[i]);
-  }
-}
-
-__global__ void __launch_bounds__(256) adam_step_inc_kernel(const AdamSteps s) {
-  if ((int)threadIdx.x < s.count) *s.step[threadIdx.x] += 1.f;
-}
-
-// ------------------------------------------------------------------------------------------------
 // Binary segmentation loss on the 1-channel head (metrics.py:493-586 CrossEntropyLoss_wrapper -> BCEWithLogits,
 // :726-762 DiceLoss with batch_dice, :764-973 DiceCELoss) and the IoU@0.5 counts (:138-232), one streaming pass each way.
 //   sums[b] = { sum bce, sum p*t, sum p, sum t, |P&T|, |P|T| }  per block b, p = sigmoid(z), P = p > 0.5, T = t > 0.5
@@ -3534,38 +3468,6 @@ extern "C" int bpx_upsample_c1_bwd(int dtype, int N, int D, int H, int W, int fz
   if (dtype == BPX_BF16) upsample_c1_bwd_kernel<uint16_t><<<grid, 256, 0, (hipStream_t)stream>>>(img_d, (const uint16_t*)dx16_d, D, H, W, fz, fy, fx, total_in, partials_d);
   else if (dtype == BPX_F32) upsample_c1_bwd_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(img_d, (const float*)dx16_d, D, H, W, fz, fy, fx, total_in, partials_d);
   else BPX_FAIL("%s: dtype must be BF16 or F32", fn);
-  BPX_LAUNCH_CHECK(fn);
-  return 0;
-}
-
-extern "C" int bpx_adam_step(int count, const bpx_adam_tensor* tensors, const float* lr_d, double lr, double beta1, double beta2, double eps,
-                             double weight_decay, int decoupled, bpx_stream_t stream) {
-  const char* fn = "bpx_adam_step";
-  BPX_CHECK(count >= 0 && (count == 0 || tensors != nullptr), "%s: bad tensor list", fn);
-  hipStream_t s = (hipStream_t)stream;
-  for (int k = 0; k < count; ++k)
-    BPX_CHECK(tensors[k].p && tensors[k].g && tensors[k].m && tensors[k].v && tensors[k].step && tensors[k].numel >= 0 &&
-              tensors[k].numel < ((int64_t)1 << 40), "%s: tensor %d has a null pointer or a bad size", fn, k);
-  for (int base = 0; base < count; base += ADAM_MAX) {
-    AdamBatch b{};
-    b.count = std::min(ADAM_MAX, count - base);
-    int64_t chunks = 0;
-    for (int k = 0; k < b.count; ++k) {
-      b.t[k] = tensors[base + k];
-      b.first_chunk[k] = (int)chunks;
-      chunks += cdiv64(b.t[k].numel, ADAM_CHUNK);
-      BPX_CHECK(chunks < (1ll << 30), "%s: too many elements in one launch", fn);
-    }
-    b.first_chunk[b.count] = (int)chunks;
-    if (chunks > 0)
-      adam_multi_kernel<<<(unsigned)chunks, 256, 0, s>>>(b, lr_d, lr, beta1, beta2, eps, weight_decay, decoupled);
-  }
-  for (int base = 0; base < count; base += 256) {   // after every update launch: the updates read the old step
-    AdamSteps st{};
-    st.count = std::min(256, count - base);
-    for (int k = 0; k < st.count; ++k) st.step[k] = tensors[base + k].step;
-    adam_step_inc_kernel<<<1, 256, 0, s>>>(st);
-  }
   BPX_LAUNCH_CHECK(fn);
   return 0;
 }

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 from typing import Callable, Optional
 
+import contextlib
 import gc
 
 import torch
@@ -31,6 +32,30 @@ _STALE_GRAPH = (
 )
 
 
+class _DeviceDoubles:
+    """One hyper-parameter that a scheduler assigns as a host double (``get(group)``), mirrored in a 0-d float64 device tensor per param group
+    (``tensors``; None for a group that ``has(group)`` rules out).  float64 because torch keeps it as a host double: a Python float is one, so the
+    device copy is exact.  ``sync()`` fills a copy whose host value differs from the one last seen (``moved`` then says so) and launches nothing
+    otherwise."""
+
+    def __init__(self, optimizer: torch.optim.Optimizer, device, get, has):
+        self.opt, self.get, self.moved = optimizer, get, False
+        self.seen = [float(get(g)) if has(g) else None for g in optimizer.param_groups]
+        self.tensors = [None if v is None else torch.tensor(v, dtype=torch.float64, device=device) for v in self.seen]
+
+    def sync(self) -> None:
+        for i, g in enumerate(self.opt.param_groups):
+            if self.seen[i] is not None and float(self.get(g)) != self.seen[i]:
+                self.seen[i] = float(self.get(g))
+                self.tensors[i].fill_(self.seen[i])
+                self.moved = True
+
+
+def _has_momentum(g) -> bool:
+    mom = g.get("momentum", None)
+    return mom is not None and not torch.is_tensor(mom) and mom > 0
+
+
 class _LrTensors:
     """A capturable Adam(W) given a Python-float ``lr`` bakes it (and ``1 - lr * weight_decay``) into the captured kernels, so a
     scheduler stepping between epochs would be ignored by the replays.  The learning rates therefore become 0-d device
@@ -39,50 +64,39 @@ class _LrTensors:
     which every replay calls: the value is copied into the captured tensor and the tensor is put back.
     ``weight_decay``, ``eps`` and ``beta2`` stay compile-time constants of the captured step.
 
-    ``beta1`` has a device copy as well - a 0-d float64 tensor per group (``beta1s``; None for a group without betas), float64 because torch keeps
-    the betas as host doubles and OneCycleLR (``cycle_momentum``, its default) assigns a new one every step.  ``group["betas"]`` itself stays a
-    tuple of Python floats, which is what torch's own step and ``optim._group_ok`` expect; ``sync()`` fills the device copy when the first beta
-    differs from the value it last saw (``beta1_moved`` then says so) and launches nothing otherwise.  The package's Adam / AdamW step reads
-    it (``GraphedTrainStep``); torch's own captured step cannot.
+    ``beta1`` has a device copy as well (``beta1s``, a ``_DeviceDoubles``; None for a group without betas): OneCycleLR (``cycle_momentum``, its
+    default) assigns a new one every step.  ``group["betas"]`` itself stays a tuple of Python floats, which is what torch's own step and
+    ``optim._group_ok`` expect; ``beta1_moved`` says whether ``sync()`` has seen it change.  The package's Adam / AdamW step reads the device copy
+    (``GraphedTrainStep``); torch's own captured step cannot.
 
-    ``momenta`` is the same for ``group["momentum"]`` (an SGD: OneCycleLR cycles it in place of beta1): a 0-d float64 tensor per group whose
-    momentum is greater than 0, None otherwise, filled by ``sync()`` when the value differs from the one last seen.  ``bpx_sgd_step`` reads it."""
+    ``momenta`` is the same for ``group["momentum"]`` (an SGD: OneCycleLR cycles it in place of beta1), None for a group whose momentum is not
+    greater than 0.  ``bpx_sgd_step`` reads it."""
 
     def __init__(self, optimizer: torch.optim.Optimizer, device):
         self.opt = optimizer
-        self.lrs, self.beta1s, self._b1, self.momenta, self._mom = [], [], [], [], []
-        self.beta1_moved = False
+        self.lrs = []
         for g in optimizer.param_groups:
             lr = g["lr"]
             if not torch.is_tensor(lr) or lr.device != torch.device(device) or lr.dtype != torch.float32 or lr.numel() != 1:
                 lr = torch.tensor(float(lr), dtype=torch.float32, device=device)      # also a host / fp64 tensor lr: the captured kernels read a device float
                 g["lr"] = lr
             self.lrs.append(lr)
-            b1 = float(g["betas"][0]) if "betas" in g else None
-            self._b1.append(b1)
-            self.beta1s.append(None if b1 is None else torch.tensor(b1, dtype=torch.float64, device=device))
-            mom = g.get("momentum", None)
-            mom = float(mom) if mom is not None and not torch.is_tensor(mom) and mom > 0 else None
-            self._mom.append(mom)
-            self.momenta.append(None if mom is None else torch.tensor(mom, dtype=torch.float64, device=device))
+        self._beta1 = _DeviceDoubles(optimizer, device, lambda g: g["betas"][0], lambda g: "betas" in g)
+        self._momentum = _DeviceDoubles(optimizer, device, lambda g: g["momentum"], _has_momentum)
+        self.beta1s, self.momenta = self._beta1.tensors, self._momentum.tensors
+
+    @property
+    def beta1_moved(self) -> bool:
+        return self._beta1.moved
 
     def sync(self) -> None:
-        for i, (g, t) in enumerate(zip(self.opt.param_groups, self.lrs)):
+        for g, t in zip(self.opt.param_groups, self.lrs):
             cur = g["lr"]
             if cur is not t:
                 t.fill_(float(cur))                    # host scalar -> device tensor, no synchronisation
                 g["lr"] = t
-            if self._b1[i] is not None:
-                b1 = float(g["betas"][0])
-                if b1 != self._b1[i]:
-                    self.beta1s[i].fill_(b1)           # a Python float is a double: the device copy is exact
-                    self._b1[i] = b1
-                    self.beta1_moved = True
-            if self._mom[i] is not None:
-                mom = float(g["momentum"])
-                if mom != self._mom[i]:
-                    self.momenta[i].fill_(mom)
-                    self._mom[i] = mom
+        self._beta1.sync()
+        self._momentum.sync()
 
 
 def _opt_step(optimizer, **kw) -> bool:
@@ -109,6 +123,24 @@ def _capturable(optimizer) -> bool:
             raise ValueError("build the optimizer with capturable=True to capture its step (a torch.optim.SGD without maximize, differentiable, step "
                              "hooks or tensor hyper-parameters needs no such key)")
     return False
+
+
+@contextlib.contextmanager
+def _capture(graph, **kw):
+    """``torch.cuda.graph(graph, capture_error_mode="thread_local", **kw)`` with the garbage collector out of the way.  A dead reference cycle may
+    hold an earlier HIP graph and its memory pool (a step object that went out of scope: its ``eager`` closure refers back to it), and a
+    collection pass that tears it down while a capture is under way - from whichever thread happens to allocate then, the autograd worker
+    included - aborts the process.  This torch collects on entry only under ``torch.compiler.config.force_cudagraph_gc``; so the cycles are
+    collected here, before the capture begins, and the collector stays off until it has ended."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, capture_error_mode="thread_local", **kw):
+            yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 def _bump() -> None:
@@ -195,7 +227,7 @@ class GraphedTrainStep:
         self.device_momentum = sgd                     # the captured SGD step reads group["momentum"] from the device (OneCycleLR cycles it)
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+        with _capture(self.graph):
             self.loss = eager()
         torch.cuda.synchronize()
         _bump()
@@ -353,13 +385,13 @@ class DataParallelTrainStep:
             _warm(eager, warmup, side)
             self._check_sgd_ready()
             g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g1, stream=side, capture_error_mode="thread_local"):
+            with _capture(g1, stream=side):
                 self.loss = fwd_bwd_adopt() if self.adopted else fwd_bwd()
             if self.adopted:
                 self.flat_grad = self._adopted_flat()                    # the slab of the captured run: static across replays
                 if self.flat_grad is None:
                     raise RuntimeError("gradient layout changed between warm-up and capture")
-            with torch.cuda.graph(g2, pool=g1.pool(), stream=side, capture_error_mode="thread_local"):
+            with _capture(g2, pool=g1.pool(), stream=side):
                 update()
             torch.cuda.synchronize()
             self._check_views()
@@ -461,13 +493,15 @@ class DataParallelTrainStep:
             _warm(eager, warmup, side)
             self._check_sgd_ready()
             g1a, g1b, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            # what torch.cuda.graph does on entry and this raw capture_begin does not: collect unreachable cycles NOW, so that no earlier
-            # graph, event or tensor (a previous step object, say) is destroyed by a garbage-collection pass inside the capture
+            # what _capture does and this raw capture_begin does not: collect unreachable cycles NOW and keep the collector off, so that no
+            # earlier graph, event or tensor (a previous step object, say) is destroyed by a garbage-collection pass inside the capture
             gc.collect()
             torch.cuda.synchronize()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 state["capturing"] = (g1a, g1b)
+                gc_was_on = gc.isenabled()
+                gc.disable()
                 try:
                     g1a.capture_begin(capture_error_mode="thread_local")
                     state["open"] = g1a
@@ -488,8 +522,10 @@ class DataParallelTrainStep:
                     raise
                 finally:
                     state["capturing"] = None
+                    if gc_was_on:
+                        gc.enable()
             torch.cuda.current_stream().wait_stream(side)
-            with torch.cuda.graph(g2, pool=g1a.pool(), stream=side, capture_error_mode="thread_local"):
+            with _capture(g2, pool=g1a.pool(), stream=side):
                 update()
         torch.cuda.synchronize()
         self._check_views()
@@ -588,7 +624,7 @@ class GraphedInference:
         with torch.no_grad():
             _warm(lambda: fn(self.x), warmup)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+            with _capture(self.graph):
                 self.y = fn(self.x)
         torch.cuda.synchronize()
 

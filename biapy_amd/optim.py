@@ -34,15 +34,67 @@ lib = L.lib
 _ENABLED = os.environ.get("BPX_FUSED_ADAM", "1") != "0"
 
 
-def _group_ok(opt, g) -> bool:
-    if g.get("amsgrad", False) or g.get("maximize", False) or g.get("differentiable", False):
+def _tensors_ok(p, ts) -> bool:
+    """What every kernel of csrc/optim.hip walks: fp32, contiguous, dense CUDA tensors of the parameter's size."""
+    return not any((not t.is_cuda) or t.dtype != torch.float32 or not t.is_contiguous() or t.is_sparse or t.numel() != p.numel() for t in ts)
+
+
+def _lr_ok(lr) -> bool:
+    """A Python number, a host tensor (read here) or ONE device float (read by the kernel)."""
+    return not (torch.is_tensor(lr) and lr.is_cuda and (lr.dtype != torch.float32 or lr.numel() != 1))
+
+
+def _lr_split(lr):
+    """``(lr_d, lr_h)`` of the entry points: the device float's address, or None and the host value."""
+    return (lr.data_ptr(), 0.0) if torch.is_tensor(lr) and lr.is_cuda else (None, float(lr))
+
+
+def _is_device_double(t) -> bool:
+    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.numel() == 1
+
+
+def _clip_ok(groups, max_norm, norm_out) -> bool:
+    """``max_norm`` needs a parameter to clip and, where given, a ``norm_out`` of two contiguous device floats."""
+    if max_norm is None:
+        return True
+    if not any(g["params"] for g in groups):
         return False
+    return norm_out is None or (norm_out.is_cuda and norm_out.dtype == torch.float32 and norm_out.numel() == 2 and norm_out.is_contiguous())
+
+
+def _tensor_list(optimizer, ps, **state_keys):
+    """The ``bpx_adam_tensor`` list of ``ps``: p, g and numel, and each field named in ``state_keys`` from that entry of the optimizer's state."""
+    arr = (L.AdamTensor * len(ps))()
+    for i, p in enumerate(ps):
+        arr[i].p, arr[i].g, arr[i].numel = p.data_ptr(), p.grad.data_ptr(), p.numel()
+        for field, key in state_keys.items():
+            setattr(arr[i], field, optimizer.state[p][key].data_ptr())
+    return arr
+
+
+def _clip_coefficient(optimizer, max_norm, norm_out, st) -> Optional[int]:
+    """``clip_grad_norm_`` over ALL groups up to the scaling itself: ``bpx_grad_norm`` leaves ``[total_norm, coefficient]`` on the device and every
+    group's update launch multiplies its gradients by that coefficient.  Returns the coefficient's device address; None without ``max_norm``."""
+    if max_norm is None:
+        return None
+    every = [p for g in optimizer.param_groups for p in g["params"]]
+    arr = _tensor_list(optimizer, every)
+    nbytes = lib.bpx_grad_norm_workspace(len(every), arr)
+    if nbytes < 0:
+        raise L.BpxError("bpx_grad_norm_workspace: bad tensor list")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=every[0].device)
+    if norm_out is None:
+        norm_out = torch.empty(2, dtype=torch.float32, device=every[0].device)
+    L.check(lib.bpx_grad_norm(len(every), arr, float(max_norm), ws.data_ptr(), nbytes, norm_out.data_ptr(), st))
+    return norm_out.data_ptr() + 4
+
+
+def _group_ok(opt, g) -> bool:
     if not g.get("capturable", False):       # host-side step counters: torch's own path
         return False
     if any(torch.is_tensor(v) for v in (*g["betas"], g["eps"], g["weight_decay"])):
         return False
-    lr = g["lr"]
-    if torch.is_tensor(lr) and lr.is_cuda and (lr.dtype != torch.float32 or lr.numel() != 1):
+    if not _lr_ok(g["lr"]):
         return False
     for p in g["params"]:
         if p.grad is None:
@@ -50,12 +102,9 @@ def _group_ok(opt, g) -> bool:
         st = opt.state.get(p)
         if not st or "exp_avg" not in st or "exp_avg_sq" not in st or not torch.is_tensor(st.get("step")):
             return False
-        ts = (p, p.grad, st["exp_avg"], st["exp_avg_sq"])
-        if any((not t.is_cuda) or t.dtype != torch.float32 or not t.is_contiguous() or t.is_sparse for t in ts):
+        if not _tensors_ok(p, (p, p.grad, st["exp_avg"], st["exp_avg_sq"])):
             return False
         if st["step"].dtype != torch.float32 or not st["step"].is_cuda or st["step"].numel() != 1:
-            return False
-        if any(t.numel() != p.numel() for t in ts):
             return False
     return True
 
@@ -88,8 +137,7 @@ def supports_sgd(optimizer) -> bool:
 
 
 def _sgd_group_ok(opt, g) -> bool:
-    lr = g["lr"]
-    if torch.is_tensor(lr) and lr.is_cuda and (lr.dtype != torch.float32 or lr.numel() != 1):
+    if not _lr_ok(g["lr"]):
         return False
     if g["nesterov"] and (g["momentum"] <= 0 or g["dampening"] != 0):       # torch's constructor refuses it; a later assignment could still make it
         return False
@@ -102,7 +150,7 @@ def _sgd_group_ok(opt, g) -> bool:
             if buf is None:                      # the first step of a fresh optimizer: torch seeds the buffer with the gradient
                 return False
             ts.append(buf)
-        if any((not t.is_cuda) or t.dtype != torch.float32 or t.is_sparse or not t.is_contiguous() or t.numel() != p.numel() for t in ts):
+        if not _tensors_ok(p, ts):
             return False
     return True
 
@@ -112,73 +160,30 @@ def sgd_ready(optimizer) -> bool:
     return supports_sgd(optimizer) and all(_sgd_group_ok(optimizer, g) for g in optimizer.param_groups)
 
 
-def _sgd_tensor_list(optimizer, ps, with_buf):
-    arr = (L.AdamTensor * len(ps))()
-    for i, p in enumerate(ps):
-        arr[i].p, arr[i].g, arr[i].numel = p.data_ptr(), p.grad.data_ptr(), p.numel()
-        if with_buf:
-            arr[i].m = optimizer.state[p]["momentum_buffer"].data_ptr()
-    return arr
-
-
 @torch.no_grad()
 def fused_sgd_step(optimizer: torch.optim.Optimizer, *, max_norm: Optional[float] = None, momentum_d: Optional[Sequence[Optional[torch.Tensor]]] = None,
                    norm_out: Optional[torch.Tensor] = None) -> bool:
     """One ``torch.optim.SGD`` step through ``bpx_sgd_step``; False (nothing done) when the optimizer or its tensors are not what the kernel
     reproduces.  ``max_norm`` / ``norm_out`` as in ``fused_step``.  ``momentum_d``: per param group a 0-d float64 device tensor the kernel reads in
     place of ``group["momentum"]``, or None for a group without momentum."""
-    if not supports_sgd(optimizer):
-        return False
     groups = optimizer.param_groups
-    if not all(_sgd_group_ok(optimizer, g) for g in groups):     # every refusal is decided BEFORE the first launch: no partial step
+    if not sgd_ready(optimizer) or not _clip_ok(groups, max_norm, norm_out):     # every refusal is decided BEFORE the first launch: no partial step
         return False
-    clip = max_norm is not None
-    if momentum_d is not None:
-        momentum_d = list(momentum_d)
-        if len(momentum_d) != len(groups):
-            return False
-        for g, m in zip(groups, momentum_d):
-            if m is None:
-                continue
-            if g["momentum"] == 0 or not (torch.is_tensor(m) and m.is_cuda and m.dtype == torch.float64 and m.numel() == 1):
-                return False
-    if clip and norm_out is not None and not (norm_out.is_cuda and norm_out.dtype == torch.float32 and norm_out.numel() == 2 and norm_out.is_contiguous()):
+    momentum_d = [None] * len(groups) if momentum_d is None else list(momentum_d)
+    if len(momentum_d) != len(groups) or any(m is not None and (g["momentum"] == 0 or not _is_device_double(m)) for g, m in zip(groups, momentum_d)):
         return False
     st = L.stream_ptr()
-    if clip:
-        every = [p for g in groups for p in g["params"]]
-        if not every:
-            return False
-        arr = _sgd_tensor_list(optimizer, every, False)
-        nbytes = lib.bpx_grad_norm_workspace(len(every), arr)
-        if nbytes < 0:
-            raise L.BpxError("bpx_grad_norm_workspace: bad tensor list")
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=every[0].device)
-        if norm_out is None:
-            norm_out = torch.empty(2, dtype=torch.float32, device=every[0].device)
-        L.check(lib.bpx_grad_norm(len(every), arr, float(max_norm), ws.data_ptr(), nbytes, norm_out.data_ptr(), st))
-    for k, g in enumerate(groups):
+    coef = _clip_coefficient(optimizer, max_norm, norm_out, st)
+    for g, m in zip(groups, momentum_d):
         ps = list(g["params"])
         if not ps:
             continue
         mom = float(g["momentum"])
-        arr = _sgd_tensor_list(optimizer, ps, mom != 0)
-        lr = g["lr"]
-        lr_d, lr_h = (lr.data_ptr(), 0.0) if torch.is_tensor(lr) and lr.is_cuda else (None, float(lr))
-        mom_d = momentum_d[k].data_ptr() if momentum_d is not None and momentum_d[k] is not None else None
-        L.check(lib.bpx_sgd_step(len(ps), arr, lr_d, lr_h, mom_d, mom, float(g["dampening"]), float(g["weight_decay"]), 1 if g["nesterov"] else 0,
-                                 norm_out.data_ptr() + 4 if clip else None, st))
-    optimizer._opt_called = True
+        arr = _tensor_list(optimizer, ps, **(dict(m="momentum_buffer") if mom != 0 else {}))
+        L.check(lib.bpx_sgd_step(len(ps), arr, *_lr_split(g["lr"]), None if m is None else m.data_ptr(), mom, float(g["dampening"]),
+                                 float(g["weight_decay"]), 1 if g["nesterov"] else 0, coef, st))
+    optimizer._opt_called = True             # what lr_scheduler's wrapper of optimizer.step() records (its "scheduler before optimizer" warning reads it)
     return True
-
-
-def _tensor_list(optimizer, ps):
-    arr = (L.AdamTensor * len(ps))()
-    for i, p in enumerate(ps):
-        s = optimizer.state[p]
-        arr[i].p, arr[i].g, arr[i].m, arr[i].v = p.data_ptr(), p.grad.data_ptr(), s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr()
-        arr[i].step, arr[i].numel = s["step"].data_ptr(), p.numel()
-    return arr
 
 
 @torch.no_grad()
@@ -189,47 +194,28 @@ def fused_step(optimizer: torch.optim.Optimizer, *, max_norm: Optional[float] = 
     ``max_norm``: ``clip_grad_norm_(all parameters, max_norm)`` first (one norm over all groups, every group's launch reads the same
     coefficient); ``norm_out`` (2 device floats, optional) receives ``[total_norm, coefficient]``.  ``beta1_d``: one 0-d float64 device tensor
     per param group, read by the kernel in place of ``group["betas"][0]``."""
-    if not _ENABLED or type(optimizer) not in (torch.optim.Adam, torch.optim.AdamW):
-        return False
-    if _has_step_hooks(optimizer):            # hooks hang on optimizer.step(): torch's own path runs them
-        return False
     groups = optimizer.param_groups
-    if not all(_group_ok(optimizer, g) for g in groups):     # every refusal is decided BEFORE the first launch: no partial step
-        return False
-    clip = max_norm is not None
+    if not supports(optimizer) or not all(_group_ok(optimizer, g) for g in groups) or not _clip_ok(groups, max_norm, norm_out):
+        return False                         # every refusal is decided BEFORE the first launch: no partial step
     if beta1_d is not None:
         beta1_d = list(beta1_d)
-        if len(beta1_d) != len(groups) or any(not (torch.is_tensor(b) and b.is_cuda and b.dtype == torch.float64 and b.numel() == 1) for b in beta1_d):
+        if len(beta1_d) != len(groups) or not all(_is_device_double(b) for b in beta1_d):
             return False
-    if clip and norm_out is not None and not (norm_out.is_cuda and norm_out.dtype == torch.float32 and norm_out.numel() == 2 and norm_out.is_contiguous()):
-        return False
     st = L.stream_ptr()
-    if clip:
-        every = [p for g in groups for p in g["params"]]
-        if not every:
-            return False
-        arr = _tensor_list(optimizer, every)
-        nbytes = lib.bpx_grad_norm_workspace(len(every), arr)
-        if nbytes < 0:
-            raise L.BpxError("bpx_grad_norm_workspace: bad tensor list")
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=every[0].device)
-        if norm_out is None:
-            norm_out = torch.empty(2, dtype=torch.float32, device=every[0].device)
-        L.check(lib.bpx_grad_norm(len(every), arr, float(max_norm), ws.data_ptr(), nbytes, norm_out.data_ptr(), st))
+    coef = _clip_coefficient(optimizer, max_norm, norm_out, st)
     for k, g in enumerate(groups):
-        decoupled = 1 if isinstance(optimizer, torch.optim.AdamW) or g.get("decoupled_weight_decay", False) else 0
-        ps = [p for p in g["params"]]
+        ps = list(g["params"])
         if not ps:
             continue
-        arr = _tensor_list(optimizer, ps)
-        lr = g["lr"]
-        lr_d, lr_h = (lr.data_ptr(), 0.0) if torch.is_tensor(lr) and lr.is_cuda else (None, float(lr))
+        decoupled = 1 if isinstance(optimizer, torch.optim.AdamW) or g.get("decoupled_weight_decay", False) else 0
+        arr = _tensor_list(optimizer, ps, m="exp_avg", v="exp_avg_sq", step="step")
         b1, b2 = g["betas"]
-        if clip or beta1_d is not None:
-            L.check(lib.bpx_adam_step_dev(len(ps), arr, lr_d, lr_h, None if beta1_d is None else beta1_d[k].data_ptr(), float(b1), float(b2),
-                                          float(g["eps"]), float(g["weight_decay"]), decoupled, norm_out.data_ptr() + 4 if clip else None, st))
+        hyper = (float(b2), float(g["eps"]), float(g["weight_decay"]), decoupled)
+        if coef is not None or beta1_d is not None:
+            L.check(lib.bpx_adam_step_dev(len(ps), arr, *_lr_split(g["lr"]), None if beta1_d is None else beta1_d[k].data_ptr(), float(b1), *hyper,
+                                          coef, st))
         else:
-            L.check(lib.bpx_adam_step(len(ps), arr, lr_d, lr_h, float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), decoupled, st))
+            L.check(lib.bpx_adam_step(len(ps), arr, *_lr_split(g["lr"]), float(b1), *hyper, st))
     optimizer._opt_called = True             # what lr_scheduler's wrapper of optimizer.step() records (its "scheduler before optimizer" warning reads it)
     return True
 
@@ -238,9 +224,11 @@ def step(optimizer: torch.optim.Optimizer, *, max_norm: Optional[float] = None, 
          norm_out: Optional[torch.Tensor] = None, momentum_d: Optional[Sequence[Optional[torch.Tensor]]] = None) -> bool:
     """[``clip_grad_norm_(parameters, max_norm)`` ->] ``optimizer.step()``, through the HIP kernels where they apply (True); torch's own otherwise
     (False: the first step of a fresh optimizer, for one - its state does not exist yet)."""
-    if fused_step(optimizer, max_norm=max_norm, beta1_d=beta1_d, norm_out=norm_out):
-        return True
-    if fused_sgd_step(optimizer, max_norm=max_norm, momentum_d=momentum_d, norm_out=norm_out):
+    if type(optimizer) is torch.optim.SGD:
+        fused = fused_sgd_step(optimizer, max_norm=max_norm, momentum_d=momentum_d, norm_out=norm_out)
+    else:
+        fused = fused_step(optimizer, max_norm=max_norm, beta1_d=beta1_d, norm_out=norm_out)
+    if fused:
         return True
     if max_norm is not None:
         total = clip_grad_norm_([p for g in optimizer.param_groups for p in g["params"]], max_norm=max_norm)

@@ -486,13 +486,15 @@ class ResUNet(nn.Module):
                 once()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        from .graphs import _capture
+
         gf, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         # thread_local: a HIP call from another thread (e.g. the RCCL watchdog of an initialised process group) must not
         # invalidate the capture
-        with torch.cuda.graph(gf, capture_error_mode="thread_local"):
+        with _capture(gf):
             logits, saved = eng.forward(P, xs, head_act=0, save=True)
         dl = torch.zeros_like(logits)
-        with torch.cuda.graph(gb, pool=gf.pool(), capture_error_mode="thread_local"):
+        with _capture(gb, pool=gf.pool()):
             grads = eng.backward(P, saved, dl)
         torch.cuda.synchronize()
         with torch.no_grad():

@@ -4,7 +4,8 @@
 # of a shared kernel template can silently cost another instance a wave per SIMD (round 3: a persistent loop added for the transposed-conv
 # forward took the 48-column 1x1x1 GEMM of the same template from 130 to 170 VGPRs and from 402 to 598 us).
 cd "$(dirname "$0")/../biapy_amd/csrc"
-for F in tiling conv3d_igemm conv3d_lean conv3d_zmarch wgrad bwd_fused pointwise elementwise losses prepost; do
+FILES="tiling conv3d_igemm conv3d_lean conv3d_zmarch wgrad bwd_fused pointwise elementwise losses prepost optim augment"
+for F in $FILES; do
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -ffp-contract=off -fPIC -c $F.hip -o /tmp/kres_$F.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
 import sys,re
 cur=None; rows=[]
@@ -15,6 +16,7 @@ for l in sys.stdin:
         m=re.search(r'remark:\s+'+k+r': (\d+)',l)
         if m and cur: cur[i]=int(m.group(1))
 for r in sorted(rows): print('$F vgpr %3d agpr %3d scratch %4d occ %d lds %6d  %s'%(r[1],r[2],r[3],r[4],r[5],r[0]))
-" &
+" > /tmp/kres_$F.txt &
 done
 wait
+for F in $FILES; do cat /tmp/kres_$F.txt; done      # in the order of the list, not of completion: the table diffs clean from run to run

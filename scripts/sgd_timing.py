@@ -149,7 +149,7 @@ def main():
     ko = torch.optim.SGD(ps, lr=LR, momentum=0.9, nesterov=True, weight_decay=1e-2)
     ko.step()                                                          # torch creates the momentum buffers
     assert O.fused_sgd_step(ko)
-    arr = O._sgd_tensor_list(ko, ps, True)                             # the C call itself, the tensor list built once: no Python between the launches
+    arr = O._tensor_list(ko, ps, m="momentum_buffer")                  # the C call itself, the tensor list built once: no Python between the launches
     st = L.stream_ptr()
     kernel_ms = timed(lambda: L.check(L.lib.bpx_sgd_step(len(ps), arr, None, LR, None, 0.9, 0.0, 1e-2, 1, None, st)), 20, warm=5)
     to = torch.optim.SGD(ps, lr=LR, momentum=0.9, nesterov=True, weight_decay=1e-2, foreach=True)

@@ -292,6 +292,34 @@ def test_graphed_step_with_an_inactive_clip_is_the_unclipped_step():
         assert torch.equal(p, q), k
 
 
+def test_capture_keeps_the_garbage_collector_out():
+    """graphs._capture: unreachable cycles are collected before the capture begins and no collection pass runs inside it (a dead step object holds
+    a HIP graph and its pool; tearing those down while another capture is open aborts the process); the collector is back on afterwards."""
+    import gc
+    import weakref
+
+    from biapy_amd.graphs import _capture
+
+    class Node:
+        pass
+
+    a, b = Node(), Node()
+    a.other, b.other = b, a                                               # a dead cycle, as a dropped GraphedTrainStep is
+    a.payload = torch.zeros(8, device=DEV)
+    alive = weakref.ref(a)
+    del a, b
+    x = torch.zeros(4, device=DEV)
+    g = torch.cuda.CUDAGraph()
+    assert gc.isenabled()
+    with _capture(g):
+        assert alive() is None and not gc.isenabled()
+        y = x + 1
+    assert gc.isenabled()
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(y, torch.ones(4, device=DEV))
+
+
 # ---- 7, 8. train_one_epoch(graph="on") -----------------------------------------------------------------------------------------------------------------
 def _cfg(clip, sched):
     return types.SimpleNamespace(DATA=types.SimpleNamespace(PATCH_SIZE=(16, 16, 16, 1)),

@@ -181,6 +181,104 @@ def test_sgd_two_runs_are_bit_identical():
     assert not _same(out[0][0], _dev(p0))
 
 
+# ---- the launch scaffold all update kernels share -------------------------------------------------------------------------------------------------------
+# 300 tensors: five update launches of at most 64 tensors and two step-increment launches of at most 256, sizes of 1 element ... two 4096-element
+# chunks, (4099,) = one chunk + 3, the gradients views of one slab 3 elements in (all but a few unaligned).
+SCAFFOLD_SIZES = [((1,), (16,), (4099,), (8192,), (5, 7))[i % 5] for i in range(300)]
+SCAFFOLD_CLIP = 100.0                                                      # ||g|| ~ sqrt(740 580) = 860: every step clips
+
+
+@functools.lru_cache(maxsize=None)
+def _scaffold_base():
+    """(parameters, momentum buffers) on the CPU - made once, never written."""
+    gen = torch.Generator().manual_seed(7)
+    return [torch.randn(*s, generator=gen) for s in SCAFFOLD_SIZES], [torch.randn(*s, generator=gen) for s in SCAFFOLD_SIZES]
+
+
+def _torch_clip(params):
+    """clip_grad_norm_ on the reference's gradients; returns the coefficient it multiplied by as a device float (the same two torch ops on the same
+    norm as torch.nn.utils.clip_grad), which the kernels under test are then handed: both sides form the same fp32 product g * c."""
+    total = clip_grad_norm_(params, SCAFFOLD_CLIP, foreach=True)
+    return torch.clamp(SCAFFOLD_CLIP / (total + 1e-6), max=1.0).float()
+
+
+@pytest.mark.parametrize("path", ["bpx_adam_step", "bpx_adam_step_dev", "bpx_sgd_step"])
+def test_update_kernels_across_launch_batches_against_torch(path):
+    """Three steps over the 300 tensors through each entry point, against torch's own step on cloned tensors.  Adam: AdamW(fused, capturable) from
+    the same zero state, p, m, v within the 2e-6 of kernel_checks.check_fused_adam, every `step` 3.0 exactly; the _dev form reads beta1 from a
+    device double (the host argument is wrong on purpose) and clips.  SGD (Nesterov, weight decay, clipped): torch.optim.SGD(foreach=True) started
+    from this side's state at every step, so both sides lie within sgd_bound of the fp64 statement of that step and differ by at most twice the
+    bound.  With clipping, .g afterwards is what clip_grad_norm_ leaves, bit for bit.  No tensor keeps its initial value."""
+    from kernel_checks import relerr
+
+    L = _L()
+    p0, b0 = _scaffold_base()
+    ps = _dev(p0)
+    ref = [torch.nn.Parameter(p) for p in _dev(p0)]
+    clip = path != "bpx_adam_step"
+    if path == "bpx_sgd_step":
+        cfg = SB.CONFIGS["nesterov_wd"]
+        ms = _dev(b0)
+        opt = SB.torch_sgd(ref, cfg, foreach=True)
+        for r, b in zip(ref, b0):
+            opt.state[r]["momentum_buffer"] = b.clone().to(DEV)
+    else:
+        beta1 = 0.8999999999999999 if clip else 0.9                      # a one-cycle double that no float32 holds
+        ms, vs = [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps]
+        steps = [torch.zeros((), dtype=torch.float32, device=DEV) for _ in ps]
+        opt = torch.optim.AdamW(ref, lr=1e-2, betas=(beta1, 0.999), weight_decay=1e-2, fused=True, capturable=True)
+        beta1_d = torch.tensor(beta1, dtype=torch.float64, device=DEV)
+        arr = (L.AdamTensor * len(ps))()
+    worst = 0.0
+    for it in range(3):
+        grads, _ = OB.make_grads(SCAFFOLD_SIZES, seed=50 + it, offset=3, device=DEV)
+        for r, g in zip(ref, grads):
+            r.grad = g.clone()
+        coef = _torch_clip(ref) if clip else None
+        if path == "bpx_sgd_step":
+            with torch.no_grad():                                          # torch's step starts from this side's state
+                for r, p, m in zip(ref, ps, ms):
+                    r.copy_(p)
+                    opt.state[r]["momentum_buffer"].copy_(m)
+            before = [(p.cpu(), m.cpu()) for p, m in zip(ps, ms)]
+            opt.step()
+            _sgd(ps, grads, ms, cfg, gscale_d=coef)
+            torch.cuda.synchronize()
+            for r, p, m, g, (pb, mb) in zip(ref, ps, ms, grads, before):
+                bp, bb = SB.sgd_bound(pb, g.cpu(), mb, first=False, **cfg)
+                worst = max(worst, SB.worst_ratio(p, r.detach().cpu().double(), 2.0 * bp),
+                            SB.worst_ratio(m, opt.state[r]["momentum_buffer"].cpu().double(), 2.0 * bb))
+        else:
+            opt.step()
+            for i, (p, g, m, v, st) in enumerate(zip(ps, grads, ms, vs, steps)):
+                arr[i].p, arr[i].g, arr[i].m, arr[i].v, arr[i].step, arr[i].numel = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                                                                                    st.data_ptr(), p.numel())
+            if clip:
+                L.check(L.lib.bpx_adam_step_dev(len(ps), arr, None, 1e-2, beta1_d.data_ptr(), 0.5, 0.999, 1e-8, 1e-2, 1, coef.data_ptr(), L.stream_ptr()))
+            else:
+                L.check(L.lib.bpx_adam_step(len(ps), arr, None, 1e-2, beta1, 0.999, 1e-8, 1e-2, 1, L.stream_ptr()))
+            torch.cuda.synchronize()
+        if clip:
+            assert float(coef) < 1.0
+            assert _same(grads, [r.grad for r in ref]), "p.grad after the step is not what clip_grad_norm_ leaves"
+    if path == "bpx_sgd_step":
+        print(f"{path}: worst err / (2 bound) {worst:.3f}, bar 1")
+        assert worst <= 1.0
+        state = (ps, ms)
+    else:
+        errs = {"p": 0.0, "m": 0.0, "v": 0.0}
+        for r, p, m, v in zip(ref, ps, ms, vs):
+            errs["p"] = max(errs["p"], relerr(p, r))
+            errs["m"] = max(errs["m"], relerr(m, opt.state[r]["exp_avg"]))
+            errs["v"] = max(errs["v"], relerr(v, opt.state[r]["exp_avg_sq"]))
+        print(f"{path}: " + ", ".join(f"{k} {e:.3e} / bound 2e-6" for k, e in errs.items()))
+        assert all(e <= 2e-6 for e in errs.values()), errs
+        assert all(float(st) == 3.0 for st in steps) and all(float(opt.state[r]["step"]) == 3.0 for r in ref)
+        state = (ps, ms, vs)
+    for ts, init in zip(state, (p0, b0 if path == "bpx_sgd_step" else [torch.zeros_like(p) for p in p0], [torch.zeros_like(p) for p in p0])):
+        assert not any(torch.equal(t.cpu(), i) for t, i in zip(ts, init)), "a tensor was left at its initial value"
+
+
 @pytest.mark.parametrize("name", ["nesterov_wd", "wd"])
 def test_optim_step_against_torch_over_four_steps(name):
     """optim.step against torch's SGD, lr a device scalar scaled between the steps (as kernel_checks.check_fused_adam does for Adam): the package
