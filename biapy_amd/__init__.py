@@ -10,6 +10,7 @@ Public surface mirrors the reference names for this path:
   biapy_amd.chunked.ChunkedPredictor / ChunkGrid  <- chunked_test_pair_data_generator + process_test_sample_by_chunks (in-HBM volumes)
   biapy_amd.train_engine.train_one_epoch/evaluate <- biapy.engine.train_engine.train_one_epoch / evaluate
   biapy_amd.augment.DeviceAugmenter               <- the flips / rot90 / brightness / contrast / noise / cutout subset of biapy.data.generators.augmentors
-  biapy_amd.losses / prepost / tta                <- biapy.engine.metrics, biapy.data.norm + semantic_seg Otsu, biapy.data.post_processing TTA
+  biapy_amd.sampler.DevicePatchSampler / DevicePatchLoader <- random patch extraction (DATA.EXTRACT_RANDOM_PATCH, probability map) from resident volumes
+  biapy_amd.losses / prepost / tta               <- biapy.engine.metrics, biapy.data.norm + semantic_seg Otsu, biapy.data.post_processing TTA
 """
 __version__ = "0.1.0"

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("BPX_LIB_PATH") or os.path.join(_HERE, "libbiapy_amd.s
 
 F32, BF16, F16, U8, MIX16 = 0, 1, 2, 3, 4   # MIX16: backward entries only - fp16 activations, bf16 gradients (include/biapy_amd.h)
 # block activations of the reference (blocks.py:1973-1998): every entry of get_activation except "softmax" (a channel reduction, not a per-element prologue)
+U16 = 5                                      # the image of bpx_patch_gather only
 ACT = {"none": 0, "linear": 0, "elu": 1, "relu": 2, "silu": 3, "leaky_relu": 4, "gelu": 5, "tanh": 6, "sigmoid": 7, "softplus": 8}
 PK_K3, PK_K3_T, PK_K1, PK_DENSE, PK_DENSE_T, PK_CT, PK_CT_T, PK_CT4, PK_CT4_T = range(9)
 
@@ -61,6 +62,8 @@ _SIGS = {
     "bpx_aug_mean_blocks": ([_i64], _i),
     "bpx_aug_mean": ([_vp, _i, _i64, _vp, _vp, _vp], _i),
     "bpx_aug_apply": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_uint64, _f, _i, _vp, _vp, _vp], _i),
+    "bpx_patch_draw": ([_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp], _i),
+    "bpx_patch_gather": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp], _i),
     "bpx_scan_blocks": ([_i64], _i),
     "bpx_select_workspace": ([], _i64),
     "bpx_select_kth_f32": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),
@@ -224,6 +227,18 @@ class AugCfg(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("thr", C.c_uint64), ("enable", C.c_uint32), ("box_lo", C.c_int32), ("box_hi", C.c_int32),
                 ("c_lo", C.c_float), ("c_hi", C.c_float), ("b_lo", C.c_float), ("b_hi", C.c_float), ("s_lo", C.c_float), ("s_hi", C.c_float),
                 ("f_lo", C.c_float), ("f_hi", C.c_float)]
+
+
+class PatchVol(C.Structure):
+    """bpx_patch_vol (include/biapy_amd.h)."""
+    _fields_ = [("img", C.c_void_p), ("tgt", C.c_void_p), ("cls", C.c_void_p), ("Z", C.c_int32), ("Y", C.c_int32), ("X", C.c_int32),
+                ("reserved", C.c_int32), ("row0", C.c_int64)]
+
+
+class PatchCfg(C.Structure):
+    """bpx_patch_cfg (include/biapy_amd.h)."""
+    _fields_ = [("seed", C.c_uint64), ("V", C.c_int32), ("Pz", C.c_int32), ("Py", C.c_int32), ("Px", C.c_int32), ("K", C.c_int32),
+                ("class_cum", C.c_float * 8)]
 
 
 class AdamTensor(C.Structure):

@@ -30,7 +30,9 @@ enum bpx_dtype { BPX_F32 = 0, BPX_BF16 = 1, BPX_F16 = 2, BPX_U8 = 3,
                   * agree with the fp32 reference to Dice delta < 1e-4 - while every GRADIENT tensor (dy, g, dx, addend) and the MFMA
                   * operands of the backward kernels are bf16 (fp32 exponent range: no loss scaling).  Each backward entry says which of
                   * its operands are activations. */
-                 BPX_MIX16 = 4 };
+                 BPX_MIX16 = 4,
+                 /* BPX_U16: unsigned 16-bit integers - the image of bpx_patch_gather only (a resident volume as the microscope stored it) */
+                 BPX_U16 = 5 };
 /* Block activations (biapy/models/blocks.py:1973-1998, get_activation): codes 0-3 since round 1; round 4 adds leaky_relu (slope 0.01, nn.LeakyReLU's
  * default), gelu (nn.GELU(): the exact erf form), tanh, sigmoid and softplus (beta 1, threshold 20).  "softmax" as a block activation needs a
  * reduction over channels and is not a per-element prologue: not offered.  ELU (the reference default) has compile-time instances of every
@@ -708,6 +710,48 @@ int bpx_aug_mean_blocks(int64_t n);
 int bpx_aug_mean(const float* x_d, int B, int64_t n, double* ws_d, uint32_t* records_d, bpx_stream_t stream);
 int bpx_aug_apply(const float* x_d, const void* t_d, int t_dtype, int B, int Z, int Y, int X, int C, int Ct, const uint32_t* records_d, uint64_t seed,
                   float cval, int mask_too, float* x_out_d, void* t_out_d, bpx_stream_t stream);
+
+/* ---- random training patches from device-resident volumes (biapy_amd/sampler.py states the semantics; csrc/sampler.hip) ---------
+ * V volumes stay on the device: image (Z,Y,X,C), 1 <= C <= 16, float32 / uint8 / uint16; target (Z,Y,X,Ct), 1 <= Ct <= 8, uint8 / float32;
+ * 2-D data is Z = 1.  A call draws B patch origins and copies the B windows of Pz x Py x Px voxels into a (B,Pz,Py,Px,C) float32 batch
+ * and its (B,Pz,Py,Px,Ct) target.
+ * ORIGIN RECORD, origins_d[B][4] int32 (16-byte rows):  word 0  v, the volume    word 1  z0    word 2  y0    word 3  x0
+ * RANDOM NUMBERS: Philox4x32-10, key = seed, counter words = (sample b, stream, state_d[0] low, state_d[0] high).  Stream 0 is the only one
+ * in use: r0..r3 its four words, r64 = (uint64) r0 << 32 | r1, mulhi64(a, n) = the high 64 bits of a * n (uniform in [0, n)).
+ *   uniform mode (K == 0): every valid origin of every volume is equally likely.  n_v = (Z_v-Pz+1)(Y_v-Py+1)(X_v-Px+1), cum_d[V+1] their
+ *     exclusive int64 prefix; k = mulhi64(r64, cum_d[V]); v = the volume with cum_d[v] <= k < cum_d[v+1]; k - cum_d[v] = (z0 * ny + y0) * nx + x0.
+ *   class mode (1 <= K <= 8): every volume has a uint8 class map (Z,Y,X) with values < K.  u = (r2 >> 8) * 2^-24; the class c is the first
+ *     with u < class_cum[c] (fp32 compare; the entries from the last class of positive probability on are 1.0).  rowcum_d[K][R+1] is the
+ *     exclusive int64 prefix of the number of voxels of class c per row, the rows being all (v, z, y) of all volumes in that order
+ *     (volume v starts at row row0_v).  k = mulhi64(r64, rowcum_d[c][R]); the row has rowcum_d[c][row] <= k < rowcum_d[c][row+1];
+ *     j = k - rowcum_d[c][row]; the centre (z, y, x) is the (j+1)-th voxel of class c of that row;
+ *     origin = clamp(centre - P / 2, 0, dim - P) per axis (integer division). */
+typedef struct {
+  const void* img;         /* (Z,Y,X,C) */
+  const void* tgt;         /* (Z,Y,X,Ct) */
+  const uint8_t* cls;      /* (Z,Y,X) class map, class mode only */
+  int32_t Z, Y, X;
+  int32_t reserved;
+  int64_t row0;            /* index of the volume's first (z, y) row among the rows of all volumes: sum of Z * Y of the volumes before it */
+} bpx_patch_vol;
+typedef struct {
+  uint64_t seed;           /* Philox key */
+  int32_t V;               /* number of volumes */
+  int32_t Pz, Py, Px;      /* the patch */
+  int32_t K;               /* 0: uniform mode; 1..8: class mode with K classes */
+  float class_cum[8];      /* class mode: running fp32 sum of the class probabilities */
+} bpx_patch_cfg;
+/*   bpx_patch_draw   : fills origins_d and then adds 1 to state_d[0], the sampler's counter; state_d[1] is the ticket of bpx_aug_draw's scheme
+ *                      (0 between launches).  vols_h / vols_d: the same V descriptors on the host (argument checks: a patch larger than a volume
+ *                      is refused) and on the device.  cum_d: uniform mode; rowcum_d and R (the number of rows): class mode.  One launch,
+ *                      nothing is read back: capturable, a replay draws anew.
+ *   bpx_patch_gather : x_out[b] = float32(img_v[z0:z0+Pz, y0:y0+Py, x0:x0+Px, :]) (uint8 / uint16 convert exactly; times `scale`, one fp32
+ *                      multiply, when use_scale != 0; a float32 image without scale moves bit for bit), t_out[b] = the same window of the target,
+ *                      bit for bit.  Origins are read from origins_d and clamped into their volume.  One launch. */
+int bpx_patch_draw(const bpx_patch_cfg* cfg, const bpx_patch_vol* vols_h, const bpx_patch_vol* vols_d, const int64_t* cum_d, const int64_t* rowcum_d,
+                   int64_t R, int B, uint64_t* state_d, int32_t* origins_d, bpx_stream_t stream);
+int bpx_patch_gather(const bpx_patch_vol* vols_h, const bpx_patch_vol* vols_d, int V, int img_dtype, int C, int tgt_dtype, int Ct, int Pz, int Py, int Px,
+                     const int32_t* origins_d, int B, int use_scale, float scale, float* x_out_d, void* t_out_d, bpx_stream_t stream);
 
 #ifdef __cplusplus
 }
