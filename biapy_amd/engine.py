@@ -290,17 +290,11 @@ def block_keys(prefix: str, first: bool) -> Dict[str, str]:
 
 
 class _Stats:
-    """Partial-statistics scratch + finalize into a norm-record array."""
+    """Partial-statistics scratch (its finalize into norm records: ResUNetEngine._norm_finalize, _norm_records, _cat_records)."""
 
     @staticmethod
     def alloc(B, tiles, C, dev):
         return torch.empty((B, tiles, 2, C), dtype=torch.float32, device=dev)
-
-    @staticmethod
-    def finalize(part, B, tiles, C, count, gamma, beta, rec, rec_ld, rec_off, st, groups=0):
-        """InstanceNorm records (groups = 0 -> one group per channel) or GroupNorm(groups) records of ONE producer's tensor."""
-        L.check(lib.bpx_norm_finalize(part.data_ptr(), B, tiles, C, count, gamma.data_ptr(), beta.data_ptr(), EPS, groups or C,
-                                      rec.data_ptr(), rec_ld, rec_off, st))
 
     @staticmethod
     def finalize_cat(parts, B, count, gamma, beta, rec, groups, st):
@@ -487,14 +481,42 @@ class ResUNetEngine:
         """Records of channels [lo, lo + C) of norm layer `layer` from one producer's partials (training mode; eval-mode BN records come from
         _bn_eval_records).  BatchNorm updates the running buffers of those channels; num_batches_tracked with the call that covers channel 0."""
         g, b = P[layer + ".weight"], P[layer + ".bias"]
-        if not self.bn:
-            _Stats.finalize(part, B, tiles, C, count, g[lo:lo + C], b[lo:lo + C], rec, rec_ld, rec_off, st, self.cfg.gn_groups)
+        if not self.bn:      # InstanceNorm (one group per channel) or GroupNorm(gn_groups) records of ONE producer's tensor
+            L.check(lib.bpx_norm_finalize(part.data_ptr(), B, tiles, C, count, g[lo:].data_ptr(), b[lo:].data_ptr(), EPS, self.cfg.gn_groups or C,
+                                          rec.data_ptr(), rec_ld, rec_off, st))
             return
         eps, mom = self._bn_hp(layer)
         rm, rv, nbt = (P.get(layer + s) for s in _BN_BUFFERS)
         L.check(lib.bpx_batchnorm_finalize(part.data_ptr(), B, tiles, C, count, g[lo:].data_ptr(), b[lo:].data_ptr(), eps, mom,
                                            None if rm is None else rm[lo:].data_ptr(), None if rv is None else rv[lo:].data_ptr(),
                                            L.ptr(nbt) if lo == 0 else None, rec.data_ptr(), rec_ld, rec_off, st))
+
+    def _norm_records(self, P, layer: str, part, tiles, C, vox, st) -> torch.Tensor:
+        """The (B, C, 4) records of norm layer `layer` on ONE producer's tensor: the running-buffer records of an eval-mode BatchNorm forward,
+        else new ones from the producer's partials (B, tiles, 2, C)."""
+        if self._bn_eval is not None:
+            return self._bn_eval[layer]
+        B = part.shape[0]
+        rec = _recs(B, C, part.device)
+        self._norm_finalize(P, layer, part, B, tiles, C, vox, rec, C, 0, st)
+        return rec
+
+    def _cat_records(self, P, layer: str, parts, B, vox, dev, st) -> torch.Tensor:
+        """The records of norm layer `layer` on torch.cat(producers, 1): parts = [(partials, tiles, C), ...] in channel order.  A GroupNorm group may
+        straddle two producers (_Stats.finalize_cat); InstanceNorm and BatchNorm finalize each producer's column range (of the records, of gamma /
+        beta and of the running buffers) on its own."""
+        if self._bn_eval is not None:
+            return self._bn_eval[layer]
+        Ct = sum(c for _, _, c in parts)
+        rec = _recs(B, Ct, dev)
+        if self.cfg.gn_groups:
+            _Stats.finalize_cat(parts, B, vox, P[layer + ".weight"], P[layer + ".bias"], rec, self.cfg.gn_groups, st)
+            return rec
+        lo = 0
+        for part, tiles, c in parts:
+            self._norm_finalize(P, layer, part, B, tiles, c, vox, rec, Ct, lo, st, lo=lo)
+            lo += c
+        return rec
 
     def _bn_eval_records(self, P, B, dev, cache: bool) -> Dict[str, torch.Tensor]:
         """{layer: (B, C, 4) records} of every BN layer from the running buffers, ONE launch (bpx_batchnorm_eval_records).  Kept while the
@@ -643,14 +665,48 @@ class ResUNetEngine:
         return (act <= 3 and self.cfg.gn_groups == 0 and self.dtype != torch.float32
                 and bool(lib.bpx_conv3d_bwd_fused_supported(self.bdt, B, S[0], S[1], S[2], Ct, Cdy)))
 
-    def _bwd_fused(self, B, S, dy: "L.Tensor", wt, t: "L.Tensor", rec, g: "L.Tensor", dw, db, db2, st, dev, act: Optional[int] = None):
+    def _dgrad_prologue(self, B, S, dy: "L.Tensor", wt, t: "L.Tensor", rec, act, g: "L.Tensor", st, *, fused: bool, dw=None, db=None, db2=None):
+        """Input gradient of ``conv3(act(norm(t)))`` into g, times act', with the norm backward's reduction partials -> (tiles, red).  ``fused``
+        (the caller asked _bwd_fused_ok): one pass over (dy, t) that also forms the conv's weight / bias gradients dw, db (db2: a second bias that
+        takes the same sums); otherwise the dgrad kernel alone - the caller issued the conv's _wgrad."""
         D, H, W = S
-        tiles = lib.bpx_conv3d_bwd_fused_stats_tiles(B, D, H, W, t.C, dy.C)
-        red = torch.empty((B, tiles, 2, t.C), dtype=torch.float32, device=dev)
-        ws = self._workspace(lib.bpx_conv3d_bwd_fused_workspace(B, D, H, W, t.C, dy.C), dev)
-        L.check(lib.bpx_conv3d_bwd_fused(self.bdt, B, D, H, W, dy, wt.data_ptr(), t, rec.data_ptr(), self.act if act is None else act, g, red.data_ptr(),
-                                         dw.data_ptr(), L.ptr(db), L.ptr(db2), ws.data_ptr(), ws.numel(), st))
+        dev = rec.device
+        if fused:
+            tiles = lib.bpx_conv3d_bwd_fused_stats_tiles(B, D, H, W, t.C, dy.C)
+            red = torch.empty((B, tiles, 2, t.C), dtype=torch.float32, device=dev)
+            ws = self._workspace(lib.bpx_conv3d_bwd_fused_workspace(B, D, H, W, t.C, dy.C), dev)
+            L.check(lib.bpx_conv3d_bwd_fused(self.bdt, B, D, H, W, dy, wt.data_ptr(), t, rec.data_ptr(), act, g, red.data_ptr(),
+                                             dw.data_ptr(), L.ptr(db), L.ptr(db2), ws.data_ptr(), ws.numel(), st))
+        else:
+            tiles = lib.bpx_conv3d_stats_tiles(self.dt, B, D, H, W, t.C)
+            red = torch.empty((B, tiles, 2, t.C), dtype=torch.float32, device=dev)
+            L.check(lib.bpx_conv3d_dgrad(self.bdt, B, D, H, W, dy, wt.data_ptr(), t, rec.data_ptr(), act, g, red.data_ptr(), st))
         return tiles, red
+
+    def _norm_bwd_coef(self, red, B, tiles, C, vox, rec, gamma, dgamma, dbeta, st, *, deferred: bool) -> torch.Tensor:
+        """Norm backward finalize: the reduction partials `red` (B, tiles, 2, C) of a dgrad prologue or of bpx_norm_act_bwd -> the (B, C, 4)
+        coefficients bpx_norm_bwd_apply and the pointwise hand-over kernels read; dgamma / dbeta (either may be None) take the affine gradients.
+        ``deferred``: dgamma / dbeta arrive with the flush of the pass's weight-gradient reductions, `red` holds their per-sample terms until then."""
+        coef = torch.empty((B, C, 4), dtype=torch.float32, device=red.device)
+        gng = self.cfg.gn_groups
+        if self.bn:
+            L.check(lib.bpx_batchnorm_bwd_finalize(red.data_ptr(), B, tiles, C, vox, rec.data_ptr(), gamma.data_ptr(), L.ptr(dgamma), L.ptr(dbeta),
+                                                   self._bn_running, coef.data_ptr(), st))
+        elif gng and (C // gng) not in (1, 2, 4, 8, 16, 32, 64):
+            # the concatenated decoder input: 6 / 12 / 24 / 48 channels per group -> per-channel totals, then the general group kernel.  Never a
+            # block's own width: NetConfig.__post_init__ rejects GroupNorm widths outside the power-of-two set
+            sums = torch.empty((B, C, 2), dtype=torch.float64, device=red.device)
+            L.check(lib.bpx_norm_channel_sums(red.data_ptr(), B, tiles, C, sums.data_ptr(), C, 0, st))
+            L.check(lib.bpx_groupnorm_bwd_finalize(sums.data_ptr(), B, C, vox, rec.data_ptr(), gamma.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), gng,
+                                                   coef.data_ptr(), st))
+        elif deferred:
+            self._keep.append(red)
+            L.check(lib.bpx_norm_bwd_finalize_deferred(red.data_ptr(), B, tiles, C, vox, rec.data_ptr(), gamma.data_ptr(), L.ptr(dgamma), L.ptr(dbeta),
+                                                       gng or C, coef.data_ptr(), st))
+        else:
+            L.check(lib.bpx_norm_bwd_finalize(red.data_ptr(), B, tiles, C, vox, rec.data_ptr(), gamma.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), gng or C,
+                                              coef.data_ptr(), st))
+        return coef
 
     def _norm_act_bwd(self, raw: torch.Tensor, rec, act, dA: "L.Tensor", gamma, dgamma, dbeta, st) -> torch.Tensor:
         """Backward of a materialised ``act(IN(raw))`` (raw: a dense NDHWC tensor): dA -> d(raw), a new gradient tensor.  The elementwise
@@ -661,17 +717,91 @@ class ResUNetEngine:
         red = torch.empty((B, tiles, 2, C), dtype=torch.float32, device=dev)
         g = torch.empty(raw.shape, dtype=self.gdtype, device=dev)
         L.check(lib.bpx_norm_act_bwd(self.bdt, B, vox, dA, L.tview(raw), rec.data_ptr(), act, L.NULL_T, L.tview(g), red.data_ptr(), st))
-        coef = torch.empty((B, C, 4), dtype=torch.float32, device=dev)
-        L.check(lib.bpx_norm_bwd_finalize(red.data_ptr(), B, tiles, C, vox, rec.data_ptr(), gamma.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), C,
-                                          coef.data_ptr(), st))
+        coef = self._norm_bwd_coef(red, B, tiles, C, vox, rec, gamma, dgamma, dbeta, st, deferred=False)
         L.check(lib.bpx_norm_bwd_apply(self.bdt, B, vox, L.tview(g), L.tview(raw), coef.data_ptr(), L.NULL_T, L.tview(g), st))
         return g
 
-    def _head_bwd(self, G, B, vox, feat: "L.Tensor", hw: torch.Tensor, dl: torch.Tensor, dfeat: "L.Tensor", st, dev) -> None:
-        """Backward of the heads (bpx_head_bwd, the (n_out, fm0) matrix hw on `feat`, fm0 = 16 or 32): the input gradient into dfeat, the
-        weight / bias gradients into G's zeroed ``heads.{h}`` entries - in place for one head, else through one matrix split by rows."""
+    def _convT_bwd(self, P, G, B, Sl, sz, x_in: torch.Tensor, dUp: torch.Tensor, wk: str, bk: str, Cin: int, Cout: int, st, dev) -> torch.Tensor:
+        """Backward of ConvTranspose3d(Cin, Cout, k = s = (sz, 2, 2)) on x_in (B, *Sl, Cin): dUp -> the new d(x_in), with the weight / bias gradients
+        into G[wk], G[bk] (bpx_convT3d_k2s2_bwd: from ONE pass over dUp at the 32 -> 32 level of a large volume, else the two kernels)."""
+        ws = self._workspace(lib.bpx_convT3d_k2s2_wgrad_workspace(B, Sl[0], Sl[1], Sl[2], sz, Cin, Cout), dev)
+        dx = torch.empty((B,) + tuple(Sl) + (Cin,), dtype=self.gdtype, device=dev)
+        wt = self._pack(P[wk], L.PK_CT_T if sz == 2 else L.PK_CT4_T, Cin, Cout, False)
+        L.check(lib.bpx_convT3d_k2s2_bwd(self.bdt, B, Sl[0], Sl[1], Sl[2], sz, L.tview(x_in), L.tview(dUp), wt.data_ptr(), L.tview(dx),
+                                         G[wk].data_ptr(), G[bk].data_ptr(), ws.data_ptr(), ws.numel(), st))
+        self._keep += [dUp, dx]
+        return dx
+
+    # ---- heads ----------------------------------------------------------------------------------------
+    def _head_matrix(self, P) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The heads as ONE (n_out, fm0) matrix and its bias: a single head reads the parameter itself, several are concatenated by rows."""
+        outs, fm0 = self.cfg.out_channels, list(self.cfg.feature_maps)[0]
+        if len(outs) == 1:
+            hw, hb = P["heads.0.weight"], P["heads.0.bias"]
+        else:
+            hw = torch.cat([P[f"heads.{h}.weight"].reshape(-1, fm0) for h in range(len(outs))], 0)
+            hb = torch.cat([P[f"heads.{h}.bias"] for h in range(len(outs))], 0)
+        return hw.reshape(sum(outs), fm0).contiguous(), hb
+
+    def _pick16_fwd(self, B, vox, o16: torch.Tensor, n_out: int, head_act: int, logits: torch.Tensor, st) -> torch.Tensor:
+        """The first n_out channels of the zero-padded 16-channel tensor o16, through the output activation, into the planar fp32 logits: the head
+        kernel with an identity matrix, which is returned (the backward's operand)."""
+        eye = torch.eye(n_out, 16, dtype=torch.float32, device=o16.device).contiguous()
+        zb = torch.zeros((n_out,), dtype=torch.float32, device=o16.device)
+        L.check(lib.bpx_head_fwd(self.dt, vox, B, L.tview(o16), eye.data_ptr(), zb.data_ptr(), n_out, head_act, logits.data_ptr(), n_out * vox, vox, st))
+        return eye
+
+    def _pick16_bwd(self, B, vox, o16: torch.Tensor, eye: torch.Tensor, n_out: int, dl: torch.Tensor, st, dev) -> torch.Tensor:
+        """Backward of _pick16_fwd: dl (the fp32 logits' gradient) -> the new d(o16); the identity matrix's own gradients are discarded."""
+        do16 = torch.empty(o16.shape, dtype=self.gdtype, device=dev)
+        eg, ebg = torch.zeros((n_out, 16), dtype=torch.float32, device=dev), torch.zeros((n_out,), dtype=torch.float32, device=dev)
+        hws = self._workspace(lib.bpx_head_bwd_workspace(16, n_out), dev)
+        L.check(lib.bpx_head_bwd(self.bdt, vox, B, L.tview(o16), eye.data_ptr(), n_out, dl.data_ptr(), n_out * vox, vox, L.tview(do16), eg.data_ptr(),
+                                 ebg.data_ptr(), hws.data_ptr(), hws.numel(), st))
+        self._keep += [do16, eg, ebg]
+        return do16
+
+    def _head_fwd(self, B, So, feat: torch.Tensor, hw: torch.Tensor, hb: torch.Tensor, head_act: int, st, dev):
+        """The heads (_head_matrix) on the dense feature tensor -> (planar fp32 logits (B, n_out, *So), what _head_bwd needs of a wide head or None)."""
+        n_out, fm0 = hw.shape
+        vox = So[0] * So[1] * So[2]
+        logits = torch.empty((B, n_out) + tuple(So), dtype=torch.float32, device=dev)
+        if fm0 in (16, 32):
+            L.check(lib.bpx_head_fwd(self.dt, vox, B, L.tview(feat), hw.data_ptr(), hb.data_ptr(), n_out, head_act, logits.data_ptr(), n_out * vox, vox, st))
+            return logits, None
+        # wider first level (e.g. FEATURE_MAPS [48, 64, 80, 96] of the reference's Ovarian-Reserve template): the heads' (n_out, fm0) matrix,
+        # zero-padded to 16 rows, runs as a 1x1x1 convolution on the pointwise MFMA kernel; the head kernel then picks the real channels of the
+        # 16-channel result and applies the output activation.  The logits pass through the 16-bit storage type once.
+        w16 = torch.zeros((16, fm0), dtype=torch.float32, device=dev)
+        b16 = torch.zeros((16,), dtype=torch.float32, device=dev)
+        w16[:n_out] = hw
+        b16[:n_out] = hb
+        o16 = torch.empty((B,) + tuple(So) + (16,), dtype=self.dtype, device=dev)
+        wp16 = self._pack(w16, L.PK_DENSE, fm0, 16, False)
+        L.check(lib.bpx_conv1x1_fwd(self.dt, B, vox, L.tview(feat), wp16.data_ptr(), b16.data_ptr(), L.NULL_T, L.NULL_T, None, L.NULL_T, L.tview(o16), st))
+        return logits, dict(o16=o16, w16=w16, eye=self._pick16_fwd(B, vox, o16, n_out, head_act, logits, st))
+
+    def _head_bwd(self, G, B, So, feat: "L.Tensor", hw: torch.Tensor, dl: torch.Tensor, dfeat: "L.Tensor", st, dev, wide=None) -> None:
+        """Backward of the heads (the (n_out, fm0) matrix hw on `feat`): the input gradient into dfeat, the weight / bias gradients into G's zeroed
+        ``heads.{h}`` entries - in place for one head, else through one matrix split by rows.  fm0 = 16 or 32: bpx_head_bwd; ``wide`` (_head_fwd):
+        the pick's backward on the 16-channel tensor, then the 1x1x1 convolution's two gradients."""
         outs = list(self.cfg.out_channels)
         n_out, fm0 = sum(outs), feat.C
+        vox = So[0] * So[1] * So[2]
+        if wide is not None:
+            # k = 1 wgrad (rows 0 .. n_out of the padded matrix are the heads') and the pointwise GEMM with the transposed matrix.  The weight gradient
+            # is reduced right away (not with the step's batch): its heads' rows are copied out at once.
+            do16 = self._pick16_bwd(B, vox, wide["o16"], wide["eye"], n_out, dl, st, dev)
+            dw16 = torch.zeros((16, fm0, 1, 1, 1), dtype=torch.float32, device=dev)
+            db16 = torch.zeros((16,), dtype=torch.float32, device=dev)
+            self._wgrad(B, So, feat, None, 0, L.tview(do16), 1, dw16, db16, st, dev)
+            L.check(lib.bpx_wgrad_defer_flush(L.stream_ptr()))
+            L.check(lib.bpx_wgrad_defer_begin())
+            self._split_heads(G, dw16.view(16, fm0)[:n_out], db16[:n_out])
+            wt16 = self._pack(wide["w16"], L.PK_DENSE_T, fm0, 16, False)
+            L.check(lib.bpx_conv1x1_fwd(self.gdt, B, vox, L.tview(do16), wt16.data_ptr(), None, L.NULL_T, L.NULL_T, None, L.NULL_T, dfeat, st))
+            self._keep += [dw16, db16]
+            return
         one_head = len(outs) == 1
         hwg = G["heads.0.weight"] if one_head else torch.zeros((n_out, fm0), dtype=torch.float32, device=dev)
         hbg = G["heads.0.bias"] if one_head else torch.zeros((n_out,), dtype=torch.float32, device=dev)
@@ -817,12 +947,7 @@ class ResUNetEngine:
             L.check(lib.bpx_conv3d_fwd(self.dt, B, D, H, W, L.tview(blk.x, blk.x_c0, blk.cin),
                                        L.ptr(blk.rec_x), self.act if blk.rec_x is not None else 0, wp.data_ptr(), P[k["b1"]].data_ptr(),
                                        L.NULL_T, None, None, L.tview(blk.h), L.ptr(part), st))
-        n1 = k["g1"][:-len(".weight")]
-        if self._bn_eval is not None:
-            blk.rec_h = self._bn_eval[n1]
-        else:
-            blk.rec_h = _recs(B, C1, dev)
-            self._norm_finalize(P, n1, part, B, tiles, C1, vox, blk.rec_h, C1, 0, st)
+        blk.rec_h = self._norm_records(P, k["g1"][:-len(".weight")], part, tiles, C1, vox, st)
         # ---- dropout: conv2 reads the materialised, masked activation instead of forming it in its prologue -------
         x2, rec2, act2 = L.tview(blk.h), blk.rec_h.data_ptr(), self.act
         if blk.drop_p > 0.0 and self.drop_active:
@@ -855,6 +980,35 @@ class ResUNetEngine:
         return part2, tiles2
 
     # ------------------------------------------------------------------------------------------
+    def _level_shapes(self, S0, zd) -> List[Tuple[int, int, int]]:
+        """(D, H, W) of every level of a patch S0: z_down zd[i] and y / x down 2 from level i to i + 1."""
+        Lv = len(zd)
+        zdiv = math.prod(zd)
+        if S0[0] % zdiv or S0[1] % (2 ** Lv) or S0[2] % (2 ** Lv):
+            raise ValueError(f"patch {tuple(S0)} must be divisible by {(zdiv, 2 ** Lv, 2 ** Lv)} (DATA.PATCH_SIZE rule, check_configuration.py:3156-3202)")
+        S = [tuple(S0)]
+        for i in range(Lv):
+            S.append((S[i][0] // zd[i], S[i][1] // 2, S[i][2] // 2))
+        return S
+
+    def _ingest(self, x: torch.Tensor, x_ndhwc: Optional[torch.Tensor], st):
+        """The (B, C, D, H, W) fp32 image as the first block reads it -> (img, x_ndhwc): one channel as the planar fp32 img; otherwise a dense NDHWC
+        tensor of the storage type - the caller's own, the zero-padded 16 channels of a 2 to 15 channel image (_pack_image16), or a cast copy."""
+        B, Cin, D0, H0, W0 = x.shape
+        if Cin == 1:
+            return x.reshape(B, D0, H0, W0).contiguous(), None
+        if x_ndhwc is not None:
+            return None, x_ndhwc
+        if self.cfg.true_in_ch is not None:
+            return None, self._pack_image16(x, st)
+        xin = x.permute(0, 2, 3, 4, 1).contiguous()
+        x_ndhwc = torch.empty(xin.shape, dtype=self.dtype, device=x.device)
+        if self.dtype == torch.float32:
+            x_ndhwc.copy_(xin)
+        else:
+            L.check(lib.bpx_cast(L.F32, xin.data_ptr(), self.dt, x_ndhwc.data_ptr(), xin.numel(), st))
+        return None, x_ndhwc
+
     def forward(self, P: Dict[str, torch.Tensor], x: Optional[torch.Tensor], head_act: int = 0, save: bool = False, cache_weights: bool = False,
                 x_ndhwc: Optional[torch.Tensor] = None, want_dx: bool = False):
         """x: (B,C,Z,Y,X) fp32 with channels_last_3d strides (or any layout for C == 1; planar or channels-last for the 2 to 15 channels of a
@@ -903,12 +1057,7 @@ class ResUNetEngine:
         B, Cin, D0, H0, W0 = x.shape
         assert Cin == (cfg.true_in_ch or cfg.in_ch), f"expected {cfg.true_in_ch or cfg.in_ch} input channels, got {Cin}"
         Lv = cfg.depth
-        div = 2 ** Lv
-        zdiv = 1
-        for v in cfg.z_down:
-            zdiv *= v
-        if D0 % zdiv or H0 % div or W0 % div:
-            raise ValueError(f"patch {D0, H0, W0} must be divisible by {(zdiv, div, div)} (DATA.PATCH_SIZE rule, check_configuration.py:3156-3202)")
+        S = self._level_shapes((D0, H0, W0), cfg.z_down)
         dev = x.device
         st = L.stream_ptr()
         fm = list(cfg.feature_maps)
@@ -917,25 +1066,7 @@ class ResUNetEngine:
             self._prepack(P, save, dev)       # ONE batched pack launch (training re-packs every step; so does a captured inference)
         else:
             self._prepacked = {}
-        if Cin == 1:
-            img = x.reshape(B, D0, H0, W0).contiguous()
-            x_ndhwc = None
-        elif x_ndhwc is not None:
-            img = None
-        elif cfg.true_in_ch is not None:
-            img, x_ndhwc = None, self._pack_image16(x, st)
-        else:
-            img = None
-            xin = x.permute(0, 2, 3, 4, 1).contiguous()
-            x_ndhwc = torch.empty(xin.shape, dtype=T, device=dev)
-            if T == torch.float32:
-                x_ndhwc.copy_(xin)
-            else:
-                L.check(lib.bpx_cast(L.F32, xin.data_ptr(), self.dt, x_ndhwc.data_ptr(), xin.numel(), st))
-
-        S = [(D0, H0, W0)]
-        for i in range(Lv):
-            S.append((S[i][0] // cfg.z_down[i], S[i][1] // 2, S[i][2] // 2))
+        img, x_ndhwc = self._ingest(x, x_ndhwc, st)
         if self.bn and self.bn_training and B * S[Lv][0] * S[Lv][1] * S[Lv][2] == 1:
             # what torch.nn.functional.batch_norm raises (at the bottleneck's first norm, the first with one value per channel); up front, not from a kernel
             raise ValueError(f"Expected more than 1 value per channel when training, got input size torch.Size([{B}, {fm[Lv - 1]}, 1, 1, 1])")
@@ -974,13 +1105,8 @@ class ResUNetEngine:
             out_stats.append((part, tiles))
             blocks.append(blk)
             nxt = "bottleneck" if i == Lv - 1 else f"down_path.{i + 1}"
-            if self._bn_eval is not None:
-                rec = self._bn_eval[f"{nxt}.block.0"]
-            else:
-                rec = _recs(B, fm[i], dev)
-                self._norm_finalize(P, f"{nxt}.block.0", ppart, B, ptiles, fm[i], S[i + 1][0] * S[i + 1][1] * S[i + 1][2], rec, fm[i], 0, st)
             pools.append(pooled)
-            cur, cur_rec = pooled, rec
+            cur, cur_rec = pooled, self._norm_records(P, f"{nxt}.block.0", ppart, ptiles, fm[i], math.prod(S[i + 1]), st)
         # ---------------- bottleneck ----------------------------------------------------------------
         bot = _Blk(keys=block_keys("bottleneck", False), first=False, S=S[Lv], cin=fm[Lv - 1], cout=fm[Lv], x=cur, rec_x=cur_rec,
                    h=buf(Lv, fm[Lv]), out=buf(Lv, fm[Lv]), out_c0=0, drop_p=cfg.dropout[Lv], site=Lv)
@@ -999,36 +1125,16 @@ class ResUNetEngine:
             upart = _Stats.alloc(B, utiles, Cup, dev) if self._bn_eval is None else None
             L.check(lib.bpx_convT3d_k2s2_fwd(self.dt, B, Dl, Hl, Wl, szl, L.tview(dec_in), wp.data_ptr(), P[bk].data_ptr(),
                                              L.tview(cat[i], 0, Cup), L.ptr(upart), st))
-            Ccat = Cup + fm[i]
             pre = f"up_paths.0.{j}.conv_block"
-            vox = S[i][0] * S[i][1] * S[i][2]
-            rec = _recs(B, Ccat, dev) if self._bn_eval is None else self._bn_eval[f"{pre}.block.0"]
-            g0, be0 = P[f"{pre}.block.0.weight"], P[f"{pre}.block.0.bias"]
-            spart, stiles = out_stats[i]
-            if self._bn_eval is not None:
-                pass                                    # eval-mode BN: the records of the running buffers (above)
-            elif self.bn:      # the two column ranges of torch.cat([up, skip], 1) and of the running buffers ([:Cup], [Cup:])
-                self._norm_finalize(P, f"{pre}.block.0", upart, B, utiles, Cup, vox, rec, Ccat, 0, st)
-                self._norm_finalize(P, f"{pre}.block.0", spart, B, stiles, fm[i], vox, rec, Ccat, Cup, st, lo=Cup)
-            elif cfg.gn_groups:
-                _Stats.finalize_cat([(upart, utiles, Cup), (spart, stiles, fm[i])], B, vox, g0, be0, rec, cfg.gn_groups, st)
-            else:
-                _Stats.finalize(upart, B, utiles, Cup, vox, g0[:Cup], be0[:Cup], rec, Ccat, 0, st)
-                _Stats.finalize(spart, B, stiles, fm[i], vox, g0[Cup:], be0[Cup:], rec, Ccat, Cup, st)
-            blk = _Blk(keys=block_keys(pre, False), first=False, S=S[i], cin=Ccat, cout=fm[i], x=cat[i], x_c0=0, rec_x=rec,
+            rec = self._cat_records(P, f"{pre}.block.0", [(upart, utiles, Cup), out_stats[i] + (fm[i],)], B, math.prod(S[i]), dev, st)
+            blk = _Blk(keys=block_keys(pre, False), first=False, S=S[i], cin=Cup + fm[i], cout=fm[i], x=cat[i], x_c0=0, rec_x=rec,
                        h=buf(i, fm[i]), out=buf(i, fm[i]), out_c0=0, drop_p=cfg.dropout[i], site=Lv + 1 + j)
             self._res_block_fwd(P, blk, B, img, st, cache_weights, want_out_stats=False)
             blocks.append(blk)
             ups.append((wk, bk, dec_in, Cup, S[i + 1], szl))
             dec_in = blk.out
         # ---------------- heads ----------------------------------------------------------------------
-        n_out = sum(cfg.out_channels)
-        if len(cfg.out_channels) == 1:
-            hw, hb = P["heads.0.weight"], P["heads.0.bias"]
-        else:
-            hw = torch.cat([P[f"heads.{h}.weight"].reshape(-1, fm[0]) for h in range(len(cfg.out_channels))], 0)
-            hb = torch.cat([P[f"heads.{h}.bias"] for h in range(len(cfg.out_channels))], 0)
-        hw = hw.reshape(n_out, fm[0]).contiguous()
+        hw, hb = self._head_matrix(P)
         feat, So = dec_in, (D0, H0, W0)
         if cfg.post_up:
             # super-resolution: ConvTranspose3d(fm0, fm0, k = s = (post_up, 2, 2)) on the decoder output (resunet.py:399-400)
@@ -1038,29 +1144,9 @@ class ResUNetEngine:
             pupart = _Stats.alloc(B, lib.bpx_convT3d_stats_tiles(D0, H0, W0, cfg.post_up), fm[0], dev)       # statistics unused
             L.check(lib.bpx_convT3d_k2s2_fwd(self.dt, B, D0, H0, W0, cfg.post_up, L.tview(dec_in), wpu.data_ptr(), P["post_upsampling.bias"].data_ptr(),
                                              L.tview(feat), pupart.data_ptr(), st))
-        logits = torch.empty((B, n_out) + So, dtype=torch.float32, device=dev)
-        vox0 = So[0] * So[1] * So[2]
-        wide = None
-        if fm[0] in (16, 32):
-            L.check(lib.bpx_head_fwd(self.dt, vox0, B, L.tview(feat), hw.data_ptr(), hb.data_ptr(), n_out, head_act, logits.data_ptr(),
-                                     n_out * vox0, vox0, st))
-        else:
-            # wider first level (e.g. FEATURE_MAPS [48, 64, 80, 96] of the reference's Ovarian-Reserve template): the heads' (n_out, fm0) matrix,
-            # zero-padded to 16 rows, runs as a 1x1x1 convolution on the pointwise MFMA kernel; the head kernel then picks the real channels of the
-            # 16-channel result (an identity matrix) and applies the output activation.  The logits pass through the 16-bit storage type once.
-            w16 = torch.zeros((16, fm[0]), dtype=torch.float32, device=dev)
-            b16 = torch.zeros((16,), dtype=torch.float32, device=dev)
-            w16[:n_out] = hw
-            b16[:n_out] = hb
-            o16 = torch.empty((B,) + So + (16,), dtype=T, device=dev)
-            wp16 = self._pack(w16, L.PK_DENSE, fm[0], 16, False)
-            L.check(lib.bpx_conv1x1_fwd(self.dt, B, vox0, L.tview(feat), wp16.data_ptr(), b16.data_ptr(), L.NULL_T, L.NULL_T, None, L.NULL_T, L.tview(o16), st))
-            eye = torch.eye(n_out, 16, dtype=torch.float32, device=dev).contiguous()
-            zb = torch.zeros((n_out,), dtype=torch.float32, device=dev)
-            L.check(lib.bpx_head_fwd(self.dt, vox0, B, L.tview(o16), eye.data_ptr(), zb.data_ptr(), n_out, head_act, logits.data_ptr(), n_out * vox0, vox0, st))
-            wide = dict(o16=o16, w16=w16, eye=eye)
+        logits, wide = self._head_fwd(B, So, feat, hw, hb, head_act, st, dev)
         if cfg.ndim == 2:
-            logits = logits.reshape(B, n_out, So[1], So[2])
+            logits = logits.reshape(B, -1, So[1], So[2])
         ctx = None
         if save:
             ctx = dict(B=B, S=S, So=So, img=img, x_ndhwc=x_ndhwc, blocks=blocks, cat=cat, pools=pools, ups=ups, feat=feat, dec_out=dec_in, hw=hw,
@@ -1069,134 +1155,94 @@ class ResUNetEngine:
         return logits, ctx
 
     # ------------------------------------------------------------------------------------------
-    def _block_bwd(self, P, G, blk: _Blk, B, dOut: L.Tensor, img, st, dx_extra: Optional[L.Tensor] = None, dx_out: Optional[L.Tensor] = None,
-                   r1_done: bool = False):
+    def _block_bwd(self, P, G, blk: _Blk, B, dOut: L.Tensor, img, st, dx_out=None, r1_done: bool = False):
         """Backward of one residual block.  dOut: gradient of the block output (T, NDHWC view).
-        Writes parameter grads into G; writes the input gradient into dx_out (a view with blk.cin channels).  r1_done: the first block's
-        shortcut weight gradient was formed by bpx_maxpool3d_bwd_r1, the pass that wrote dOut (see _backward)."""
+        Writes parameter grads into G; writes the input gradient into dx_out: a view with blk.cin channels, a decoder block's (up, skip) pair of
+        views, or None when the input needs none.  r1_done: the first block's shortcut weight gradient was formed by bpx_maxpool3d_bwd_r1, the
+        pass that wrote dOut (see _backward)."""
         D, H, W = blk.S
-        k = blk.keys
-        dev = blk.h.device
-        C1 = blk.cout
-        vox = D * H * W
-        T = self.gdtype
-        # conv2 weight/bias grad, shortcut weight grad
-        # both biases add to the same tensor: identical gradients, written by the same reduction
+        k, dev, C1, Cx, vox = blk.keys, blk.h.device, blk.cout, blk.cin, D * H * W
+        first_c1 = blk.first and self.cfg.in_ch == 1
+        hv = L.tview(blk.h)
+        xv = None if first_c1 else L.tview(blk.x, blk.x_c0, Cx)
+        # ---- conv2: weight / bias gradients (both biases add to the same tensor: identical gradients, written by the same reduction) --------------
         dropped = blk.a is not None                      # training-mode dropout: conv2 read the materialised, masked activation blk.a
         fused2 = not dropped and self._bwd_fused_ok(B, blk.S, C1, dOut.C)
         if dropped:
             self._wgrad(B, blk.S, L.tview(blk.a), None, 0, dOut, 3, G[k["w2"]], G[k["b2"]], st, dev, db2=G[k["bsc"]])
         elif not fused2:
-            self._wgrad(B, blk.S, L.tview(blk.h), blk.rec_h, self.act, dOut, 3, G[k["w2"]], G[k["b2"]], st, dev, db2=G[k["bsc"]])
-        # decoder blocks at the large levels (round 6): the shortcut's weight gradient rides along in the pass that forms the block's input gradient
+            self._wgrad(B, blk.S, hv, blk.rec_h, self.act, dOut, 3, G[k["w2"]], G[k["b2"]], st, dev, db2=G[k["bsc"]])
+        # ---- shortcut weight gradient.  Decoder blocks at the large levels: it rides along in the pass that forms the block's input gradient
         # (bpx_conv1x1_fwd_split_wgrad below streams both of its operands anyway); everywhere else it is a launch of its own
         sc_ws = 0
         if (isinstance(dx_out, tuple) and blk.rec_x is not None and self.cfg.gn_groups == 0
-                and dOut.C * 3 == blk.cin and self.dtype != torch.float32):
+                and dOut.C * 3 == Cx and self.dtype != torch.float32):
             # asked with the operands: the kernel's span, pitch and alignment bounds decide too (g0 and coef0 are allocated below, dense)
-            sc_ws = int(lib.bpx_conv1x1_fwd_split_wgrad_query(self.bdt, B, vox, dOut, L.Tensor(None, blk.cin, blk.cin, 0),
-                                                              L.tview(blk.x, blk.x_c0, blk.cin), None, dx_out[0], dx_out[1]))
-        if blk.first and self.cfg.in_ch == 1:
+            sc_ws = int(lib.bpx_conv1x1_fwd_split_wgrad_query(self.bdt, B, vox, dOut, L.Tensor(None, Cx, Cx, 0), xv, None, dx_out[0], dx_out[1]))
+        if first_c1:
             if not r1_done:
                 ws1 = self._workspace(lib.bpx_conv1x1_c1_wgrad_workspace(C1), dev)
                 L.check(lib.bpx_conv1x1_c1_wgrad(self.gdt, B * vox, img.data_ptr(), dOut, G[k["wsc"]].data_ptr(), ws1.data_ptr(), ws1.numel(), st))
         elif not sc_ws:
-            self._wgrad(B, blk.S, L.tview(blk.x, blk.x_c0, blk.cin), None, 0, dOut, 1, G[k["wsc"]], None, st, dev)
-        # conv2 dgrad fused with ELU' and the InstanceNorm reductions
-        g1 = torch.empty((B, D, H, W, C1), dtype=T, device=dev)
+            self._wgrad(B, blk.S, xv, None, 0, dOut, 1, G[k["wsc"]], None, st, dev)
+        # ---- conv2: input gradient, times act' (and the dropout mask), with the reduction partials of the h norm ---------------------------------
+        g1 = torch.empty((B, D, H, W, C1), dtype=self.gdtype, device=dev)
         self._keep.append(g1)
+        gv = L.tview(g1)
         w2t = self._pack(P[k["w2"]], L.PK_K3_T, C1, C1, False)
         if dropped:   # plain dgrad -> gradient of the masked activation; then mask, activation derivative and the IN-backward sums in one pass
-            L.check(lib.bpx_conv3d_dgrad(self.gdt, B, D, H, W, dOut, w2t.data_ptr(), L.NULL_T, None, 0, L.tview(g1), None, st))
+            L.check(lib.bpx_conv3d_dgrad(self.gdt, B, D, H, W, dOut, w2t.data_ptr(), L.NULL_T, None, 0, gv, None, st))
             tiles = lib.bpx_norm_act_dropout_tiles(self.gdt, vox, C1)
             red = torch.empty((B, tiles, 2, C1), dtype=torch.float32, device=dev)
             mptr, mmode = self._drop_mask(blk, g1.numel(), dev)
-            L.check(lib.bpx_norm_act_dropout_bwd(self.bdt, B, vox, L.tview(g1), L.tview(blk.h), blk.rec_h.data_ptr(), self.act, blk.drop_p, self.drop_seed,
-                                                 blk.drop_ctr.data_ptr(), blk.site, mptr, 1 if mmode else 0, L.tview(g1), red.data_ptr(), st))
-        elif fused2:   # dgrad + wgrad of conv2 in one pass over (dOut, h)
-            tiles, red = self._bwd_fused(B, blk.S, dOut, w2t, L.tview(blk.h), blk.rec_h, L.tview(g1), G[k["w2"]], G[k["b2"]], G[k["bsc"]], st, dev)
+            L.check(lib.bpx_norm_act_dropout_bwd(self.bdt, B, vox, gv, hv, blk.rec_h.data_ptr(), self.act, blk.drop_p, self.drop_seed,
+                                                 blk.drop_ctr.data_ptr(), blk.site, mptr, 1 if mmode else 0, gv, red.data_ptr(), st))
         else:
-            tiles = lib.bpx_conv3d_stats_tiles(self.dt, B, D, H, W, C1)
-            red = torch.empty((B, tiles, 2, C1), dtype=torch.float32, device=dev)
-            L.check(lib.bpx_conv3d_dgrad(self.bdt, B, D, H, W, dOut, w2t.data_ptr(), L.tview(blk.h), blk.rec_h.data_ptr(), self.act,
-                                         L.tview(g1), red.data_ptr(), st))
-        coef = torch.empty((B, C1, 4), dtype=torch.float32, device=dev)
-        # (deferred form: dgamma / dbeta arrive with the flush of the weight-gradient reductions; `red` holds their per-sample terms until then)
-        self._keep.append(red)
-        if self.bn:
-            L.check(lib.bpx_batchnorm_bwd_finalize(red.data_ptr(), B, tiles, C1, vox, blk.rec_h.data_ptr(), P[k["g1"]].data_ptr(), G[k["g1"]].data_ptr(),
-                                                   G[k["be1"]].data_ptr(), self._bn_running, coef.data_ptr(), st))
-        else:
-            L.check(lib.bpx_norm_bwd_finalize_deferred(red.data_ptr(), B, tiles, C1, vox, blk.rec_h.data_ptr(), P[k["g1"]].data_ptr(),
-                                                       G[k["g1"]].data_ptr(), G[k["be1"]].data_ptr(), self.cfg.gn_groups or C1, coef.data_ptr(), st))
-        first_c1 = blk.first and self.cfg.in_ch == 1
-        if first_c1 and lib.bpx_conv3d_c1_wgrad_nb_supported(self.bdt, W):
-            # the first layer has no input gradient: its weight gradient is the only reader of dH = a * g1 + b * h + c0, which is therefore formed
-            # inside that kernel and never stored (bpx_norm_bwd_apply's pass over three tensor units is gone)
-            wsc = self._workspace(lib.bpx_conv3d_c1_wgrad_workspace(C1), dev)
-            self._keep.append(coef)
-            L.check(lib.bpx_conv3d_c1_wgrad_nb(self.bdt, B, D, H, W, img.data_ptr(), L.tview(g1), L.tview(blk.h), coef.data_ptr(),
-                                               G[k["w1"]].data_ptr(), G[k["b1"]].data_ptr(), wsc.data_ptr(), wsc.numel(), st))
-            self._keep.append(g1)
-            return
-        L.check(lib.bpx_norm_bwd_apply(self.bdt, B, vox, L.tview(g1), L.tview(blk.h), coef.data_ptr(), L.NULL_T, L.tview(g1), st))
-        dH = L.tview(g1)
-        # conv1
+            tiles, red = self._dgrad_prologue(B, blk.S, dOut, w2t, hv, blk.rec_h, self.act, gv, st, fused=fused2,
+                                              dw=G[k["w2"]], db=G[k["b2"]], db2=G[k["bsc"]])
+        coef = self._norm_bwd_coef(red, B, tiles, C1, vox, blk.rec_h, P[k["g1"]], G[k["g1"]], G[k["be1"]], st, deferred=True)
+        # ---- dH = a * g1 + b * h + c0 in place; the first layer (no input gradient) leaves with its weight gradient ----------------------------
         if first_c1:
+            # where the kernel takes the width, dH is formed inside the weight-gradient kernel, its only reader, and never stored
+            nb = lib.bpx_conv3d_c1_wgrad_nb_supported(self.bdt, W)
+            if not nb:
+                L.check(lib.bpx_norm_bwd_apply(self.bdt, B, vox, gv, hv, coef.data_ptr(), L.NULL_T, gv, st))
             wsc = self._workspace(lib.bpx_conv3d_c1_wgrad_workspace(C1), dev)
-            L.check(lib.bpx_conv3d_c1_wgrad(self.gdt, B, D, H, W, img.data_ptr(), dH, G[k["w1"]].data_ptr(), G[k["b1"]].data_ptr(),
-                                            wsc.data_ptr(), wsc.numel(), st))
-            self._keep.append(g1)
+            if nb:
+                self._keep.append(coef)
+                L.check(lib.bpx_conv3d_c1_wgrad_nb(self.bdt, B, D, H, W, img.data_ptr(), gv, hv, coef.data_ptr(), G[k["w1"]].data_ptr(),
+                                                   G[k["b1"]].data_ptr(), wsc.data_ptr(), wsc.numel(), st))
+            else:
+                L.check(lib.bpx_conv3d_c1_wgrad(self.gdt, B, D, H, W, img.data_ptr(), gv, G[k["w1"]].data_ptr(), G[k["b1"]].data_ptr(),
+                                                wsc.data_ptr(), wsc.numel(), st))
             return
-        xv = L.tview(blk.x, blk.x_c0, blk.cin)
+        L.check(lib.bpx_norm_bwd_apply(self.bdt, B, vox, gv, hv, coef.data_ptr(), L.NULL_T, gv, st))
+        # ---- conv1: weight / bias gradients; with a wanted dx the input gradient g0 and the reduction partials of the x norm -------------------
         has_norm = blk.rec_x is not None
-        Cx = blk.cin
         fused1 = has_norm and dx_out is not None and self._bwd_fused_ok(B, blk.S, Cx, C1)
         if not fused1:
-            self._wgrad(B, blk.S, xv, blk.rec_x, self.act if has_norm else 0, dH, 3, G[k["w1"]], G[k["b1"]], st, dev)
+            self._wgrad(B, blk.S, xv, blk.rec_x, self.act if has_norm else 0, gv, 3, G[k["w1"]], G[k["b1"]], st, dev)
         if dx_out is None:
             return
-        g0 = torch.empty((B, D, H, W, Cx), dtype=T, device=dev)
-        tiles0 = lib.bpx_conv3d_stats_tiles(self.dt, B, D, H, W, Cx)
+        g0 = torch.empty((B, D, H, W, Cx), dtype=self.gdtype, device=dev)
         w1t = self._pack(P[k["w1"]], L.PK_K3_T, Cx, C1, False)
         wsct = self._pack(P[k["wsc"]], L.PK_DENSE_T, Cx, C1, False)
-        if has_norm:
-            if fused1:   # dgrad + wgrad of conv1 in one pass over (dH, x)
-                tiles0, red0 = self._bwd_fused(B, blk.S, dH, w1t, xv, blk.rec_x, L.tview(g0), G[k["w1"]], G[k["b1"]], None, st, dev)
-            else:
-                red0 = torch.empty((B, tiles0, 2, Cx), dtype=torch.float32, device=dev)
-                L.check(lib.bpx_conv3d_dgrad(self.bdt, B, D, H, W, dH, w1t.data_ptr(), xv, blk.rec_x.data_ptr(), self.act, L.tview(g0),
-                                             red0.data_ptr(), st))
-            coef0 = torch.empty((B, Cx, 4), dtype=torch.float32, device=dev)
-            gng = self.cfg.gn_groups
-            if self.bn:
-                L.check(lib.bpx_batchnorm_bwd_finalize(red0.data_ptr(), B, tiles0, Cx, vox, blk.rec_x.data_ptr(), P[k["g0"]].data_ptr(), G[k["g0"]].data_ptr(),
-                                                       G[k["be0"]].data_ptr(), self._bn_running, coef0.data_ptr(), st))
-            elif gng and (Cx // gng) not in (1, 2, 4, 8, 16, 32, 64):
-                # the concatenated decoder input: 6 / 12 / 24 / 48 channels per group -> per-channel totals, then the general group kernel
-                sums0 = torch.empty((B, Cx, 2), dtype=torch.float64, device=dev)
-                L.check(lib.bpx_norm_channel_sums(red0.data_ptr(), B, tiles0, Cx, sums0.data_ptr(), Cx, 0, st))
-                L.check(lib.bpx_groupnorm_bwd_finalize(sums0.data_ptr(), B, Cx, vox, blk.rec_x.data_ptr(), P[k["g0"]].data_ptr(), G[k["g0"]].data_ptr(),
-                                                       G[k["be0"]].data_ptr(), gng, coef0.data_ptr(), st))
-            else:
-                self._keep.append(red0)
-                L.check(lib.bpx_norm_bwd_finalize_deferred(red0.data_ptr(), B, tiles0, Cx, vox, blk.rec_x.data_ptr(), P[k["g0"]].data_ptr(),
-                                                           G[k["g0"]].data_ptr(), G[k["be0"]].data_ptr(), gng or Cx, coef0.data_ptr(), st))
-            if isinstance(dx_out, tuple):   # decoder block: the gradient of the concatenated input leaves as its (up, skip) parts
-                assert dx_extra is None
-                if sc_ws:
-                    wsw = self._workspace(sc_ws, dev)
-                    L.check(lib.bpx_conv1x1_fwd_split_wgrad(self.bdt, B, vox, dOut, wsct.data_ptr(), L.tview(g0), xv, coef0.data_ptr(), dx_out[0], dx_out[1],
-                                                            G[k["wsc"]].data_ptr(), wsw.data_ptr(), wsw.numel(), st))
-                else:
-                    L.check(lib.bpx_conv1x1_fwd_split(self.bdt, B, vox, dOut, wsct.data_ptr(), None, L.tview(g0), xv, coef0.data_ptr(),
-                                                      L.NULL_T, dx_out[0], dx_out[1], st))
-            else:
-                L.check(lib.bpx_conv1x1_fwd(self.bdt, B, vox, dOut, wsct.data_ptr(), None, L.tview(g0), xv, coef0.data_ptr(),
-                                            dx_extra if dx_extra is not None else L.NULL_T, dx_out, st))
-        else:
-            L.check(lib.bpx_conv3d_dgrad(self.gdt, B, D, H, W, dH, w1t.data_ptr(), L.NULL_T, None, 0, L.tview(g0), None, st))
+        if not has_norm:      # a first block that reads a dense tensor (16 channels and up): dx = dgrad + shortcut, no norm in between
+            L.check(lib.bpx_conv3d_dgrad(self.gdt, B, D, H, W, gv, w1t.data_ptr(), L.NULL_T, None, 0, L.tview(g0), None, st))
             L.check(lib.bpx_conv1x1_fwd(self.gdt, B, vox, dOut, wsct.data_ptr(), None, L.NULL_T, L.NULL_T, None, L.tview(g0), dx_out, st))
+            return
+        tiles0, red0 = self._dgrad_prologue(B, blk.S, gv, w1t, xv, blk.rec_x, self.act, L.tview(g0), st, fused=fused1, dw=G[k["w1"]], db=G[k["b1"]])
+        coef0 = self._norm_bwd_coef(red0, B, tiles0, Cx, vox, blk.rec_x, P[k["g0"]], G[k["g0"]], G[k["be0"]], st, deferred=True)
+        # ---- hand-over: dx = a0 * g0 + b0 * x + c0 + shortcut^T dOut in one pointwise pass; a decoder block's leaves as its (up, skip) parts ----
+        if not isinstance(dx_out, tuple):
+            L.check(lib.bpx_conv1x1_fwd(self.bdt, B, vox, dOut, wsct.data_ptr(), None, L.tview(g0), xv, coef0.data_ptr(), L.NULL_T, dx_out, st))
+        elif sc_ws:
+            wsw = self._workspace(sc_ws, dev)
+            L.check(lib.bpx_conv1x1_fwd_split_wgrad(self.bdt, B, vox, dOut, wsct.data_ptr(), L.tview(g0), xv, coef0.data_ptr(), dx_out[0], dx_out[1],
+                                                    G[k["wsc"]].data_ptr(), wsw.data_ptr(), wsw.numel(), st))
+        else:
+            L.check(lib.bpx_conv1x1_fwd_split(self.bdt, B, vox, dOut, wsct.data_ptr(), None, L.tview(g0), xv, coef0.data_ptr(),
+                                              L.NULL_T, dx_out[0], dx_out[1], st))
 
     def backward(self, P: Dict[str, torch.Tensor], ctx, dlogits: torch.Tensor, on_last_block=None) -> Dict[str, torch.Tensor]:
         """``on_last_block``: called (no arguments) right before the backward of the FIRST encoder block - the last stretch of the pass.  At that
@@ -1233,70 +1279,25 @@ class ResUNetEngine:
         T = self.gdtype
         G = self._grad_slab(P, dev)
         # ---- head -------------------------------------------------------------------------------
-        n_out = sum(cfg.out_channels)
-        D0, H0, W0 = S[0]
-        So = ctx.get("So", S[0])
-        vox0 = So[0] * So[1] * So[2]
-        dl = dlogits.contiguous().float()
-        dfeat = torch.empty((B,) + tuple(So) + (fm[0],), dtype=T, device=dev)
-        wide = ctx.get("wide_head")
-        if wide is None:
-            self._head_bwd(G, B, vox0, L.tview(feat), ctx["hw"], dl, L.tview(dfeat), st, dev)
-        else:
-            # wide head (forward above): the head kernel's backward on the 16-channel tensor gives its gradient (the identity pick's own gradients are
-            # discarded), then the 1x1x1 convolution's two gradients: k = 1 wgrad (rows 0 .. n_out of the padded matrix are the heads') and the
-            # pointwise GEMM with the transposed matrix.  The weight gradient is reduced right away (not with the step's batch): its heads' rows are copied out at once.
-            do16 = torch.empty((B,) + tuple(So) + (16,), dtype=T, device=dev)
-            eg, ebg = torch.zeros((n_out, 16), dtype=torch.float32, device=dev), torch.zeros((n_out,), dtype=torch.float32, device=dev)
-            hws = self._workspace(lib.bpx_head_bwd_workspace(16, n_out), dev)
-            L.check(lib.bpx_head_bwd(self.bdt, vox0, B, L.tview(wide["o16"]), wide["eye"].data_ptr(), n_out, dl.data_ptr(), n_out * vox0, vox0,
-                                     L.tview(do16), eg.data_ptr(), ebg.data_ptr(), hws.data_ptr(), hws.numel(), st))
-            dw16 = torch.zeros((16, fm[0], 1, 1, 1), dtype=torch.float32, device=dev)
-            db16 = torch.zeros((16,), dtype=torch.float32, device=dev)
-            ws16 = self._workspace(lib.bpx_conv3d_wgrad_workspace(B, So[0], So[1], So[2], fm[0], 16, 1), dev)
-            L.check(lib.bpx_conv3d_wgrad_db2(self.bdt, B, So[0], So[1], So[2], L.tview(feat), None, 0, L.tview(do16), 1, dw16.data_ptr(), db16.data_ptr(), None,
-                                             ws16.data_ptr(), ws16.numel(), st))
-            L.check(lib.bpx_wgrad_defer_flush(L.stream_ptr()))
-            L.check(lib.bpx_wgrad_defer_begin())
-            self._split_heads(G, dw16.view(16, fm[0])[:n_out], db16[:n_out])
-            wt16 = self._pack(wide["w16"], L.PK_DENSE_T, fm[0], 16, False)
-            L.check(lib.bpx_conv1x1_fwd(self.gdt, B, vox0, L.tview(do16), wt16.data_ptr(), None, L.NULL_T, L.NULL_T, None, L.NULL_T, L.tview(dfeat), st))
-            self._keep += [do16, dw16, db16, eg, ebg]
+        So = tuple(ctx.get("So", S[0]))
+        dfeat = torch.empty((B,) + So + (fm[0],), dtype=T, device=dev)
+        self._head_bwd(G, B, So, L.tview(feat), ctx["hw"], dlogits.contiguous().float(), L.tview(dfeat), st, dev, wide=ctx.get("wide_head"))
+        self._keep.append(dfeat)
         if cfg.post_up:
-            dec_out, dup_feat = ctx["dec_out"], dfeat
-            wsn = lib.bpx_convT3d_k2s2_wgrad_workspace(B, D0, H0, W0, cfg.post_up, fm[0], fm[0])
-            ws = self._workspace(wsn, dev)
-            dfeat = torch.empty((B, D0, H0, W0, fm[0]), dtype=T, device=dev)
-            wt = self._pack(P["post_upsampling.weight"], L.PK_CT_T if cfg.post_up == 2 else L.PK_CT4_T, fm[0], fm[0], False)
-            L.check(lib.bpx_convT3d_k2s2_bwd(self.bdt, B, D0, H0, W0, cfg.post_up, L.tview(dec_out), L.tview(dup_feat), wt.data_ptr(), L.tview(dfeat),
-                                             G["post_upsampling.weight"].data_ptr(), G["post_upsampling.bias"].data_ptr(), ws.data_ptr(), ws.numel(), st))
-            self._keep.append(dup_feat)
+            dfeat = self._convT_bwd(P, G, B, S[0], cfg.post_up, ctx["dec_out"], dfeat, "post_upsampling.weight", "post_upsampling.bias", fm[0], fm[0], st, dev)
         # ---- decoder (blocks list: enc 0..Lv-1, bottleneck, dec j=0..Lv-1 for levels Lv-1..0) -------
         dskip: List[Optional[torch.Tensor]] = [None] * Lv      # d(concat) leaves the decoder block as two dense tensors
-        dOut = L.tview(dfeat)
-        keep = [dfeat]
+        dOut = dfeat
         for j in range(Lv - 1, -1, -1):       # decoder block j handles level i = Lv-1-j; walk from level 0 up
             i = Lv - 1 - j
-            blk = blocks[Lv + 1 + j]
             wk, bk, x_in, Cup, Sl, szl = ups[j]
             dup = torch.empty((B,) + S[i] + (Cup,), dtype=T, device=dev)
             dskip[i] = torch.empty((B,) + S[i] + (fm[i],), dtype=T, device=dev)
-            self._block_bwd(P, G, blk, B, dOut, img, st, None, (L.tview(dup), L.tview(dskip[i])))
-            # transposed conv backward
-            keep.append(dup)
-            dUp = L.tview(dup)
-            wsn = lib.bpx_convT3d_k2s2_wgrad_workspace(B, Sl[0], Sl[1], Sl[2], szl, Cup, Cup)
-            ws = self._workspace(wsn, dev)
-            dxin = torch.empty((B,) + Sl + (Cup,), dtype=T, device=dev)
-            wt = self._pack(P[wk], L.PK_CT_T if szl == 2 else L.PK_CT4_T, Cup, Cup, False)
-            # dW, db and dx_in; at the 32 -> 32 level of a large volume from ONE pass over dUp (wgrad_ct_kernel<.., DG>), else the two kernels
-            L.check(lib.bpx_convT3d_k2s2_bwd(self.bdt, B, Sl[0], Sl[1], Sl[2], szl, L.tview(x_in), dUp, wt.data_ptr(), L.tview(dxin),
-                                             G[wk].data_ptr(), G[bk].data_ptr(), ws.data_ptr(), ws.numel(), st))
-            dOut = L.tview(dxin)
-            keep.append(dxin)
+            self._block_bwd(P, G, blocks[Lv + 1 + j], B, L.tview(dOut), img, st, (L.tview(dup), L.tview(dskip[i])))
+            dOut = self._convT_bwd(P, G, B, Sl, szl, x_in, dup, wk, bk, Cup, Cup, st, dev)
         # ---- bottleneck -------------------------------------------------------------------------
         dP = torch.empty((B,) + S[Lv] + (fm[Lv - 1],), dtype=T, device=dev)
-        self._block_bwd(P, G, blocks[Lv], B, dOut, img, st, None, L.tview(dP))
+        self._block_bwd(P, G, blocks[Lv], B, L.tview(dOut), img, st, L.tview(dP))
         # ---- encoder ------------------------------------------------------------------------------
         for i in range(Lv - 1, -1, -1):
             D, H, W = S[i]
@@ -1320,13 +1321,13 @@ class ResUNetEngine:
                 on_last_block()
             if i > 0:
                 dPn = torch.empty((B,) + S[i] + (fm[i - 1],), dtype=T, device=dev)
-                self._block_bwd(P, G, blocks[i], B, skipv, img, st, None, L.tview(dPn))
-                keep.append(dP)
+                self._block_bwd(P, G, blocks[i], B, skipv, img, st, L.tview(dPn))
+                self._keep.append(dP)
                 dP = dPn
             elif ctx.get("want_dx"):
                 dx0 = torch.empty((B,) + S[0] + (cfg.in_ch,), dtype=T, device=dev)
-                self._block_bwd(P, G, blocks[0], B, skipv, img, st, None, L.tview(dx0), r1_done=bool(r1_ws))
+                self._block_bwd(P, G, blocks[0], B, skipv, img, st, L.tview(dx0), r1_done=bool(r1_ws))
                 G["__dx__"] = dx0
             else:
-                self._block_bwd(P, G, blocks[0], B, skipv, img, st, None, None, r1_done=bool(r1_ws))  # the image needs no gradient
+                self._block_bwd(P, G, blocks[0], B, skipv, img, st, None, r1_done=bool(r1_ws))  # the image needs no gradient
         return G

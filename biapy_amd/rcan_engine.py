@@ -32,7 +32,6 @@ from .engine import NetConfig, ResUNetEngine, _Stats
 lib = L.lib
 
 
-
 # ---- x scale stage: orders of the 16 s^3 conv channels (pure tensor algebra, checked on the CPU against autograd through the oracle's pixel_shuffle3d) ----
 def rows_to_subposition_major(w: torch.Tensor, b: torch.Tensor, Fc: int, s3: int):
     """PyTorch's pixel-shuffle channel order [channel][sub-position] -> the kernels' [sub-position][channel] (weight rows and bias alike)."""
@@ -159,10 +158,8 @@ class RCANEngine(ResUNetEngine):
         b2p[: self.n_out] = P["conv2.bias"]
         o16 = buf(16)
         self._conv(B, S, t, None, 0, w2p, b2p, o16)
-        hw = torch.eye(self.n_out, 16, dtype=torch.float32, device=dev).contiguous()
-        hb = torch.zeros(self.n_out, dtype=torch.float32, device=dev)
         y = torch.empty((B, self.n_out, D, H, W), dtype=torch.float32, device=dev)
-        L.check(lib.bpx_head_fwd(self.dt, vox, B, L.tview(o16), hw.data_ptr(), hb.data_ptr(), self.n_out, head_act, y.data_ptr(), self.n_out * vox, vox, st))
+        hw = self._pick16_fwd(B, vox, o16, self.n_out, head_act, y, st)
         ctx = dict(B=B, S=S, img=img, f0=f0, groups=groups, last=cur, t=t, o16=o16, w2p=w2p, hw=hw, head_act=head_act, low=low if self.scale else None) if save else None
         return y, ctx
 
@@ -198,13 +195,7 @@ class RCANEngine(ResUNetEngine):
                 return o
 
             # head (linear): gradient of the padded 16-channel tensor
-            do16 = buf(16)
-            hwg = torch.zeros((self.n_out, 16), dtype=torch.float32, device=dev)
-            hbg = torch.zeros((self.n_out,), dtype=torch.float32, device=dev)
-            dl = dy_out.contiguous().float()
-            hws = self._workspace(lib.bpx_head_bwd_workspace(16, self.n_out), dev)
-            L.check(lib.bpx_head_bwd(self.bdt, vox, B, L.tview(ctx["o16"]), ctx["hw"].data_ptr(), self.n_out, dl.data_ptr(), self.n_out * vox, vox,
-                                     L.tview(do16), hwg.data_ptr(), hbg.data_ptr(), hws.data_ptr(), hws.numel(), st))
+            do16 = self._pick16_bwd(B, vox, ctx["o16"], ctx["hw"], self.n_out, dy_out.contiguous().float(), st, dev)
             dw16 = torch.zeros((16, Fc, 3, 3, 3), dtype=torch.float32, device=dev)
             db16 = torch.zeros(16, dtype=torch.float32, device=dev)
             wgrad(ctx["t"], None, 0, do16, dw16, db16)

@@ -160,15 +160,10 @@ class ResUNetPPEngine(ResUNetEngine):
         L.check(lib.bpx_tensor_stats(self.dt, self._B, v.vox, v.view(), part.data_ptr(), self._st))
         return part, tiles
 
-    def _finalize(self, part, tiles, C, vox, gamma, beta, rec=None, rec_ld=None, rec_off=0):
-        if rec is None:
-            rec = _recs(self._B, C, self._dev)
-        _Stats.finalize(part, self._B, tiles, C, vox, gamma, beta, rec, C if rec_ld is None else rec_ld, rec_off, self._st)
-        return rec
-
-    def _stats_rec(self, v: _V, gamma, beta):
+    def _stats_rec(self, v: _V, layer: str):
+        """Records of norm layer `layer` on a materialised tensor."""
         part, tiles = self._tensor_part(v)
-        return self._finalize(part, tiles, v.C, v.vox, gamma, beta)
+        return self._norm_records(self._P, layer, part, tiles, v.C, v.vox, self._st)
 
     def _in_bwd(self, raw: _V, rec, act, dA: torch.Tensor, gamma, dgamma, dbeta) -> torch.Tensor:
         """Backward of a materialised ``act(IN(raw))``: dA (dense) -> d(raw)."""
@@ -206,18 +201,11 @@ class ResUNetPPEngine(ResUNetEngine):
                     self._wgrad(B, x.S, x.view(), nrm.rec if nrm else None, nrm.act if nrm else 0, dy, 3, G[wk], G[bk], self._st, self._dev)
                 wt = self._pack(P[wk], L.PK_K3_T, x.C, Cout, False)
                 g = torch.empty((B, D, H, W, x.C), dtype=self.gdtype, device=self._dev)
-                if fused:
-                    # round 5 (first part): dgrad (+ act', + IN-backward sums) and wgrad (+ bias gradient) of the conv in ONE pass
-                    # over (dy, x) - the level-0 / level-1 shapes the cfg-2 engine fuses too (bpx_conv3d_bwd_fused_supported)
-                    rt, red = self._bwd_fused(B, x.S, dy, wt, x.view(), nrm.rec, L.tview(g), G[wk], G[bk], None, self._st, self._dev, nrm.act)
-                elif nrm is not None:
-                    rt = lib.bpx_conv3d_stats_tiles(self.dt, B, D, H, W, x.C)
-                    red = torch.empty((B, rt, 2, x.C), dtype=torch.float32, device=self._dev)
-                    L.check(lib.bpx_conv3d_dgrad(self.bdt, B, D, H, W, dy, wt.data_ptr(), x.view(), nrm.rec.data_ptr(), nrm.act, L.tview(g), red.data_ptr(), self._st))
                 if nrm is not None:
-                    coef = torch.empty((B, x.C, 4), dtype=torch.float32, device=self._dev)
-                    L.check(lib.bpx_norm_bwd_finalize(red.data_ptr(), B, rt, x.C, x.vox, nrm.rec.data_ptr(), nrm.gamma.data_ptr(), L.ptr(nrm.dgamma),
-                                                      L.ptr(nrm.dbeta), x.C, coef.data_ptr(), self._st))
+                    # fused (round 5): dgrad (+ act', + IN-backward sums) and wgrad (+ bias gradient) of the conv in ONE pass over (dy, x) - the
+                    # level-0 / level-1 shapes the cfg-2 engine fuses too (bpx_conv3d_bwd_fused_supported)
+                    rt, red = self._dgrad_prologue(B, x.S, dy, wt, x.view(), nrm.rec, nrm.act, L.tview(g), self._st, fused=fused, dw=G[wk], db=G[bk])
+                    coef = self._norm_bwd_coef(red, B, rt, x.C, x.vox, nrm.rec, nrm.gamma, nrm.dgamma, nrm.dbeta, self._st, deferred=False)
                     add, dst, fresh = self._acc_target(x)             # the InstanceNorm-backward affine adds to the gradient x already has
                     L.check(lib.bpx_norm_bwd_apply(self.bdt, B, x.vox, L.tview(g), x.view(), coef.data_ptr(), add, L.tview(dst), self._st))
                     if fresh:
@@ -273,10 +261,10 @@ class ResUNetPPEngine(ResUNetEngine):
             nrm = _Nrm(rec_x, self.act, P[g0], G[g0] if G is not None else None, G[b0] if G is not None else None)
             h, part, tiles = self._conv3(x, f"{k1}.0.weight", f"{k1}.0.bias", Cout, nrm)
             s, spart, stiles = self._conv3(x, f"{prefix}.shortcut.0.weight", f"{prefix}.shortcut.0.bias", Cout)
-        rec_h = self._finalize(part, tiles, Cout, vox, P[f"{k1}.1.weight"], P[f"{k1}.1.bias"])
+        rec_h = self._norm_records(P, f"{k1}.1", part, tiles, Cout, vox, self._st)
         nrm_h = _Nrm(rec_h, self.act, P[f"{k1}.1.weight"], G[f"{k1}.1.weight"] if G is not None else None, G[f"{k1}.1.bias"] if G is not None else None)
         main, _, _ = self._conv3(h, f"{k2}.0.weight", f"{k2}.0.bias", Cout, nrm_h, want_stats=False)
-        rec_s = self._finalize(spart, stiles, Cout, vox, P[f"{prefix}.shortcut.1.weight"], P[f"{prefix}.shortcut.1.bias"])
+        rec_s = self._norm_records(P, f"{prefix}.shortcut.1", spart, stiles, Cout, vox, self._st)
         return self._add_in(main, s, rec_s, f"{prefix}.shortcut.1.weight", f"{prefix}.shortcut.1.bias")
 
     def _sqex(self, x: _V, prefix: str) -> _V:
@@ -365,7 +353,7 @@ class ResUNetPPEngine(ResUNetEngine):
                                             L.NULL_T, L.NULL_T, None, L.NULL_T, raw.view(), self._st))
                 r = self._new(x.S, Cout)
                 L.check(lib.bpx_norm_act_fwd(self.dt, B, x.vox, raw.view(), self._ident_rec(Cout).data_ptr(), self.relu, r.view(), self._st))
-                rec = self._stats_rec(r, P[gk], P[bek])
+                rec = self._stats_rec(r, gk[:-len(".weight")])
                 L.check(lib.bpx_norm_act_fwd(self.dt, B, x.vox, r.view(), rec.data_ptr(), 0, L.tview(cat.buf, j * Cout, Cout), self._st))
                 branches.append((0, wc, None, raw, r, rec, wk, bk, gk, bek))
                 continue
@@ -380,7 +368,7 @@ class ResUNetPPEngine(ResUNetEngine):
             raw = _V(dilation.packed_to_space(ys.buf, d, x.S, tables), x.S)
             r = self._new(x.S, Cout)
             L.check(lib.bpx_norm_act_fwd(self.dt, B, x.vox, raw.view(), self._ident_rec(Cout).data_ptr(), self.relu, r.view(), self._st))
-            rec = self._stats_rec(r, P[gk], P[bek])
+            rec = self._stats_rec(r, gk[:-len(".weight")])
             L.check(lib.bpx_norm_act_fwd(self.dt, B, x.vox, r.view(), rec.data_ptr(), 0, L.tview(cat.buf, j * Cout, Cout), self._st))
             branches.append((d, tables, xsv, raw, r, rec, wk, bk, gk, bek))
         if G is not None:
@@ -431,7 +419,7 @@ class ResUNetPPEngine(ResUNetEngine):
 
         def nrm_of(v, name):
             gk, bk = f"{prefix}.{name}.0.weight", f"{prefix}.{name}.0.bias"
-            return _Nrm(self._stats_rec(v, P[gk], P[bk]), self.relu, P[gk], G[gk] if G is not None else None, G[bk] if G is not None else None)
+            return _Nrm(self._stats_rec(v, f"{prefix}.{name}.0"), self.relu, P[gk], G[gk] if G is not None else None, G[bk] if G is not None else None)
 
         e_full, _, _ = self._conv3(x1, f"{prefix}.conv_encoder.2.weight", f"{prefix}.conv_encoder.2.bias", C, nrm_of(x1, "conv_encoder"), want_stats=False)
         e = self._maxpool(e_full, pool_sz)
@@ -439,7 +427,7 @@ class ResUNetPPEngine(ResUNetEngine):
         sm = self._new(x2.S, C)
         L.check(lib.bpx_channel_affine(self.dt, B, x2.vox, e.view(), d.view(), self._ones_bc(C).data_ptr(), None, sm.view(), self._st))
         gk, bk = f"{prefix}.conv_attn.0.weight", f"{prefix}.conv_attn.0.bias"
-        rec = self._stats_rec(sm, P[gk], P[bk])
+        rec = self._stats_rec(sm, f"{prefix}.conv_attn.0")
         m = self._new(x2.S, C)
         L.check(lib.bpx_norm_act_fwd(self.dt, B, x2.vox, sm.view(), rec.data_ptr(), self.relu, m.view(), self._st))
         if G is not None:
@@ -486,11 +474,10 @@ class ResUNetPPEngine(ResUNetEngine):
         L.check(lib.bpx_convT3d_k2s2_fwd(self.dt, B, Dl, Hl, Wl, sz, x.view(), wp.data_ptr(), P[bk].data_ptr(), L.tview(cat.buf, 0, Cup), upart.data_ptr(), self._st))
         L.check(lib.bpx_norm_act_fwd(self.dt, B, vox, bridge.view(), self._ident_rec(Cb).data_ptr(), 0, L.tview(cat.buf, Cup, Cb), self._st))   # the skip copy
         pre = f"up_paths.0.{j}.conv_block"
-        g0, be0 = P[f"{pre}.block.0.weight"], P[f"{pre}.block.0.bias"]
-        rec = _recs(B, Cup + Cb, self._dev)
-        self._finalize(upart, utiles, Cup, vox, g0[:Cup], be0[:Cup], rec, Cup + Cb, 0)
+        rec = _recs(B, Cup + Cb, self._dev)      # the two column ranges of torch.cat([up, bridge], 1); the bridge's statistics are taken in between
+        self._norm_finalize(P, f"{pre}.block.0", upart, B, utiles, Cup, vox, rec, Cup + Cb, 0, self._st)
         bpart, btiles = self._tensor_part(bridge)
-        self._finalize(bpart, btiles, Cb, vox, g0[Cup:], be0[Cup:], rec, Cup + Cb, Cup)
+        self._norm_finalize(P, f"{pre}.block.0", bpart, B, btiles, Cb, vox, rec, Cup + Cb, Cup, self._st, lo=Cup)
         if G is not None:
             def bwd():                                                 # runs after the residual block's closures: cat.grad is complete
                 dcat = cat.grad
@@ -513,19 +500,12 @@ class ResUNetPPEngine(ResUNetEngine):
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[1] == 1
         B, _, D0, H0, W0 = x.shape
         fm, depth, zd = list(cfg.feature_maps), cfg.depth, cfg.z_down
-        zdiv = 1
-        for v in zd[1:]:
-            zdiv *= v
-        if D0 % zdiv or H0 % (2 ** depth) or W0 % (2 ** depth):
-            raise ValueError(f"patch {D0, H0, W0} must be divisible by {(zdiv, 2 ** depth, 2 ** depth)} (DATA.PATCH_SIZE rule, check_configuration.py:3156-3202)")
+        S = self._level_shapes((D0, H0, W0), zd[1:])
         self._B, self._dev, self._st, self._P = B, x.device, L.stream_ptr(), P
         self._begin_recorded_packs(P, save, x.device, cache_weights)   # one batched weight-pack launch from the second step on
         self._tape: List[Callable[[], None]] = []
         self._G = self._grad_slab(P, x.device) if save else None
         img = x.reshape(B, D0, H0, W0).contiguous()
-        S = [(D0, H0, W0)]
-        for i in range(1, depth + 1):
-            S.append((S[i - 1][0] // zd[i], S[i - 1][1] // 2, S[i - 1][2] // 2))
         # ---------------- encoder (resunet++.py:435-444): level 0 is not pooled, the last level has no SE block ----------------
         blocks: List[_V] = []
         cur: Optional[_V] = None
@@ -534,7 +514,7 @@ class ResUNetPPEngine(ResUNetEngine):
                 cur = self._res_block(None, img, S[0], "down_path.0", True, fm[0])
             else:
                 pre = f"down_path.{i}"
-                rec = self._stats_rec(cur, P[f"{pre}.block.0.weight"], P[f"{pre}.block.0.bias"])
+                rec = self._stats_rec(cur, f"{pre}.block.0")
                 cur = self._res_block(cur, None, cur.S, pre, False, fm[i], rec_x=rec)
             if i < depth:
                 cur = self._sqex(cur, f"sqex_blocks.{i}")
@@ -549,12 +529,8 @@ class ResUNetPPEngine(ResUNetEngine):
             cur = self._up_block(cur, blocks[-j - 2], j, zd[i + 1], fm[i + 1])
         feat = self._aspp(cur, "aspp_out.0", fm[0])
         # ---------------- heads -----------------------------------------------------------------------------------------------
-        n_out = sum(cfg.out_channels)
-        hw = torch.cat([P[f"heads.{h}.weight"].reshape(-1, fm[0]) for h in range(len(cfg.out_channels))], 0).contiguous()
-        hb = torch.cat([P[f"heads.{h}.bias"] for h in range(len(cfg.out_channels))], 0).contiguous()
-        vox0 = D0 * H0 * W0
-        logits = torch.empty((B, n_out, D0, H0, W0), dtype=torch.float32, device=x.device)
-        L.check(lib.bpx_head_fwd(self.dt, vox0, B, feat.view(), hw.data_ptr(), hb.data_ptr(), n_out, head_act, logits.data_ptr(), n_out * vox0, vox0, self._st))
+        hw, hb = self._head_matrix(P)
+        logits, _ = self._head_fwd(B, S[0], feat.buf, hw, hb, head_act, self._st, x.device)
         ctx = None
         if save:
             # the packed operands and the parameter versions they were made from travel with the context: a later forward() replaces the
@@ -578,7 +554,7 @@ class ResUNetPPEngine(ResUNetEngine):
             with self._backward_pass(defer=True):
                 dl = dlogits.contiguous().float()
                 feat.grad = torch.empty((B, D0, H0, W0, cfg.feature_maps[0]), dtype=self.gdtype, device=self._dev)
-                self._head_bwd(G, B, D0 * H0 * W0, feat.view(), ctx["hw"], dl, L.tview(feat.grad), self._st, self._dev)
+                self._head_bwd(G, B, ctx["S0"], feat.view(), ctx["hw"], dl, L.tview(feat.grad), self._st, self._dev)
                 for fn in reversed(ctx["tape"]):
                     fn()
         finally:

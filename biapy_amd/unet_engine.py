@@ -21,10 +21,12 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
+import copy
+
 import torch
 
 from . import _lib as L
-from .engine import NetConfig, ResUNetEngine, _recs, _Stats, lift_params, pad_input_channels, unlift_grads, unpad_input_grads
+from .engine import NetConfig, ResUNetEngine, _Stats, lift_params, pad_input_channels, unlift_grads, unpad_input_grads
 
 lib = L.lib
 
@@ -51,6 +53,11 @@ class UNetEngine(ResUNetEngine):
             raise NotImplementedError("UNetEngine: conv_layers must be 2 at every level")
         self.ndim = ndim
         self.nconvs = nconvs
+        if cfg.gn_groups:
+            # unet.U_Net builds InstanceNorm layers whatever `normalization` names, and this engine has always run them as such: the shared norm
+            # helpers (_norm_records, _norm_bwd_coef) read the group count from the configuration
+            self.cfg = copy.copy(cfg)
+            self.cfg.gn_groups = 0
 
     # ---- parameters: 2D weights are lifted to one-z-slice 3D weights (engine.lift_params); the first convolution of a network whose image is
     # zero-padded to 16 channels (NetConfig.true_in_ch) gets zero input-channel columns (engine.pad_input_channels) ------------------------
@@ -80,9 +87,7 @@ class UNetEngine(ResUNetEngine):
                 wp = self._pack(P[kw], L.PK_K3, ci, cout, False)
                 L.check(lib.bpx_conv3d_fwd(self.dt, B, D, H, W, L.tview(src), L.ptr(src_rec), self.act if src_rec is not None else 0,
                                            wp.data_ptr(), P[kb].data_ptr(), L.NULL_T, None, None, L.tview(h), part.data_ptr(), st))
-            rec = _recs(B, cout, dev)
-            _Stats.finalize(part, B, tiles, cout, vox, P[f"{prefix}.block.{c}.block.1.weight"], P[f"{prefix}.block.{c}.block.1.bias"],
-                            rec, cout, 0, st)
+            rec = self._norm_records(P, f"{prefix}.block.{c}.block.1", part, tiles, cout, vox, st)
             cb.h.append(h)
             cb.rec.append(rec)
             src, src_rec = h, rec
@@ -102,30 +107,12 @@ class UNetEngine(ResUNetEngine):
         assert Cin == (cfg.true_in_ch or cfg.in_ch), f"expected {cfg.true_in_ch or cfg.in_ch} input channels, got {Cin}"
         Lv = cfg.depth
         zd = cfg.z_down if self.ndim == 3 else (1,) * Lv
-        zdiv = 1
-        for v in zd:
-            zdiv *= v
-        if D0 % zdiv or H0 % (2 ** Lv) or W0 % (2 ** Lv):
-            raise ValueError(f"patch {D0, H0, W0} must be divisible by {(zdiv, 2 ** Lv, 2 ** Lv)} (DATA.PATCH_SIZE rule, check_configuration.py:3156-3202)")
+        S = self._level_shapes((D0, H0, W0), zd)
         dev, st, T = x.device, L.stream_ptr(), self.dtype
         fm = list(cfg.feature_maps)
         self._prepacked = {}
         Pw = self._lift(P)
-        if Cin == 1:
-            img, cur = x.reshape(B, D0, H0, W0).contiguous(), None
-        elif cfg.true_in_ch is not None:
-            img, cur = None, self._pack_image16(x, st)
-        else:
-            img = None
-            xin = x.permute(0, 2, 3, 4, 1).contiguous()
-            cur = torch.empty(xin.shape, dtype=T, device=dev)
-            if T == torch.float32:
-                cur.copy_(xin)
-            else:
-                L.check(lib.bpx_cast(L.F32, xin.data_ptr(), self.dt, cur.data_ptr(), xin.numel(), st))
-        S = [(D0, H0, W0)]
-        for i in range(Lv):
-            S.append((S[i][0] // zd[i], S[i][1] // 2, S[i][2] // 2))
+        img, cur = self._ingest(x, None, st)
 
         def buf(i, C):
             return torch.empty((B,) + S[i] + (C,), dtype=T, device=dev)
@@ -158,23 +145,17 @@ class UNetEngine(ResUNetEngine):
             L.check(lib.bpx_convT3d_k2s2_fwd(self.dt, B, Dl, Hl, Wl, zd[i], L.tview(dec_in), wp.data_ptr(), Pw[bk].data_ptr(), L.tview(up_raw),
                                              upart.data_ptr(), st))
             vox = S[i][0] * S[i][1] * S[i][2]
-            urec = _recs(B, Cup, dev)
-            _Stats.finalize(upart, B, utiles, Cup, vox, Pw[f"up_paths.0.{j}.up.1.weight"], Pw[f"up_paths.0.{j}.up.1.bias"], urec, Cup, 0, st)
+            urec = self._norm_records(Pw, f"up_paths.0.{j}.up.1", upart, utiles, Cup, vox, st)
             L.check(lib.bpx_norm_act_fwd(self.dt, B, vox, L.tview(up_raw), urec.data_ptr(), self.act, L.tview(cat[i], 0, Cup), st))
             out = buf(i, fm[i])
             blocks.append(self._conv_block_fwd(Pw, f"up_paths.0.{j}.conv_block", B, S[i], 2 * fm[i], fm[i], cat[i], None, L.tview(out), st, dev))
             ups.append((j, i, dec_in, up_raw, urec))
             dec_in = out
         # ---------------- heads ----------------------------------------------------------------------
-        n_out = sum(cfg.out_channels)
-        hw = torch.cat([Pw[f"heads.{h}.weight"].reshape(-1, fm[0]) for h in range(len(cfg.out_channels))], 0).contiguous()
-        hb = torch.cat([Pw[f"heads.{h}.bias"] for h in range(len(cfg.out_channels))], 0).contiguous()
-        vox0 = D0 * H0 * W0
-        logits = torch.empty((B, n_out, D0, H0, W0), dtype=torch.float32, device=dev)
-        L.check(lib.bpx_head_fwd(self.dt, vox0, B, L.tview(dec_in), hw.data_ptr(), hb.data_ptr(), n_out, head_act, logits.data_ptr(),
-                                 n_out * vox0, vox0, st))
+        hw, hb = self._head_matrix(Pw)
+        logits, _ = self._head_fwd(B, S[0], dec_in, hw, hb, head_act, st, dev)
         if self.ndim == 2:
-            logits = logits.reshape(B, n_out, H0, W0)
+            logits = logits.reshape(B, -1, H0, W0)
         ctx = dict(B=B, S=S, zd=zd, img=img, blocks=blocks, cat=cat, ups=ups, feat=dec_in, hw=hw, Pw=Pw) if save else None
         return logits, ctx
 
@@ -191,14 +172,9 @@ class UNetEngine(ResUNetEngine):
         self._wgrad(B, cb.S, L.tview(cb.h[0]), cb.rec[0], self.act, L.tview(g2), 3, G[k(1, "0.weight")], G[k(1, "0.bias")], st, dev)
         g1 = torch.empty((B, D, H, W, C1), dtype=self.gdtype, device=dev)
         self._keep.append(g1)
-        tiles = lib.bpx_conv3d_stats_tiles(self.dt, B, D, H, W, C1)
-        red = torch.empty((B, tiles, 2, C1), dtype=torch.float32, device=dev)
         w2t = self._pack(Pw[k(1, "0.weight")], L.PK_K3_T, C1, C1, False)
-        L.check(lib.bpx_conv3d_dgrad(self.bdt, B, D, H, W, L.tview(g2), w2t.data_ptr(), L.tview(cb.h[0]), cb.rec[0].data_ptr(), self.act,
-                                     L.tview(g1), red.data_ptr(), st))
-        coef = torch.empty((B, C1, 4), dtype=torch.float32, device=dev)
-        L.check(lib.bpx_norm_bwd_finalize(red.data_ptr(), B, tiles, C1, vox, cb.rec[0].data_ptr(), Pw[k(0, "1.weight")].data_ptr(),
-                                          G[k(0, "1.weight")].data_ptr(), G[k(0, "1.bias")].data_ptr(), C1, coef.data_ptr(), st))
+        tiles, red = self._dgrad_prologue(B, cb.S, L.tview(g2), w2t, L.tview(cb.h[0]), cb.rec[0], self.act, L.tview(g1), st, fused=False)
+        coef = self._norm_bwd_coef(red, B, tiles, C1, vox, cb.rec[0], Pw[k(0, "1.weight")], G[k(0, "1.weight")], G[k(0, "1.bias")], st, deferred=False)
         L.check(lib.bpx_norm_bwd_apply(self.bdt, B, vox, L.tview(g1), L.tview(cb.h[0]), coef.data_ptr(), L.NULL_T, L.tview(g1), st))
         # conv 1
         if img is not None:
@@ -230,31 +206,21 @@ class UNetEngine(ResUNetEngine):
         fm, Lv = list(cfg.feature_maps), cfg.depth
         dev, st, T = dlogits.device, L.stream_ptr(), self.gdtype       # T: storage type of the gradient tensors
         # ---- head -------------------------------------------------------------------------------
-        D0, H0, W0 = S[0]
         dl = dlogits.contiguous().float()
-        dfeat = torch.empty((B, D0, H0, W0, fm[0]), dtype=T, device=dev)
-        self._head_bwd(G, B, D0 * H0 * W0, L.tview(feat), ctx["hw"], dl, L.tview(dfeat), st, dev)
+        dfeat = torch.empty((B,) + S[0] + (fm[0],), dtype=T, device=dev)
+        self._head_bwd(G, B, S[0], L.tview(feat), ctx["hw"], dl, L.tview(dfeat), st, dev)
         # ---- decoder: walk from level 0 down to the bottleneck ---------------------------------------------------------
         dcat: List[Optional[torch.Tensor]] = [None] * Lv
         dA = L.tview(dfeat)
-        keep = [dfeat]
+        self._keep.append(dfeat)
         for j, i, x_low, up_raw, urec in reversed(ups):
             Cl, Cup = fm[i + 1], fm[i]
             dcat[i] = torch.empty((B,) + S[i] + (2 * fm[i],), dtype=T, device=dev)
             self._conv_block_bwd(Pw, G, blocks[Lv + 1 + j], B, dA, None, L.tview(dcat[i]), st, dev)
-            vox = S[i][0] * S[i][1] * S[i][2]
             pre = f"up_paths.0.{j}.up"
             dup = self._norm_act_bwd(up_raw, urec, self.act, L.tview(dcat[i], 0, Cup), Pw[f"{pre}.1.weight"], G[f"{pre}.1.weight"],
                                      G[f"{pre}.1.bias"], st)
-            keep.append(dup)
-            Dl, Hl, Wl = S[i + 1]
-            ws = self._workspace(lib.bpx_convT3d_k2s2_wgrad_workspace(B, Dl, Hl, Wl, zd[i], Cl, Cup), dev)
-            dlow = torch.empty((B, Dl, Hl, Wl, Cl), dtype=T, device=dev)
-            wt = self._pack(Pw[f"{pre}.0.weight"], L.PK_CT_T if zd[i] == 2 else L.PK_CT4_T, Cl, Cup, False)
-            L.check(lib.bpx_convT3d_k2s2_bwd(self.bdt, B, Dl, Hl, Wl, zd[i], L.tview(x_low), L.tview(dup), wt.data_ptr(), L.tview(dlow),
-                                             G[f"{pre}.0.weight"].data_ptr(), G[f"{pre}.0.bias"].data_ptr(), ws.data_ptr(), ws.numel(), st))
-            dA = L.tview(dlow)
-            keep.append(dlow)
+            dA = L.tview(self._convT_bwd(Pw, G, B, S[i + 1], zd[i], x_low, dup, f"{pre}.0.weight", f"{pre}.0.bias", Cl, Cup, st, dev))
         # ---- bottleneck ---------------------------------------------------------------------------------------------
         dP = torch.empty((B,) + S[Lv] + (fm[Lv - 1],), dtype=T, device=dev)
         self._conv_block_bwd(Pw, G, blocks[Lv], B, dA, None, L.tview(dP), st, dev)
@@ -267,7 +233,7 @@ class UNetEngine(ResUNetEngine):
             if i > 0:
                 dPn = torch.empty((B,) + S[i] + (fm[i - 1],), dtype=T, device=dev)
                 self._conv_block_bwd(Pw, G, blocks[i], B, skipv, None, L.tview(dPn), st, dev)
-                keep.append(dP)
+                self._keep.append(dP)
                 dP = dPn
             else:
                 self._conv_block_bwd(Pw, G, blocks[0], B, skipv, img, None, st, dev)   # the image needs no gradient

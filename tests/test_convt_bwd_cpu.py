@@ -34,9 +34,12 @@ def test_entry_is_declared_exported_and_bound():
 
 
 def test_engines_call_the_one_entry():
-    for f in ("engine.py", "unet_engine.py"):
-        src = open(os.path.join(ROOT, "biapy_amd", f)).read()
-        assert "bpx_convT3d_k2s2_bwd(" in src and "bpx_convT3d_k2s2_dgrad(" not in src, f
+    """Both engines run the transposed conv's backward through ResUNetEngine._convT_bwd, the one caller of the entry; neither calls the separate dgrad."""
+    src = {f: open(os.path.join(ROOT, "biapy_amd", f)).read() for f in ("engine.py", "unet_engine.py")}
+    helper = src["engine.py"].split("    def _convT_bwd(", 1)[1].split("\n    def ", 1)[0]
+    assert "bpx_convT3d_k2s2_bwd(" in helper
+    for f, text in src.items():
+        assert "self._convT_bwd(" in text and "bpx_convT3d_k2s2_dgrad(" not in text and "bpx_convT3d_k2s2_wgrad(" not in text, f
 
 
 @pytest.fixture(scope="module")
