@@ -62,6 +62,8 @@ _SIGS = {
     "bpx_aug_mean_blocks": ([_i64], _i),
     "bpx_aug_mean": ([_vp, _i, _i64, _vp, _vp, _vp], _i),
     "bpx_aug_apply": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_uint64, _f, _i, _vp, _vp, _vp], _i),
+    "bpx_warp_draw": ([_vp, _i, _i, _i, _vp, _vp, _vp], _i),
+    "bpx_warp_apply": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp], _i),
     "bpx_patch_draw": ([_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp], _i),
     "bpx_patch_gather": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp], _i),
     "bpx_scan_blocks": ([_i64], _i),
@@ -227,6 +229,13 @@ class AugCfg(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("thr", C.c_uint64), ("enable", C.c_uint32), ("box_lo", C.c_int32), ("box_hi", C.c_int32),
                 ("c_lo", C.c_float), ("c_hi", C.c_float), ("b_lo", C.c_float), ("b_hi", C.c_float), ("s_lo", C.c_float), ("s_hi", C.c_float),
                 ("f_lo", C.c_float), ("f_hi", C.c_float)]
+
+
+class WarpCfg(C.Structure):
+    """bpx_warp_cfg (include/biapy_amd.h)."""
+    _fields_ = [("seed", C.c_uint64), ("thr", C.c_uint64), ("enable", C.c_uint32), ("reserved", C.c_uint32), ("rot_lo", C.c_float),
+                ("rot_hi", C.c_float), ("zoom_lo", C.c_float), ("zoom_hi", C.c_float), ("shear_lo", C.c_float), ("shear_hi", C.c_float),
+                ("shift_lo", C.c_float), ("shift_hi", C.c_float)]
 
 
 class PatchVol(C.Structure):

@@ -7,6 +7,8 @@ PRODUCT'S OWN - **parity-unpinned**: the reference's draws are random, and its e
 
 Per sample every enabled transform fires independently with probability ``da_prob``; the output is defined in this order:
 
+0. affine warp in the (Y, X) plane, identically for every z and channel, when ``rotation`` / ``zoom`` / ``shear`` / ``shift`` are given (the
+   section "The affine warp" below); image bilinear, target nearest;
 1. geometry, image and target alike: ``v = torch.rot90(src, k, dims=(Y, X))`` with ``k`` uniform in {0, 1, 2, 3} when ``rot90`` fires (else 0),
    then ``torch.flip`` over Z (``zflip``), Y (``vflip``) and X (``hflip``) for the flips that fired - bit for bit a permutation;
 2. contrast, image only: ``v = (v - m) * a + m``, ``a = 1 + c`` with ``c`` uniform in ``contrast``, ``m`` the fp32 rounding of the sample's
@@ -23,6 +25,30 @@ nothing fired the output is bit for bit the input.
 The draws of a call are one 32-word record per sample (layout: ``include/biapy_amd.h``), filled on the device from Philox4x32-10 keyed by
 ``seed`` with the augmenter's own device counter, which advances by one per call.  Nothing is read back, so a call can be captured in a HIP
 graph and every replay draws anew.  ``last_records`` / ``records=`` / ``counter`` are the inspection hooks.
+
+The affine warp (step 0; product-defined and parity-unpinned like the rest)
+---------------------------------------------------------------------------
+``rotation=(lo, hi)`` (degrees), ``zoom=(lo, hi)``, ``shear=(lo, hi)`` (degrees) and ``shift=(lo, hi)`` (fractions of Y and X, ``ty`` and ``tx``
+drawn independently) each fire with ``da_prob``; a sample's draw is a WARP RECORD of 16 words (layout: ``include/biapy_amd.h``): word 0 the flags
+(bit 0 rotation, 1 zoom, 2 shear, 3 shift), words 1-6 ``m00 m01 m02 m10 m11 m12`` (fp32), words 8-12 the drawn ``theta, z, phi, ty, tx`` with the
+neutral 0, 1, 0, 0, 0 where a transform did not fire, the other words 0.  A sample with flags 0 is copied bit for bit (the step is skipped).
+
+Output voxel (y, x) reads the source at, all in fp32 with one IEEE operation per written operation and in exactly this association,
+``cy = (Y-1)/2``, ``cx = (X-1)/2``, ``dy = y - cy``, ``dx = x - cx``, ``fy = (m00 dy + m01 dx) + m02``, ``fx = (m10 dy + m11 dx) + m12``, each
+clamped to ``[-2^30, 2^30]`` (a NaN becomes a bound).  Image: ``y0 = floor(fy)``, ``wy = fy - y0``, likewise ``x0``, ``wx``; taps ``v00 v01 v10
+v11`` at ``(y0, x0) (y0, x0+1) (y0+1, x0) (y0+1, x0+1)``; ``top = v00 (1-wx) + v01 wx``, ``bot = v10 (1-wx) + v11 wx``, ``out = top (1-wy) + bot wy``.
+Target: the voxel ``(floor(fy + 0.5), floor(fx + 0.5))``.  The border rule ``affine_mode`` acts on every integer tap index on its own, for an axis
+of ``n`` voxels: ``"constant"`` - a tap outside ``[0, n)`` is ``affine_cval`` for the image and 0 for the target; ``"edge"`` - the index is clamped;
+``"reflect"`` - ``numpy.pad``'s: index 0 for ``n == 1``, else ``p = 2n - 2``, ``r = i mod p`` (non-negative), the index ``r`` if ``r < n`` else ``p - r``.
+
+The matrix of the drawn parameters, computed in fp32 by the draw kernel:
+``A = (1/z) [[cos t, sin t], [-sin t, cos t]] [[1, 0], [tan p, 1]]``, ``m00 m01 m10 m11 = A``, ``m02 = cy - ty Y``, ``m12 = cx - tx X``: zoom > 1
+magnifies, and the exact matrix ``[[0, 1], [-1, 0]]`` on a square plane is ``torch.rot90(src, 1, dims=(Y, X))``.  Draws: the key and counter words
+of the other draws (the call's counter value is read from words 5-6 of the sample's record), streams 16 (fires), 17 (theta, z, phi) and 18
+(ty, tx).  The contrast mean ``m`` stays the mean of the INPUT sample.  With any affine option on, the call launches ``bpx_aug_draw``,
+``bpx_warp_draw``, ``bpx_aug_mean`` (contrast only), ``bpx_warp_apply`` into scratch tensors the augmenter owns and ``bpx_aug_apply`` from those
+into the output - a second pass over the batch that leaves the gather pass as it is; with none on, exactly the launches listed above.
+``last_warp_records`` / ``warp_records=`` are the inspection hooks.
 """
 from __future__ import annotations
 
@@ -43,6 +69,12 @@ F_ZFLIP, F_VFLIP, F_HFLIP, K_SHIFT, F_CONTRAST, F_BRIGHTNESS, F_NOISE, NBOX_SHIF
 W_FLAGS, W_A, W_B, W_S, W_M, W_CTR, W_BOX = 0, 1, 2, 3, 4, 5, 8
 EN_ROT90, EN_ZFLIP, EN_VFLIP, EN_HFLIP, EN_CONTRAST, EN_BRIGHTNESS, EN_NOISE, EN_CUTOUT = (1 << i for i in range(8))
 
+WARP_REC_WORDS = 16
+WF_ROT, WF_ZOOM, WF_SHEAR, WF_SHIFT = 1, 2, 4, 8                 # warp record word 0, and bpx_warp_cfg.enable
+WW_FLAGS, WW_M, WW_P = 0, 1, 8
+AFFINE_MODES = {"constant": 0, "reflect": 1, "edge": 2}          # BPX_WARP_CONSTANT / _REFLECT / _EDGE
+WARP_M_MAX = 2.0 ** 20                                            # |matrix word| accepted through warp_records=
+
 _CUTOUT_DEFAULTS = dict(n=(1, 3), size=(0.05, 0.3), cval=0.0, apply_to_mask=False)
 
 
@@ -56,6 +88,13 @@ def _range(name: str, v) -> Optional[Tuple[float, float]]:
     if not (math.isfinite(lo) and math.isfinite(hi)) or lo > hi:
         raise ValueError(f"{name} must be a finite (lo, hi) range with lo <= hi, got {v!r}")
     return lo, hi
+
+
+def _bounded(name: str, v, lo: float, hi: float) -> Optional[Tuple[float, float]]:
+    r = _range(name, v)
+    if r is not None and not (lo <= r[0] and r[1] <= hi):
+        raise ValueError(f"{name} must lie within [{lo:g}, {hi:g}], got {v!r}")
+    return r
 
 
 def _contig_strides(shape: Sequence[int]):
@@ -99,10 +138,11 @@ def _span(t: torch.Tensor):
 
 
 class DeviceAugmenter:
-    """See the module docstring.  ``aug(x, t, out=None, records=None) -> (x_out, t_out)``."""
+    """See the module docstring.  ``aug(x, t, out=None, records=None, warp_records=None) -> (x_out, t_out)``."""
 
     def __init__(self, *, da_prob: float = 0.5, rot90: bool = False, zflip: bool = False, vflip: bool = False, hflip: bool = False,
-                 brightness=None, contrast=None, gaussian_noise=None, cutout=None, seed: Optional[int] = None):
+                 brightness=None, contrast=None, gaussian_noise=None, cutout=None, seed: Optional[int] = None, rotation=None, zoom=None,
+                 shear=None, shift=None, affine_mode: str = "constant", affine_cval: float = 0.0):
         da_prob = float(da_prob)
         if not (0.0 <= da_prob <= 1.0):
             raise ValueError(f"da_prob must lie in [0, 1], got {da_prob}")
@@ -134,6 +174,19 @@ class DeviceAugmenter:
             if not math.isfinite(cval):
                 raise ValueError(f"cutout['cval'] must be finite, got {c['cval']!r}")
             self.cutout = dict(n=(n_lo, n_hi), size=size, cval=cval, apply_to_mask=bool(c["apply_to_mask"]))
+        self.rotation = _bounded("rotation", rotation, -360.0, 360.0)
+        self.zoom = _bounded("zoom", zoom, 0.1, 10.0)
+        self.shear = _bounded("shear", shear, -60.0, 60.0)
+        self.shift = _bounded("shift", shift, -1.0, 1.0)
+        if affine_mode not in AFFINE_MODES:
+            raise ValueError(f"affine_mode must be one of {sorted(AFFINE_MODES)}, got {affine_mode!r}")
+        self.affine_mode = affine_mode
+        try:
+            self.affine_cval = float(affine_cval)
+        except (TypeError, ValueError):
+            raise ValueError(f"affine_cval must be a number, got {affine_cval!r}") from None
+        if not math.isfinite(self.affine_cval):
+            raise ValueError(f"affine_cval must be finite, got {affine_cval!r}")
         if seed is None:
             rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
             seed = torch.initial_seed() + rank                        # ranks draw differently
@@ -144,6 +197,8 @@ class DeviceAugmenter:
         self._state = None            # int64[2] on the device: [counter, ticket of the draw kernel]
         self._records = None
         self._ws = None
+        self._warp = None             # int32 (B, 16): the warp records
+        self._wx = self._wt = None    # the warped pair, input of the gather pass
 
     # ---- configuration --------------------------------------------------------------------------------------------------------
     @property
@@ -163,12 +218,25 @@ class DeviceAugmenter:
                     contrast=self.contrast or (0.0, 0.0), brightness=self.brightness or (0.0, 0.0), noise=self.gaussian_noise or (0.0, 0.0),
                     size=cut["size"])
 
+    @property
+    def warp_enable_mask(self) -> int:
+        return sum(bit for on, bit in ((self.rotation, WF_ROT), (self.zoom, WF_ZOOM), (self.shear, WF_SHEAR), (self.shift, WF_SHIFT)) if on is not None)
+
+    def warp_config(self) -> dict:
+        """The warp's draw parameters as plain numbers (what ``bpx_warp_cfg`` carries; ``tests/warp_ref.draw`` takes the same dict)."""
+        return dict(seed=self.seed, thr=int(math.floor(self.da_prob * 2.0 ** 32)), enable=self.warp_enable_mask, rotation=self.rotation or (0.0, 0.0),
+                    zoom=self.zoom or (1.0, 1.0), shear=self.shear or (0.0, 0.0), shift=self.shift or (0.0, 0.0))
+
+    def _warp_cfg_struct(self) -> "L.WarpCfg":
+        c = self.warp_config()
+        return L.WarpCfg(c["seed"], c["thr"], c["enable"], 0, *c["rotation"], *c["zoom"], *c["shear"], *c["shift"])
+
     def _cfg_struct(self) -> "L.AugCfg":
         c = self.config()
         return L.AugCfg(c["seed"], c["thr"], c["enable"], c["box"][0], c["box"][1], *c["contrast"], *c["brightness"], *c["noise"], *c["size"])
 
     @classmethod
-    def from_cfg(cls, cfg, seed: Optional[int] = None) -> Optional["DeviceAugmenter"]:
+    def from_cfg(cls, cfg, seed: Optional[int] = None, *, affine: bool = False) -> Optional["DeviceAugmenter"]:
         """The augmenter a reference configuration asks for, ``None`` when ``AUGMENTOR.ENABLE`` is false.
 
         Mapped ``AUGMENTOR`` keys: ``DA_PROB``; ``ROT90``, ``ZFLIP``, ``VFLIP``, ``HFLIP``; ``BRIGHTNESS`` + ``BRIGHTNESS_FACTOR``; ``CONTRAST`` +
@@ -176,6 +244,11 @@ class DeviceAugmenter:
         ``GAUSSIAN_NOISE_VAR`` (the fixed deviation ``sqrt(var)``); ``CUTOUT`` + ``COUT_NB_ITERATIONS``, ``COUT_SIZE``, ``COUT_CVAL``,
         ``COUT_APPLY_TO_MASK``.  Any OTHER switch of the node that is ``True`` (``RANDOM_ROT``, ``ELASTIC``, ``ZOOM``, ``SHEAR``, ``G_BLUR``,
         ``GAMMA_CONTRAST``, ...) raises ``NotImplementedError`` naming it: a run never silently trains with less augmentation than configured.
+
+        ``affine=True`` also maps the affine family onto step 0: ``RANDOM_ROT`` + ``RANDOM_ROT_RANGE`` (degrees), ``ZOOM`` + ``ZOOM_RANGE``
+        (``ZOOM_IN_Z`` is refused: the warp acts in the (Y, X) plane), ``SHEAR`` + ``SHEAR_RANGE`` (degrees), ``SHIFT`` + ``SHIFT_RANGE`` (fractions)
+        and ``AFFINE_MODE`` (``constant`` / ``reflect`` / ``edge``; ``wrap`` and ``symmetric`` are refused by name; ``reflect`` when the key is
+        absent, as the reference's tree is remembered).  It is opt-in because these semantics are this package's own: the default keeps refusing them.
 
         The key names are written from memory of the reference's configuration tree and could not be verified against it on the build machine;
         the semantics of every transform are this package's own (parity-unpinned, see the module docstring)."""
@@ -191,11 +264,11 @@ class DeviceAugmenter:
             items = dict(node)
         else:
             items = {k: getattr(node, k) for k in dir(node) if k.isupper()}
-        for k in _UNSUPPORTED_SWITCHES:                                # also those a node that cannot be listed still answers for
+        for k in _UNSUPPORTED_SWITCHES + (("ZOOM_IN_Z",) if affine else ()):   # also those a node that cannot be listed still answers for
             if k not in items and get(k, False) is True:
                 items[k] = True
         for k in sorted(items):
-            if items[k] is True and k not in _MAPPED_SWITCHES and k not in _NEUTRAL_SWITCHES:
+            if items[k] is True and k not in _MAPPED_SWITCHES and k not in _NEUTRAL_SWITCHES and not (affine and k in _AFFINE_SWITCHES):
                 raise NotImplementedError(f"AUGMENTOR.{k} is enabled but biapy_amd.augment.DeviceAugmenter does not implement it (supported: "
                                           f"{', '.join(sorted(_MAPPED_SWITCHES - {'ENABLE'}))}); keep this transform in the loader or switch it off")
         kw = dict(da_prob=get("DA_PROB", 0.5), rot90=bool(get("ROT90", False)), zflip=bool(get("ZFLIP", False)),
@@ -215,6 +288,16 @@ class DeviceAugmenter:
         if get("CUTOUT", False):
             kw["cutout"] = dict(n=tuple(get("COUT_NB_ITERATIONS", (1, 3))), size=tuple(get("COUT_SIZE", (0.05, 0.3))),
                                 cval=get("COUT_CVAL", 0.0), apply_to_mask=bool(get("COUT_APPLY_TO_MASK", False)))
+        if affine:
+            for switch, key, name, default in (("RANDOM_ROT", "RANDOM_ROT_RANGE", "rotation", (-180.0, 180.0)), ("ZOOM", "ZOOM_RANGE", "zoom", (0.8, 1.2)),
+                                               ("SHEAR", "SHEAR_RANGE", "shear", (-20.0, 20.0)), ("SHIFT", "SHIFT_RANGE", "shift", (0.1, 0.2))):
+                if get(switch, False):
+                    kw[name] = tuple(get(key, default))
+            mode = str(get("AFFINE_MODE", "reflect"))
+            if mode not in AFFINE_MODES:
+                raise NotImplementedError(f"AUGMENTOR.AFFINE_MODE = {mode!r} is not implemented by biapy_amd.augment.DeviceAugmenter (supported: "
+                                          f"{', '.join(sorted(AFFINE_MODES))})")
+            kw["affine_mode"] = mode
         return cls(**kw)
 
     # ---- state ----------------------------------------------------------------------------------------------------------------
@@ -234,12 +317,18 @@ class DeviceAugmenter:
         return self._state[0]
 
     @property
+    def last_warp_records(self) -> Optional[torch.Tensor]:
+        """The ``(B, 16)`` int32 device tensor of the last call's warp records (``None`` before the first call that warps)."""
+        return self._warp
+
+    @property
     def last_records(self) -> Optional[torch.Tensor]:
         """The ``(B, 32)`` int32 device tensor of the last call's records (the augmenter's own buffer, overwritten by the next call)."""
         return self._records
 
     # ---- the call -------------------------------------------------------------------------------------------------------------
-    def __call__(self, x: torch.Tensor, t: torch.Tensor, out=None, *, records: Optional[torch.Tensor] = None):
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, out=None, *, records: Optional[torch.Tensor] = None,
+                 warp_records: Optional[torch.Tensor] = None):
         for name, v in (("x", x), ("t", t)):
             if not torch.is_tensor(v) or not v.is_cuda:
                 raise ValueError(f"{name} must be a CUDA/HIP tensor: biapy_amd.augment runs on the device only, there is no CPU path")
@@ -288,8 +377,23 @@ class DeviceAugmenter:
             if (not torch.is_tensor(records) or records.device != x.device or records.dtype != torch.int32
                     or tuple(records.shape) != (B, REC_WORDS) or not records.is_contiguous()):
                 raise ValueError(f"records must be a contiguous ({B}, {REC_WORDS}) int32 tensor on the device of x")
+        warp = warp_records is not None or self.warp_enable_mask != 0
+        if warp_records is not None:                                   # checked on the host: the hook may read back
+            if (not torch.is_tensor(warp_records) or warp_records.device != x.device or warp_records.dtype != torch.int32
+                    or tuple(warp_records.shape) != (B, WARP_REC_WORDS) or not warp_records.is_contiguous()):
+                raise ValueError(f"warp_records must be a contiguous ({B}, {WARP_REC_WORDS}) int32 tensor on the device of x")
+            m = warp_records[:, WW_M:WW_M + 6].contiguous().view(torch.float32)
+            if not bool((torch.isfinite(m) & (m.abs() <= WARP_M_MAX)).all()):
+                raise ValueError(f"warp_records words 1-6 (the matrix) must be finite with |m| <= 2^20, got {m.cpu().tolist()}")
 
         self._ensure(x.device, B)
+        if warp:
+            if self._warp is None or self._warp.shape[0] != B or self._warp.device != x.device:
+                self._warp = torch.zeros((B, WARP_REC_WORDS), dtype=torch.int32, device=x.device)
+            for name, like in (("_wx", xm), ("_wt", tm)):
+                buf = getattr(self, name)
+                if buf is None or buf.shape != like.shape or buf.dtype != like.dtype or buf.device != like.device:
+                    setattr(self, name, torch.empty(like.shape, dtype=like.dtype, device=like.device))
         s = L.stream_ptr()
         rec = self._records
         if records is None:
@@ -299,12 +403,23 @@ class DeviceAugmenter:
             L.check(lib.bpx_aug_draw(ctypes.addressof(cfg), B, Z, Y, X, self._state.data_ptr(), rec.data_ptr(), s))
         else:
             rec.copy_(records)
+        if warp_records is not None:
+            self._warp.copy_(warp_records)
+        elif warp:
+            import ctypes
+
+            wcfg = self._warp_cfg_struct()
+            L.check(lib.bpx_warp_draw(ctypes.addressof(wcfg), B, Y, X, rec.data_ptr(), self._warp.data_ptr(), s))
         if records is not None or self.contrast is not None:           # m is only ever used by the contrast step
             n = Z * Y * X * C
             need = B * int(lib.bpx_aug_mean_blocks(n))
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(need, dtype=torch.float64, device=x.device)
             L.check(lib.bpx_aug_mean(xm.data_ptr(), B, n, self._ws.data_ptr(), rec.data_ptr(), s))
+        if warp:                                                       # step 0 into the scratch pair, the gather pass then reads that
+            L.check(lib.bpx_warp_apply(xm.data_ptr(), tm.data_ptr(), L.dt_of(t), B, Z, Y, X, C, Ct, self._warp.data_ptr(), AFFINE_MODES[self.affine_mode],
+                                       self.affine_cval, self._wx.data_ptr(), self._wt.data_ptr(), s))
+            xm, tm = self._wx, self._wt
         cut = self.cutout or _CUTOUT_DEFAULTS
         L.check(lib.bpx_aug_apply(xm.data_ptr(), tm.data_ptr(), L.dt_of(t), B, Z, Y, X, C, Ct, rec.data_ptr(), self.seed, float(cut["cval"]),
                                   int(bool(cut["apply_to_mask"])), xo.data_ptr(), to.data_ptr(), s))
@@ -313,6 +428,7 @@ class DeviceAugmenter:
 
 # AUGMENTOR switches from_cfg maps, switches that select no transform, and the transforms it refuses by name (from memory of the reference's tree)
 _MAPPED_SWITCHES = {"ENABLE", "ROT90", "ZFLIP", "VFLIP", "HFLIP", "BRIGHTNESS", "CONTRAST", "GAUSSIAN_NOISE", "CUTOUT", "COUT_APPLY_TO_MASK"}
+_AFFINE_SWITCHES = {"RANDOM_ROT", "ZOOM", "SHEAR", "SHIFT"}         # mapped by from_cfg(affine=True) only
 _NEUTRAL_SWITCHES = {"DRAW_GRID", "AUG_SAMPLES", "SHUFFLE_TRAIN_DATA_EACH_EPOCH", "SHUFFLE_VAL_DATA_EACH_EPOCH"}
 _UNSUPPORTED_SWITCHES = ("RANDOM_ROT", "ELASTIC", "ZOOM", "SHEAR", "SHIFT", "AFFINE", "G_BLUR", "MEDIAN_BLUR", "MOTION_BLUR", "GAMMA_CONTRAST",
                          "BRIGHTNESS_EM", "CONTRAST_EM", "DROPOUT", "CUTBLUR", "CUTMIX", "CUTNOISE", "MISALIGNMENT", "MISSING_SECTIONS",

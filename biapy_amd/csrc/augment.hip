@@ -1,5 +1,6 @@
 // Training-time augmentation on the device (biapy_amd/augment.py states the semantics, include/biapy_amd.h the record layout): flips, rot90 over
 // (Y, X), contrast, brightness, Gaussian noise and cutout of a float32 (B,Z,Y,X,C) batch and its float32 / uint8 target in ONE gather pass.
+// The affine warp (rotation, zoom, shear, shift: step 0, a pass of its own in front of that one) is the last section of the file.
 //
 // Random numbers: Philox4x32-10 (philox.h), key = the augmenter's 64-bit seed, counter words = (sample, stream, counter low, counter high) with the
 // augmenter's own device counter, one value per call.  Streams of the draw kernel, r = the four output words:
@@ -362,6 +363,172 @@ void launch_apply(int vx, int vt, unsigned blocks, size_t lds, hipStream_t s, co
   else aug_apply_kernel<TT, 1, 1><<<blocks, 256, lds, s>>>(x, t, g, C, Ct, pitch_x, pitch_t, rec, seed, cval, mask_too, xo, to);
 }
 
+// ---- the affine warp (step 0): one 2x3 matrix per sample, bilinear image, nearest target ---------------------------------------------------
+// Streams 16-18 of the draw key and counter words (the call's counter value is read back out of the sample's augmentation record):
+//   16     fires: r0 rotation, r1 zoom, r2 shear, r3 shift
+//   17     uniforms: r0 theta (degrees), r1 zoom, r2 phi (degrees)
+//   18     uniforms: r0 ty, r1 tx (fractions of Y and X)
+constexpr int WREC = BPX_WARP_REC_WORDS;
+
+__global__ void __launch_bounds__(256) warp_draw_kernel(const bpx_warp_cfg cfg, int B, int Y, int X, const uint32_t* __restrict__ rec,
+                                                        uint32_t* __restrict__ warp) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const uint32_t k0 = (uint32_t)cfg.seed, k1 = (uint32_t)(cfg.seed >> 32);
+  const uint32_t cl = rec[(size_t)b * REC + BPX_AUG_W_CTR], ch = rec[(size_t)b * REC + BPX_AUG_W_CTR + 1];
+  uint32_t f[4], u[4], v[4];
+  philox4x32_10((uint32_t)b, 16u, cl, ch, k0, k1, f);
+  philox4x32_10((uint32_t)b, 17u, cl, ch, k0, k1, u);
+  philox4x32_10((uint32_t)b, 18u, cl, ch, k0, k1, v);
+  auto fires = [&](uint32_t r, uint32_t en) { return (cfg.enable & en) && (uint64_t)r < cfg.thr; };
+  uint32_t flags = 0;
+  float th = 0.f, zm = 1.f, ph = 0.f, ty = 0.f, tx = 0.f;
+  if (fires(f[0], BPX_WARP_F_ROT)) { flags |= BPX_WARP_F_ROT; th = aug_uniform(u[0], cfg.rot_lo, cfg.rot_hi); }
+  if (fires(f[1], BPX_WARP_F_ZOOM)) { flags |= BPX_WARP_F_ZOOM; zm = aug_uniform(u[1], cfg.zoom_lo, cfg.zoom_hi); }
+  if (fires(f[2], BPX_WARP_F_SHEAR)) { flags |= BPX_WARP_F_SHEAR; ph = aug_uniform(u[2], cfg.shear_lo, cfg.shear_hi); }
+  if (fires(f[3], BPX_WARP_F_SHIFT)) {
+    flags |= BPX_WARP_F_SHIFT;
+    ty = aug_uniform(v[0], cfg.shift_lo, cfg.shift_hi);
+    tx = aug_uniform(v[1], cfg.shift_lo, cfg.shift_hi);
+  }
+  // A = (1/z) [[c, s], [-s, c]] [[1, 0], [t, 1]] = (1/z) [[c + s t, s], [c t - s, c]]
+  const float d2r = 0.017453292519943295f;
+  const float ra = __fmul_rn(th, d2r), rp = __fmul_rn(ph, d2r);
+  const float c = cosf(ra), s = sinf(ra), t = tanf(rp), iz = __fdiv_rn(1.f, zm);
+  const float cy = (float)(Y - 1) * 0.5f, cx = (float)(X - 1) * 0.5f;
+  const float m00 = __fmul_rn(iz, __fadd_rn(c, __fmul_rn(s, t))), m01 = __fmul_rn(iz, s);
+  const float m10 = __fmul_rn(iz, __fsub_rn(__fmul_rn(c, t), s)), m11 = __fmul_rn(iz, c);
+  const float m02 = __fsub_rn(cy, __fmul_rn(ty, (float)Y)), m12 = __fsub_rn(cx, __fmul_rn(tx, (float)X));
+  u32x4_t* dst = reinterpret_cast<u32x4_t*>(warp + (size_t)b * WREC);
+  dst[0] = u32x4_t{flags, __float_as_uint(m00), __float_as_uint(m01), __float_as_uint(m02)};
+  dst[1] = u32x4_t{__float_as_uint(m10), __float_as_uint(m11), __float_as_uint(m12), 0u};
+  dst[2] = u32x4_t{__float_as_uint(th), __float_as_uint(zm), __float_as_uint(ph), __float_as_uint(ty)};
+  dst[3] = u32x4_t{__float_as_uint(tx), 0u, 0u, 0u};
+}
+
+// One workgroup = one (sample, z, WT x WT tile of (Y, X)) of the OUTPUT, never two samples: flags and matrix are uniform over it.  Its source
+// footprint is a parallelogram of one z plane, read with plain loads - consecutive lanes walk consecutive output elements of a row, so their
+// taps step by one matrix column through the source and the four taps of neighbouring lanes share cache lines.
+constexpr int WT = 32;
+struct WarpGeom { int Z, Y, X, tiles_x, tiles_y; };
+
+// the source index of tap i on an axis of n voxels (p = max(2n - 2, 1), the reflect period); `in`: whether a constant-mode tap reads the plane
+template <int MODE>
+__device__ __forceinline__ int warp_tap(int i, int n, int p, bool& in) {
+  if constexpr (MODE == BPX_WARP_REFLECT) {
+    int r = i % p;
+    r += r < 0 ? p : 0;
+    in = true;
+    return r < n ? r : p - r;
+  } else {
+    in = MODE == BPX_WARP_EDGE || (unsigned)i < (unsigned)n;
+    return min(max(i, 0), n - 1);
+  }
+}
+
+struct WarpMap {
+  float m00, m01, m02, m10, m11, m12, cy, cx;
+  __device__ __forceinline__ void src(int y, int x, float& fy, float& fx) const {
+    const float dy = __fsub_rn((float)y, cy), dx = __fsub_rn((float)x, cx);
+    fy = __fadd_rn(__fadd_rn(__fmul_rn(m00, dy), __fmul_rn(m01, dx)), m02);
+    fx = __fadd_rn(__fadd_rn(__fmul_rn(m10, dy), __fmul_rn(m11, dx)), m12);
+    fy = fminf(fmaxf(fy, -1073741824.f), 1073741824.f);          // a NaN becomes the lower bound: every index below is finite
+    fx = fminf(fmaxf(fx, -1073741824.f), 1073741824.f);
+  }
+};
+
+template <typename TT, int MODE>
+__global__ void __launch_bounds__(256) warp_apply_kernel(const float* __restrict__ x, const TT* __restrict__ t, WarpGeom g, int C, int Ct,
+                                                         const uint32_t* __restrict__ warp, float cval, float* __restrict__ xo, TT* __restrict__ to) {
+  const int tiles = g.tiles_x * g.tiles_y;
+  const int64_t per_sample = (int64_t)g.Z * tiles;
+  const int b = (int)((int64_t)blockIdx.x / per_sample);
+  const int rest = (int)((int64_t)blockIdx.x - (int64_t)b * per_sample);
+  const int z = rest / tiles, tile = rest % tiles;
+  const int yo0 = (tile / g.tiles_x) * WT, xo0 = (tile % g.tiles_x) * WT;
+  const int nyo = min(WT, g.Y - yo0), nxo = min(WT, g.X - xo0);
+  const int Y = g.Y, X = g.X;
+  const int py = max(2 * Y - 2, 1), px = max(2 * X - 2, 1);
+
+  const uint32_t* rc = warp + (size_t)b * WREC;
+  const uint32_t flags = rc[BPX_WARP_W_FLAGS];
+  WarpMap wm;
+  wm.m00 = __uint_as_float(rc[BPX_WARP_W_M]); wm.m01 = __uint_as_float(rc[BPX_WARP_W_M + 1]); wm.m02 = __uint_as_float(rc[BPX_WARP_W_M + 2]);
+  wm.m10 = __uint_as_float(rc[BPX_WARP_W_M + 3]); wm.m11 = __uint_as_float(rc[BPX_WARP_W_M + 4]); wm.m12 = __uint_as_float(rc[BPX_WARP_W_M + 5]);
+  wm.cy = (float)(Y - 1) * 0.5f; wm.cx = (float)(X - 1) * 0.5f;
+
+  const int64_t plane = ((int64_t)b * g.Z + z) * Y * X;           // the sample's z plane, in voxels: source and destination alike
+  const float* xs = x + plane * C;
+  const TT* ts = t + plane * Ct;
+  const float rcp_c = 1.f / (float)C, rcp_ct = 1.f / (float)Ct;
+
+  // ---- image ----
+  {
+    const int ipr = nxo * C, items = nyo * ipr;                    // < 2^15 items, rows of at most 2^9 elements: small_div is exact
+    const float rcp = 1.f / (float)ipr;
+    for (int i = threadIdx.x; i < items; i += 256) {
+      const int r = small_div(i, rcp), e = i - r * ipr;
+      const int xl = C == 1 ? e : small_div(e, rcp_c), c = e - xl * C;
+      const int yo = yo0 + r, xv = xo0 + xl;
+      const int64_t dst = ((int64_t)yo * X + xv) * C + c;
+      float out;
+      if (!flags) {
+        out = xs[dst];
+      } else {
+        float fy, fx;
+        wm.src(yo, xv, fy, fx);
+        const float fy0 = floorf(fy), fx0 = floorf(fx);
+        const float wy = __fsub_rn(fy, fy0), wx = __fsub_rn(fx, fx0);
+        const int y0 = (int)fy0, x0 = (int)fx0;
+        bool iy0, iy1, ix0, ix1;
+        const int64_t ra = (int64_t)warp_tap<MODE>(y0, Y, py, iy0) * X, rb = (int64_t)warp_tap<MODE>(y0 + 1, Y, py, iy1) * X;
+        const int xa = warp_tap<MODE>(x0, X, px, ix0), xb = warp_tap<MODE>(x0 + 1, X, px, ix1);
+        float v00 = xs[(ra + xa) * C + c], v01 = xs[(ra + xb) * C + c], v10 = xs[(rb + xa) * C + c], v11 = xs[(rb + xb) * C + c];
+        if constexpr (MODE == BPX_WARP_CONSTANT) {
+          v00 = iy0 && ix0 ? v00 : cval; v01 = iy0 && ix1 ? v01 : cval;
+          v10 = iy1 && ix0 ? v10 : cval; v11 = iy1 && ix1 ? v11 : cval;
+        }
+        const float ux = __fsub_rn(1.f, wx), uy = __fsub_rn(1.f, wy);
+        const float top = __fadd_rn(__fmul_rn(v00, ux), __fmul_rn(v01, wx));
+        const float bot = __fadd_rn(__fmul_rn(v10, ux), __fmul_rn(v11, wx));
+        out = __fadd_rn(__fmul_rn(top, uy), __fmul_rn(bot, wy));
+      }
+      xo[plane * C + dst] = out;
+    }
+  }
+  // ---- target: the nearest voxel ----
+  {
+    const int ipr = nxo * Ct, items = nyo * ipr;
+    const float rcp = 1.f / (float)ipr;
+    for (int i = threadIdx.x; i < items; i += 256) {
+      const int r = small_div(i, rcp), e = i - r * ipr;
+      const int xl = Ct == 1 ? e : small_div(e, rcp_ct), c = e - xl * Ct;
+      const int yo = yo0 + r, xv = xo0 + xl;
+      const int64_t dst = ((int64_t)yo * X + xv) * Ct + c;
+      TT out;
+      if (!flags) {
+        out = ts[dst];
+      } else {
+        float fy, fx;
+        wm.src(yo, xv, fy, fx);
+        bool iy, ix;
+        const int ya = warp_tap<MODE>((int)floorf(__fadd_rn(fy, 0.5f)), Y, py, iy), xa = warp_tap<MODE>((int)floorf(__fadd_rn(fx, 0.5f)), X, px, ix);
+        out = ts[((int64_t)ya * X + xa) * Ct + c];
+        if constexpr (MODE == BPX_WARP_CONSTANT) out = iy && ix ? out : (TT)0;
+      }
+      to[plane * Ct + dst] = out;
+    }
+  }
+}
+
+template <typename TT>
+void launch_warp(int mode, unsigned blocks, hipStream_t s, const float* x, const TT* t, WarpGeom g, int C, int Ct, const uint32_t* warp, float cval,
+                 float* xo, TT* to) {
+  if (mode == BPX_WARP_CONSTANT) warp_apply_kernel<TT, BPX_WARP_CONSTANT><<<blocks, 256, 0, s>>>(x, t, g, C, Ct, warp, cval, xo, to);
+  else if (mode == BPX_WARP_REFLECT) warp_apply_kernel<TT, BPX_WARP_REFLECT><<<blocks, 256, 0, s>>>(x, t, g, C, Ct, warp, cval, xo, to);
+  else warp_apply_kernel<TT, BPX_WARP_EDGE><<<blocks, 256, 0, s>>>(x, t, g, C, Ct, warp, cval, xo, to);
+}
+
 }  // namespace
 
 extern "C" int bpx_aug_draw(const bpx_aug_cfg* cfg, int B, int Z, int Y, int X, uint64_t* state_d, uint32_t* records_d, bpx_stream_t stream) {
@@ -422,6 +589,43 @@ extern "C" int bpx_aug_apply(const float* x_d, const void* t_d, int t_dtype, int
   else
     launch_apply<uint8_t>(vx, vt, (unsigned)blocks, lds, (hipStream_t)stream, x_d, (const uint8_t*)t_d, g, C, Ct, pitch_x, pitch_t, records_d, seed, cval,
                           mask_too, x_out_d, (uint8_t*)t_out_d);
+  BPX_LAUNCH_CHECK(fn);
+  return 0;
+}
+
+extern "C" int bpx_warp_draw(const bpx_warp_cfg* cfg, int B, int Y, int X, const uint32_t* records_d, uint32_t* warp_d, bpx_stream_t stream) {
+  const char* fn = "bpx_warp_draw";
+  BPX_CHECK(cfg && records_d && warp_d, "%s: null pointer", fn);
+  BPX_CHECK(B > 0 && Y > 0 && X > 0, "%s: bad extents", fn);
+  BPX_CHECK(((uintptr_t)warp_d & 15) == 0 && ((uintptr_t)records_d & 3) == 0, "%s: warp records must be 16-byte aligned", fn);
+  BPX_CHECK(cfg->thr <= (1ull << 32), "%s: thr above 2^32", fn);
+  BPX_CHECK((cfg->enable & ~0xFu) == 0, "%s: unknown enable bits", fn);
+  BPX_CHECK(cfg->rot_lo <= cfg->rot_hi && cfg->shear_lo <= cfg->shear_hi && cfg->shift_lo <= cfg->shift_hi, "%s: a range has lo > hi", fn);
+  if (cfg->enable & BPX_WARP_F_ZOOM) BPX_CHECK(cfg->zoom_lo > 0.f && cfg->zoom_lo <= cfg->zoom_hi, "%s: the zoom range must be positive with lo <= hi", fn);
+  warp_draw_kernel<<<cdiv(B, 256), 256, 0, (hipStream_t)stream>>>(*cfg, B, Y, X, records_d, warp_d);
+  BPX_LAUNCH_CHECK(fn);
+  return 0;
+}
+
+extern "C" int bpx_warp_apply(const float* x_d, const void* t_d, int t_dtype, int B, int Z, int Y, int X, int C, int Ct, const uint32_t* warp_d, int mode,
+                              float cval, float* x_out_d, void* t_out_d, bpx_stream_t stream) {
+  const char* fn = "bpx_warp_apply";
+  BPX_CHECK(x_d && t_d && warp_d && x_out_d && t_out_d, "%s: null pointer", fn);
+  BPX_CHECK(B > 0 && Z > 0 && Y > 0 && X > 0, "%s: bad extents", fn);
+  BPX_CHECK(C >= 1 && C <= 16 && Ct >= 1 && Ct <= 8, "%s: 1..16 image channels and 1..8 target channels (got %d, %d)", fn, C, Ct);
+  BPX_CHECK(t_dtype == BPX_F32 || t_dtype == BPX_U8, "%s: the target is float32 or uint8", fn);
+  BPX_CHECK(mode == BPX_WARP_CONSTANT || mode == BPX_WARP_REFLECT || mode == BPX_WARP_EDGE, "%s: unknown border mode %d", fn, mode);
+  BPX_CHECK((const void*)x_d != (const void*)x_out_d && t_d != t_out_d, "%s: the pass is a gather and cannot run in place", fn);
+  BPX_CHECK(Y <= (1 << 24) && X <= (1 << 24), "%s: a plane axis above 2^24 voxels", fn);      // (Y-1)/2 and every y - cy stay exact in fp32
+  WarpGeom g;
+  g.Z = Z; g.Y = Y; g.X = X;
+  g.tiles_x = cdiv(X, WT); g.tiles_y = cdiv(Y, WT);
+  const int64_t blocks = (int64_t)B * Z * g.tiles_x * g.tiles_y;
+  BPX_CHECK(blocks < (1ll << 31), "%s: %lld tiles exceed one launch", fn, (long long)blocks);
+  if (t_dtype == BPX_F32)
+    launch_warp<float>(mode, (unsigned)blocks, (hipStream_t)stream, x_d, (const float*)t_d, g, C, Ct, warp_d, cval, x_out_d, (float*)t_out_d);
+  else
+    launch_warp<uint8_t>(mode, (unsigned)blocks, (hipStream_t)stream, x_d, (const uint8_t*)t_d, g, C, Ct, warp_d, cval, x_out_d, (uint8_t*)t_out_d);
   BPX_LAUNCH_CHECK(fn);
   return 0;
 }

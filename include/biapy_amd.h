@@ -711,6 +711,50 @@ int bpx_aug_mean(const float* x_d, int B, int64_t n, double* ws_d, uint32_t* rec
 int bpx_aug_apply(const float* x_d, const void* t_d, int t_dtype, int B, int Z, int Y, int X, int C, int Ct, const uint32_t* records_d, uint64_t seed,
                   float cval, int mask_too, float* x_out_d, void* t_out_d, bpx_stream_t stream);
 
+/* ---- affine warp in the (Y, X) plane: random rotation, zoom, shear and shift (step 0 of biapy_amd/augment.py; csrc/augment.hip) ----------
+ * One 2x3 matrix per sample, identical for every z and channel; the image is interpolated bilinearly, the target takes the nearest voxel.
+ * The draws of a call live in one WARP RECORD of 16 four-byte words per sample:
+ *   word 0       flags: bit 0 rotation, 1 zoom, 2 shear, 3 shift fired; 0 = the sample is copied bit for bit
+ *   words 1-6    m00 m01 m02 m10 m11 m12 (float): the source coordinate of output voxel (y, x) is
+ *                fy = (m00 dy + m01 dx) + m02, fx = (m10 dy + m11 dx) + m12 with dy = y - (Y-1)/2, dx = x - (X-1)/2, each clamped to +-2^30
+ *   word 7       0
+ *   words 8-12   the drawn parameters (float): theta in degrees, zoom z, shear phi in degrees, ty, tx as fractions of Y and X; a transform
+ *                that did not fire holds its neutral value 0, 1, 0, 0, 0
+ *   words 13-15  0
+ * The matrix of the drawn parameters, in fp32:  A = (1/z) [[cos t, sin t], [-sin t, cos t]] [[1, 0], [tan p, 1]],  m00 m01 m10 m11 = A,
+ * m02 = (Y-1)/2 - ty Y, m12 = (X-1)/2 - tx X. */
+#define BPX_WARP_REC_WORDS 16
+#define BPX_WARP_F_ROT 0x1u
+#define BPX_WARP_F_ZOOM 0x2u
+#define BPX_WARP_F_SHEAR 0x4u
+#define BPX_WARP_F_SHIFT 0x8u
+#define BPX_WARP_W_FLAGS 0
+#define BPX_WARP_W_M 1
+#define BPX_WARP_W_P 8
+/* border rule of a tap outside the plane (bpx_warp_apply's mode), per integer tap index and axis of n voxels */
+#define BPX_WARP_CONSTANT 0 /* cval for the image, 0 for the target */
+#define BPX_WARP_REFLECT 1  /* numpy.pad's "reflect": period 2n - 2, true modulo; n == 1: index 0 */
+#define BPX_WARP_EDGE 2     /* the index is clamped */
+typedef struct {
+  uint64_t seed;              /* Philox key: the augmenter's */
+  uint64_t thr;               /* floor(da_prob * 2^32), as in bpx_aug_cfg */
+  uint32_t enable;            /* BPX_WARP_F_*: which transforms may fire */
+  uint32_t reserved;
+  float rot_lo, rot_hi;       /* degrees */
+  float zoom_lo, zoom_hi;     /* > 0 */
+  float shear_lo, shear_hi;   /* degrees */
+  float shift_lo, shift_hi;   /* fraction of the axis, ty and tx drawn independently */
+} bpx_warp_cfg;
+/*   bpx_warp_draw  : fills warp_d[B][16] from Philox4x32-10(key = seed, counter = (sample, stream, c low, c high)), c = the counter value in
+ *                    words 5-6 of the sample's augmentation record records_d[b] (what bpx_aug_draw drew with: no second ticket).  Streams: 16
+ *                    fires (r0 rotation, r1 zoom, r2 shear, r3 shift), 17 uniforms theta, z, phi, 18 uniforms ty, tx.  One launch, nothing
+ *                    is read back: capturable.
+ *   bpx_warp_apply : out = the warped pair, ONE out-of-place pass over image (1..16 channels) and target (1..8, BPX_F32 or BPX_U8).  Whatever
+ *                    the matrix words hold, the clamp and the border rule keep every load inside the sample's plane. */
+int bpx_warp_draw(const bpx_warp_cfg* cfg, int B, int Y, int X, const uint32_t* records_d, uint32_t* warp_d, bpx_stream_t stream);
+int bpx_warp_apply(const float* x_d, const void* t_d, int t_dtype, int B, int Z, int Y, int X, int C, int Ct, const uint32_t* warp_d, int mode,
+                   float cval, float* x_out_d, void* t_out_d, bpx_stream_t stream);
+
 /* ---- random training patches from device-resident volumes (biapy_amd/sampler.py states the semantics; csrc/sampler.hip) ---------
  * V volumes stay on the device: image (Z,Y,X,C), 1 <= C <= 16, float32 / uint8 / uint16; target (Z,Y,X,Ct), 1 <= Ct <= 8, uint8 / float32;
  * 2-D data is Z = 1.  A call draws B patch origins and copies the B windows of Pz x Py x Px voxels into a (B,Pz,Py,Px,C) float32 batch
