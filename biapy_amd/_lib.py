@@ -66,6 +66,11 @@ _SIGS = {
     "bpx_warp_apply": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp], _i),
     "bpx_patch_draw": ([_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp], _i),
     "bpx_patch_gather": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp], _i),
+    "bpx_label_workspace": ([_i, _i, _i], _i64),
+    "bpx_label_u8": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp], _i),
+    "bpx_label_sizes": ([_vp, _i64, _i, _vp, _vp], _i),
+    "bpx_label_filter": ([_vp, _i64, _i, _vp, _i, _i, _vp, _vp], _i),
+    "bpx_debug_set_label_tiled": ([_i], _i),
     "bpx_scan_blocks": ([_i64], _i),
     "bpx_select_workspace": ([], _i64),
     "bpx_select_kth_f32": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),
@@ -206,7 +211,7 @@ def _load() -> C.CDLL:
     for env, hook in (("BPX_WGRAD_CAP", "bpx_debug_set_wgrad_cap"), ("BPX_WGRAD_K1", "bpx_debug_set_wgrad_k1"),
                       ("BPX_PW_STREAM", "bpx_debug_set_pw_stream"), ("BPX_C1_PERSIST", "bpx_debug_set_c1_persist"),
                       ("BPX_BWD_RS", "bpx_debug_set_bwd_rs"), ("BPX_FUSED_BITS", "bpx_debug_set_bwd_fused"),
-                      ("BPX_CT_BWD", "bpx_debug_set_convt_bwd")):
+                      ("BPX_CT_BWD", "bpx_debug_set_convt_bwd"), ("BPX_LABEL_TILED", "bpx_debug_set_label_tiled")):
         if os.environ.get(env) is not None:
             getattr(lib, hook)(int(os.environ[env]))
     return lib

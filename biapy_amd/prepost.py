@@ -9,7 +9,9 @@ percentiles / histogram on the host.
   (``bpx_select_kth_f32``) and the interpolation repeats NumPy's float32 ``_lerp`` arithmetic, so the bounds are bit-identical;
 * the histogram repeats ``np.histogram``'s float32 bin arithmetic (``bpx_histogram_f32``): identical counts, hence the
   identical Otsu threshold;
-* mean / std use double accumulation on the device (NumPy: float32 pairwise sums) - equal to ~1e-7 relative, not bitwise.
+* mean / std use double accumulation on the device (NumPy: float32 pairwise sums) - equal to ~1e-7 relative, not bitwise;
+* ``label`` / ``component_sizes`` / ``remove_small_objects`` carry on from the binarised mask: connected components with
+  ``scipy.ndimage.label``'s numbering bit for bit (``csrc/label.hip``), so the mask no longer leaves the device to be labelled.
 """
 from __future__ import annotations
 
@@ -160,3 +162,86 @@ def binarize(pred: torch.Tensor, threshold: Optional[float] = None) -> torch.Ten
     out = torch.empty(pred.shape, dtype=torch.uint8, device=pred.device)
     L.check(lib.bpx_threshold_u8(f.data_ptr(), f.numel(), th, out.data_ptr(), L.stream_ptr()))
     return out
+
+
+# ---- connected components of the binarised mask (csrc/label.hip) ----------------------------------------------------------------
+# What follows binarize() in every segmentation workflow of the reference: label(seed_map) ahead of the instance watershed, the
+# detection workflow's blobs, object counts and small-object removal of semantic masks (skimage.measure.label / scipy.ndimage.label
+# on the host there).  Watershed, matching and instance merging are not offered.
+
+def _label_volume(t: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    if t.dim() not in (2, 3):
+        raise ValueError(f"biapy_amd.prepost.{what} takes a 2-D (Y, X) or 3-D (Z, Y, X) tensor (got {t.dim()} dimensions)")
+    if t.numel() >= 2 ** 31:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: {t.numel()} voxels - volumes of 2^31 voxels or more are not supported (int32 indices)")
+    return (1,) + tuple(t.shape) if t.dim() == 2 else tuple(t.shape)
+
+
+def label(mask: torch.Tensor, connectivity: Optional[int] = None, return_num: bool = False):
+    """``skimage.measure.label(mask, connectivity=connectivity, return_num=return_num)`` of a binary 2-D / 3-D ``uint8`` or ``bool`` device
+    tensor: an ``int32`` tensor of the same shape, 0 for background, the components numbered ``1..N`` in raster order of each component's
+    first voxel - bit for bit ``scipy.ndimage.label(mask, generate_binary_structure(mask.ndim, connectivity))``.  ``connectivity`` 1 joins
+    faces, 2 faces and edges, 3 (3-D only) corners too; ``None`` is the full connectivity ``mask.ndim``.
+
+    Two differences from scikit-image, both on purpose: with ``return_num`` the count comes back as a 0-d ``int32`` DEVICE tensor, so the
+    call never waits for the device (it is a fixed sequence of six launches and can be captured in a graph); and the input is binary - every
+    nonzero value is foreground, regions of different nonzero values are NOT separated.  Other dtypes raise ``NotImplementedError``, as does
+    a volume of 2^31 voxels or more (before anything is launched); a CPU tensor raises ``RuntimeError``: there is no CPU path."""
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise NotImplementedError(f"biapy_amd.prepost.label works on uint8 or bool masks (got {mask.dtype}); binarize() makes one")
+    if not mask.is_cuda:
+        raise RuntimeError("biapy_amd.prepost runs on the MI355X only (tensor is on %s); there is no CPU path" % mask.device)
+    Z, Y, X = _label_volume(mask, "label")
+    c = mask.dim() if connectivity is None else int(connectivity)
+    if not 1 <= c <= mask.dim():
+        raise ValueError(f"connectivity must be in 1..{mask.dim()} for a {mask.dim()}-D mask (got {connectivity})")
+    m = mask.contiguous()
+    if m.dtype == torch.bool:
+        m = m.view(torch.uint8)
+    need = int(lib.bpx_label_workspace(Z, Y, X))
+    if need < 0:
+        raise NotImplementedError(f"biapy_amd.prepost.label: a {tuple(mask.shape)} volume is refused (an empty axis, or 2^31 voxels or more)")
+    ws = torch.empty(need, dtype=torch.uint8, device=m.device)
+    out = torch.empty(mask.shape, dtype=torch.int32, device=m.device)
+    num = torch.empty((), dtype=torch.int32, device=m.device)
+    L.check(lib.bpx_label_u8(m.data_ptr(), Z, Y, X, c, out.data_ptr(), num.data_ptr(), ws.data_ptr(), need, L.stream_ptr()))
+    return (out, num) if return_num else out
+
+
+def _labels(labels: torch.Tensor, what: str) -> torch.Tensor:
+    if labels.dtype != torch.int32:
+        raise NotImplementedError(f"biapy_amd.prepost.{what} works on the int32 labels of label() (got {labels.dtype})")
+    if not labels.is_cuda:
+        raise RuntimeError("biapy_amd.prepost runs on the MI355X only (tensor is on %s); there is no CPU path" % labels.device)
+    if labels.numel() < 1 or labels.numel() >= 2 ** 31:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: {labels.numel()} voxels - empty volumes and volumes of 2^31 voxels or more are not supported")
+    return labels
+
+
+def component_sizes(labels: torch.Tensor, num) -> torch.Tensor:
+    """``np.bincount(labels.ravel(), minlength=num + 1)[:num + 1]`` as an ``int32`` device tensor: entry 0 counts the background, entry ``l``
+    the voxels of component ``l``; labels above ``num`` are not counted.  ``num``: a Python int (no wait for the device; inside a graph an
+    upper bound of the count serves, the entries past ``N`` are 0), or the 0-d tensor ``label(..., return_num=True)`` returns, which is read
+    back here."""
+    lab = _labels(labels, "component_sizes").contiguous()
+    n_max = int(num)
+    if n_max < 0:
+        raise ValueError(f"num must not be negative (got {n_max})")
+    sizes = torch.empty(n_max + 1, dtype=torch.int32, device=lab.device)
+    L.check(lib.bpx_label_sizes(lab.data_ptr(), lab.numel(), n_max, sizes.data_ptr(), L.stream_ptr()))
+    return sizes
+
+
+def remove_small_objects(labels: torch.Tensor, min_size: int = 64, relabel: bool = False, num=None, return_num: bool = False):
+    """``skimage.morphology.remove_small_objects(labels, min_size)`` on an ``int32`` label image: a NEW tensor in which every component
+    with fewer than ``min_size`` voxels is 0.  The survivors keep their ids, as in scikit-image; ``relabel=True`` renumbers them ``1..N'`` in
+    the same order.  ``num``: the largest label (an int, or the device count of ``label``); ``None`` reads ``labels.max()`` back.
+    ``return_num`` adds ``N'``, the number of survivors, as a 0-d ``int32`` device tensor."""
+    lab = _labels(labels, "remove_small_objects")
+    n_max = int(lab.max()) if num is None else int(num)
+    sizes = component_sizes(lab, n_max)
+    out = lab.clone(memory_format=torch.contiguous_format)
+    left = torch.empty((), dtype=torch.int32, device=lab.device)
+    L.check(lib.bpx_label_filter(out.data_ptr(), out.numel(), n_max, sizes.data_ptr(), int(min_size), 1 if relabel else 0, left.data_ptr(),
+                                 L.stream_ptr()))
+    return (out, left) if return_num else out

@@ -797,6 +797,28 @@ int bpx_patch_draw(const bpx_patch_cfg* cfg, const bpx_patch_vol* vols_h, const 
 int bpx_patch_gather(const bpx_patch_vol* vols_h, const bpx_patch_vol* vols_d, int V, int img_dtype, int C, int tgt_dtype, int Ct, int Pz, int Py, int Px,
                      const int32_t* origins_d, int B, int use_scale, float scale, float* x_out_d, void* t_out_d, bpx_stream_t stream);
 
+/* ---- connected-component labelling of a binary volume (biapy_amd/prepost.py: label, component_sizes, remove_small_objects; csrc/label.hip) ----
+ * mask (Z,Y,X) uint8, contiguous, every nonzero byte foreground; 2-D is Z = 1.  connectivity 1 / 2 / 3: faces, + edges, + corners (6 / 18 / 26
+ * neighbours; 4 / 8 at Z = 1).  labels (Z,Y,X) int32: 0 background, components 1..N IN RASTER ORDER OF EACH COMPONENT'S FIRST VOXEL - bit for bit
+ * scipy.ndimage.label(mask, generate_binary_structure(ndim, connectivity)).  Union-find with integer atomics, labels_d itself the parent array:
+ * the same bits every run, a launch sequence fixed by (Z, Y, X, connectivity), nothing read back, capturable.  Z * Y * X < 2^31.
+ *   bpx_label_workspace : bytes of workspace bpx_label_u8 needs (4 per chunk of 4096 voxels); NEGATIVE when an extent is < 1 or the volume has
+ *                         2^31 voxels or more (refused: int32 indices).
+ *   bpx_label_u8        : labels_d = the labels, *num_d = N (device int32).  labels_d is the only voxel-sized array written.
+ *   bpx_label_sizes     : sizes_d[l] = number of the n voxels with label l for 0 <= l <= n_max (np.bincount(labels, minlength = n_max + 1) cut
+ *                         at n_max); labels outside [0, n_max] are not counted.
+ *   bpx_label_filter    : zeroes every component with fewer than min_size voxels (skimage.morphology.remove_small_objects on a label image).
+ *                         sizes_d: IN the sizes from bpx_label_sizes for the same n_max, OUT the id map applied (scratch).  relabel == 0 keeps the
+ *                         survivors' ids; relabel != 0 renumbers them 1..N' in the same order.  *num_out_d = N', the number of survivors (may be
+ *                         NULL).  Labels above n_max become 0.
+ * All entry points check their arguments on the host and return nonzero, with bpx_last_error naming the cause, before anything is launched. */
+int64_t bpx_label_workspace(int Z, int Y, int X);
+int bpx_label_u8(const uint8_t* mask_d, int Z, int Y, int X, int connectivity, int32_t* labels_d, int32_t* num_d, void* ws_d, int64_t ws_bytes,
+                 bpx_stream_t stream);
+int bpx_label_sizes(const int32_t* labels_d, int64_t n, int n_max, int32_t* sizes_d, bpx_stream_t stream);
+int bpx_label_filter(int32_t* labels_d, int64_t n, int n_max, int32_t* sizes_d, int min_size, int relabel, int32_t* num_out_d, bpx_stream_t stream);
+int bpx_debug_set_label_tiled(int on); /* test / A-B hook of bpx_label_u8's merge: 0 (default) = every union on global memory; 1 = tiles resolved in LDS, then unions across tile borders only; same bits (environment: BPX_LABEL_TILED) */
+
 #ifdef __cplusplus
 }
 #endif
