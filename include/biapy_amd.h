@@ -32,7 +32,9 @@ enum bpx_dtype { BPX_F32 = 0, BPX_BF16 = 1, BPX_F16 = 2, BPX_U8 = 3,
                   * its operands are activations. */
                  BPX_MIX16 = 4,
                  /* BPX_U16: unsigned 16-bit integers - the image of bpx_patch_gather only (a resident volume as the microscope stored it) */
-                 BPX_U16 = 5 };
+                 BPX_U16 = 5,
+                 /* BPX_I32: signed 32-bit integers - the label volume of bpx_edt only (what bpx_label_u8 writes) */
+                 BPX_I32 = 6 };
 /* Block activations (biapy/models/blocks.py:1973-1998, get_activation): codes 0-3 since round 1; round 4 adds leaky_relu (slope 0.01, nn.LeakyReLU's
  * default), gelu (nn.GELU(): the exact erf form), tanh, sigmoid and softplus (beta 1, threshold 20).  "softmax" as a block activation needs a
  * reduction over channels and is not a per-element prologue: not offered.  ELU (the reference default) has compile-time instances of every
@@ -818,6 +820,25 @@ int bpx_label_u8(const uint8_t* mask_d, int Z, int Y, int X, int connectivity, i
 int bpx_label_sizes(const int32_t* labels_d, int64_t n, int n_max, int32_t* sizes_d, bpx_stream_t stream);
 int bpx_label_filter(int32_t* labels_d, int64_t n, int n_max, int32_t* sizes_d, int min_size, int relabel, int32_t* num_out_d, bpx_stream_t stream);
 int bpx_debug_set_label_tiled(int on); /* test / A-B hook of bpx_label_u8's merge: 0 (default) = every union on global memory; 1 = tiles resolved in LDS, then unions across tile borders only; same bits (environment: BPX_LABEL_TILED) */
+
+/* ---- exact Euclidean distance transform of a mask or a label volume (biapy_amd/prepost.py: distance_transform_edt, label_distance; csrc/edt.hip) ----
+ * keys (Z,Y,X) contiguous, BPX_U8 or BPX_I32; 2-D is Z = 1.  key(v) = (value != 0) with label_mode == 0, the value itself otherwise.
+ *   out(v) = 0 where key(v) == 0, else the least |u - v|^2 over the voxels u with key(u) != key(v), |.| the Euclidean norm of the index
+ *   difference scaled per axis by sampling (host pointer to 3 doubles, z y x).  The volume border is no source.  Where the volume holds no
+ *   voxel of another key the result is a SENTINEL: INT32_MAX (int32 results), +inf (float32 results) - scipy.ndimage.distance_transform_edt
+ *   answers with distances to a fictitious point there.
+ * sampling == NULL, the integer path: exact.  squared != 0: out_d int32; else out_d float32 = float32(sqrt(float64(squared distance))), which
+ *   is scipy's float64 result rounded to float32 bit for bit.  out_d is the only voxel-sized array written (in place); Z^2 + Y^2 + X^2 must stay
+ *   below 2^31 - 1.  sampling given (positive, finite), the fp64 path: fp64 throughout, out_d float32 = the rounded distance, or its square.
+ * Three launches fixed by (Z, Y, X) and the path, no atomics, nothing read back, the same bits every run, capturable.  Z * Y * X < 2^31.
+ *   bpx_edt_workspace : bytes of workspace; NEGATIVE for a refused shape (an extent < 1, 2^31 voxels or more, the integer path's limit).
+ *                       Integer path: 8 * E, E = max(T(Z * X) * Y, T(Y * X) * Z) with T(columns) = min(131072, a quarter of the columns rounded
+ *                       up to 64) - the envelope stacks of the threads in flight of the Y and of the Z pass, never more than half the output's
+ *                       bytes plus one wave's share.  The fp64 path: 8 bytes per voxel + 16 * E.
+ * Argument checks run on the host before anything is launched and set bpx_last_error. */
+int64_t bpx_edt_workspace(int Z, int Y, int X, int fp64_path);
+int bpx_edt(const void* key_d, int key_dtype, int label_mode, int Z, int Y, int X, const double* sampling, int squared, void* out_d, void* ws_d,
+            int64_t ws_bytes, bpx_stream_t stream);
 
 #ifdef __cplusplus
 }
