@@ -20,6 +20,21 @@ __device__ __forceinline__ uint32_t fkey(float f) {  // monotone float -> uint32
 }
 __device__ __forceinline__ float fkey_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
+// Elements 4i .. 4i+3 of x: one 16-byte load where x allows it, four 4-byte loads otherwise (a contiguous view such as stack[1] of a tensor
+// with an odd element count per item is only 4-byte aligned).  Either way a thread owns the same four elements, so what a kernel sums or
+// counts - and the order it sums in - does not depend on the alignment.
+__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+__device__ __forceinline__ f32x4_t load4(const float* __restrict__ x, int64_t i, bool vec) {
+  if (vec) return reinterpret_cast<const f32x4_t*>(x)[i];
+  f32x4_t v;
+  v[0] = x[4 * i]; v[1] = x[4 * i + 1]; v[2] = x[4 * i + 2]; v[3] = x[4 * i + 3];
+  return v;
+}
+
+// min / max that keep a NaN once they have met one, in either operand (fminf / fmaxf drop it; ndarray.min() / .max() return it)
+__device__ __forceinline__ float nan_min(float a, float b) { return (b < a || b != b) ? b : a; }
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+
 struct SelectState { uint32_t prefix; uint32_t pad; unsigned long long k; unsigned long long hist[256]; };
 
 __global__ void __launch_bounds__(256) select_init_kernel(SelectState* st, unsigned long long k) {
@@ -35,8 +50,9 @@ __global__ void __launch_bounds__(256) select_hist_kernel(const float* __restric
   const uint32_t prefix = st->prefix;
   const uint32_t himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
   const int64_t n4 = n / 4;
+  const bool vec = aligned16(x);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const f32x4_t v = reinterpret_cast<const f32x4_t*>(x)[i];
+    const f32x4_t v = load4(x, i, vec);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const uint32_t key = fkey(v[e]);
@@ -71,28 +87,36 @@ __global__ void __launch_bounds__(256) select_pick_kernel(SelectState* st, int s
 }
 
 __global__ void __launch_bounds__(256) minmax_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ part) {
-  float mn = INFINITY, mx = -INFINITY;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+  float mn = INFINITY, mx = -INFINITY;          // a block (or a thread) that gets no element leaves these: neutral for the caller's reduction
+  const int64_t n4 = n / 4;
+  const bool vec = aligned16(x);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const f32x4_t v = load4(x, i, vec);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { mn = nan_min(mn, v[e]); mx = nan_max(mx, v[e]); }
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float v = x[i];
-    mn = fminf(mn, v); mx = fmaxf(mx, v);
+    mn = nan_min(mn, v); mx = nan_max(mx, v);
   }
 #pragma unroll
-  for (int m = 1; m < 64; m <<= 1) { mn = fminf(mn, __shfl_xor(mn, m, 64)); mx = fmaxf(mx, __shfl_xor(mx, m, 64)); }
+  for (int m = 1; m < 64; m <<= 1) { mn = nan_min(mn, __shfl_xor(mn, m, 64)); mx = nan_max(mx, __shfl_xor(mx, m, 64)); }
   __shared__ float r[4][2];
   if ((threadIdx.x & 63) == 0) { r[threadIdx.x >> 6][0] = mn; r[threadIdx.x >> 6][1] = mx; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = fminf(fminf(r[0][0], r[1][0]), fminf(r[2][0], r[3][0]));
-    part[2 * blockIdx.x + 1] = fmaxf(fmaxf(r[0][1], r[1][1]), fmaxf(r[2][1], r[3][1]));
+    part[2 * blockIdx.x] = nan_min(nan_min(r[0][0], r[1][0]), nan_min(r[2][0], r[3][0]));
+    part[2 * blockIdx.x + 1] = nan_max(nan_max(r[0][1], r[1][1]), nan_max(r[2][1], r[3][1]));
   }
 }
 
 // part[b] = sum over the block's elements of (x - center)^power, power 1 or 2, in double
 __global__ void __launch_bounds__(256) moment_kernel(const float* __restrict__ x, int64_t n, double center, int power, double* __restrict__ part) {
   double s = 0.0;
-  const int64_t n4 = (((uintptr_t)x & 15) == 0) ? n / 4 : 0;
+  const int64_t n4 = n / 4;
+  const bool vec = aligned16(x);                 // the same terms in the same order either way: the sums do not depend on the alignment
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const f32x4_t v = reinterpret_cast<const f32x4_t*>(x)[i];
+    const f32x4_t v = load4(x, i, vec);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const double d = (double)v[e] - center;
@@ -149,9 +173,15 @@ __global__ void __launch_bounds__(256) hist_uniform_kernel(const float* __restri
 
 __global__ void __launch_bounds__(256) threshold_kernel(const float* __restrict__ x, int64_t n, float thr, uint8_t* __restrict__ out) {
   const int64_t n4 = n / 4;
+  const bool vec = aligned16(x), packed = ((uintptr_t)out & 3) == 0;     // the four bytes go out as one word where `out` allows it
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const f32x4_t v = reinterpret_cast<const f32x4_t*>(x)[i];
-    reinterpret_cast<uint32_t*>(out)[i] = (v[0] > thr ? 1u : 0u) | (v[1] > thr ? 0x100u : 0u) | (v[2] > thr ? 0x10000u : 0u) | (v[3] > thr ? 0x1000000u : 0u);
+    const f32x4_t v = load4(x, i, vec);
+    if (packed) {
+      reinterpret_cast<uint32_t*>(out)[i] = (v[0] > thr ? 1u : 0u) | (v[1] > thr ? 0x100u : 0u) | (v[2] > thr ? 0x10000u : 0u) | (v[3] > thr ? 0x1000000u : 0u);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) out[4 * i + e] = v[e] > thr ? 1 : 0;
+    }
   }
   if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) out[n4 * 4 + threadIdx.x] = x[n4 * 4 + threadIdx.x] > thr ? 1 : 0;
 }
@@ -175,7 +205,7 @@ extern "C" int bpx_select_kth_f32(const float* x_d, int64_t n, int64_t k, float*
   const char* fn = "bpx_select_kth_f32";
   BPX_CHECK(x_d && out_d && ws_d, "%s: null pointer", fn);
   BPX_CHECK(n > 0 && k >= 0 && k < n, "%s: rank %lld outside [0, %lld)", fn, (long long)k, (long long)n);
-  BPX_CHECK(((uintptr_t)x_d & 15) == 0 && ((uintptr_t)ws_d & 7) == 0, "%s: x must be 16-byte aligned, the workspace 8-byte aligned", fn);
+  BPX_CHECK(((uintptr_t)x_d & 3) == 0 && ((uintptr_t)ws_d & 7) == 0, "%s: x must be 4-byte aligned, the workspace 8-byte aligned", fn);
   hipStream_t s = (hipStream_t)stream;
   SelectState* st = reinterpret_cast<SelectState*>(ws_d);
   select_init_kernel<<<1, 256, 0, s>>>(st, (unsigned long long)k);
@@ -219,7 +249,6 @@ extern "C" int bpx_histogram_f32(const float* x_d, int64_t n, float first_edge, 
 extern "C" int bpx_threshold_u8(const float* x_d, int64_t n, float thr, uint8_t* out_d, bpx_stream_t stream) {
   const char* fn = "bpx_threshold_u8";
   BPX_CHECK(x_d && out_d && n > 0, "%s: bad arguments", fn);
-  BPX_CHECK((((uintptr_t)x_d) & 15) == 0 && (((uintptr_t)out_d) & 3) == 0, "%s: x must be 16-byte, out 4-byte aligned", fn);
   threshold_kernel<<<blocks_for(n / 4), 256, 0, (hipStream_t)stream>>>(x_d, n, thr, out_d);
   BPX_LAUNCH_CHECK(fn);
   return 0;

@@ -14,6 +14,16 @@ percentiles / histogram on the host.
   ``scipy.ndimage.label``'s numbering bit for bit (``csrc/label.hip``), so the mask no longer leaves the device to be labelled;
 * ``distance_transform_edt`` / ``label_distance`` give the exact Euclidean distance map of the mask or of the labels
   (``csrc/edt.hip``): on a unit grid ``scipy.ndimage.distance_transform_edt`` bit for bit.
+
+Any contiguous float32 tensor is taken as it is, 16-byte aligned or not (``stack[1]`` of a batch with an odd element count per item is not):
+the scans then read four 4-byte words where they would read one 16-byte word, and return the same bits.
+
+NaN.  ``minmax`` returns ``(nan, nan)`` as soon as the data holds one NaN, as ``ndarray.min()`` / ``.max()`` do; ``histogram``, and with it
+``threshold_otsu`` / ``binarize`` without a given threshold, then raise ``ValueError`` as ``np.histogram`` does for a range that is not
+finite (an infinity in the data does the same), and such data never counts as binary.  ``mean_std`` and the normalisation carry the NaN
+through, as NumPy.  ``kth_values`` / ``percentile`` / ``percentile_clip`` on data with NaN are UNSPECIFIED (NumPy returns NaN; the radix
+select ranks a NaN by its bit pattern, beyond the infinities of its sign), and the class arg-max never lets a NaN win where ``np.argmax``
+returns the first NaN (``csrc/prepost.hip``).
 """
 from __future__ import annotations
 
@@ -52,12 +62,16 @@ def percentile(x: torch.Tensor, q: float) -> float:
     NumPy's arithmetic repeated operation by operation.  For a float32 array NumPy (>= 2) works in float32 throughout:
     ``quantile = q / float32(100)``, virtual index ``(n - 1) * quantile``, ``gamma = index - floor(index)`` and the ``_lerp``
     ``a + (b - a) * gamma`` (``b - (b - a) * (1 - gamma)`` for gamma >= 0.5) - numpy/lib/_function_base_impl.py."""
-    n = x.numel()
+    return _percentile_of(x.numel(), q, lambda ranks: kth_values(x, ranks))
+
+
+def _percentile_of(n: int, q: float, kth) -> float:
+    """The host arithmetic of ``percentile`` on its own: ``kth(ranks)`` returns the order statistics at the two ranks asked for."""
     vi = np.float32(n - 1) * (np.float32(q) / np.float32(100))
     lo = int(math.floor(float(vi)))
     hi = min(lo + 1, n - 1)
     t = np.float32(vi - np.float32(lo))
-    a, b = (np.float32(v) for v in kth_values(x, [lo, hi]))
+    a, b = (np.float32(v) for v in kth([lo, hi]))
     d = np.float32(b - a)
     if t >= 0.5:
         return float(np.float32(b - np.float32(d * np.float32(np.float32(1) - t))))
@@ -131,12 +145,27 @@ def zero_mean_unit_variance_normalization(data: torch.Tensor, mean: Optional[flo
 
 def histogram(x: torch.Tensor, nbins: int = 256) -> Tuple[np.ndarray, np.ndarray]:
     """``np.histogram(x, bins=nbins, range=(x.min(), x.max()))`` of a float32 tensor: (counts int64, float32 edges)."""
-    f = _flat(x)
-    mn, mx = minmax(x)
+    return _histogram(x, nbins, *minmax(x))
+
+
+def _bin_edges(mn: float, mx: float, nbins: int) -> np.ndarray:
+    """The float32 edge table ``np.histogram`` builds for ``range=(mn, mx)``, and its two refusals: a range that is not finite (a NaN or an
+    infinity in the data) and edges that float32 cannot keep strictly increasing - counting into duplicate edges would be meaningless."""
     first, last = np.float32(mn), np.float32(mx)
+    if not (np.isfinite(first) and np.isfinite(last)):
+        raise ValueError(f"autodetected range of [{first}, {last}] is not finite")
     if first == last:                                    # numpy widens an empty range by +-0.5
         first, last = np.float32(first - np.float32(0.5)), np.float32(last + np.float32(0.5))
     edges = np.linspace(first, last, nbins + 1, endpoint=True, dtype=np.float32)
+    if np.any(edges[:-1] >= edges[1:]):
+        raise ValueError(f"Too many bins for data range. Cannot create {nbins} finite-sized bins.")
+    return edges
+
+
+def _histogram(x: torch.Tensor, nbins: int, mn: float, mx: float) -> Tuple[np.ndarray, np.ndarray]:
+    f = _flat(x)
+    edges = _bin_edges(mn, mx, nbins)                    # refuses before anything is launched
+    first, last = edges[0], edges[-1]
     ed = torch.from_numpy(edges).to(f.device)
     counts = torch.zeros(nbins, dtype=torch.int64, device=f.device)
     L.check(lib.bpx_histogram_f32(f.data_ptr(), f.numel(), float(first), float(last), nbins, ed.data_ptr(), counts.data_ptr(), L.stream_ptr()))
@@ -146,9 +175,10 @@ def histogram(x: torch.Tensor, nbins: int = 256) -> Tuple[np.ndarray, np.ndarray
 def threshold_otsu(x: torch.Tensor, nbins: int = 256) -> float:
     """skimage.filters.threshold_otsu on the device histogram (Otsu 1979: arg-max of the between-class variance over the
     bin centres).  The counts are bit-identical to np.histogram's, the few float64 operations below follow scikit-image."""
-    counts, edges = histogram(x, nbins)
-    if float(edges[0]) == float(edges[-1]):
-        return float(edges[0])
+    mn, mx = minmax(x)
+    if mn == mx:                                         # a constant volume (a blank tile): the value itself, so `x > th` is empty - as scikit-image
+        return float(mn)
+    counts, edges = _histogram(x, nbins, mn, mx)
     centers = (edges[:-1] + edges[1:]) / 2
     c = counts.astype(np.float64)
     w1, w2 = np.cumsum(c), np.cumsum(c[::-1])[::-1]

@@ -623,13 +623,15 @@ int bpx_gate_mul_bwd(int dtype, int64_t total_voxels, bpx_tensor dy, bpx_tensor 
  * Input normalisation (biapy/data/norm.py: percentile_clip :395-473 -> np.percentile, zero_mean_unit_variance_normalization
  * :586-645) and the Otsu binarisation after the merge (biapy/engine/semantic_seg.py:418-431) on volumes that live on the device.
  *   bpx_select_kth_f32 : exact k-th smallest element (0-based), 4-pass radix select, result written to out_d (device float)
- *   bpx_minmax_f32     : per-block {min, max} partials, bpx_scan_blocks(n) rows
+ *   bpx_minmax_f32     : per-block {min, max} partials, bpx_scan_blocks(n) rows; a NaN in a block's share makes both of its partials NaN,
+ *                        a block without a share writes {+inf, -inf}
  *   bpx_moment_f32     : per-block partial sums of (x - center)^power in double (power 1 or 2), bpx_scan_blocks(n) rows
  *   bpx_histogram_f32  : np.histogram(a, bins=nbins, range=(first, last)) of a float32 array, bit-identical counts;
  *                        edges_d = the float32 edge table NumPy builds (np.linspace(first, last, nbins + 1, dtype=float32));
  *                        counts_d (uint64[nbins]) is ACCUMULATED into (zero it first)
  *   bpx_threshold_u8   : out = x > thr
- *   bpx_clip_affine_f32: out = (clip(x, lo, hi) - sub) / div in float32 operations */
+ *   bpx_clip_affine_f32: out = (clip(x, lo, hi) - sub) / div in float32 operations
+ * x_d needs the 4-byte alignment of a float only: 16-byte loads are used where it allows them, and the results do not depend on it. */
 int bpx_scan_blocks(int64_t n);
 int64_t bpx_select_workspace(void);
 int bpx_select_kth_f32(const float* x_d, int64_t n, int64_t k, float* out_d, void* ws_d, bpx_stream_t stream);
