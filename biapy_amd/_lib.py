@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("BPX_LIB_PATH") or os.path.join(_HERE, "libbiapy_amd.s
 F32, BF16, F16, U8, MIX16 = 0, 1, 2, 3, 4   # MIX16: backward entries only - fp16 activations, bf16 gradients (include/biapy_amd.h)
 # block activations of the reference (blocks.py:1973-1998): every entry of get_activation except "softmax" (a channel reduction, not a per-element prologue)
 U16 = 5                                      # the image of bpx_patch_gather only
-I32 = 6                                      # the label volume of bpx_edt only
+I32 = 6                                      # the label volume of bpx_edt and the int32 image of bpx_watershed only
 ACT = {"none": 0, "linear": 0, "elu": 1, "relu": 2, "silu": 3, "leaky_relu": 4, "gelu": 5, "tanh": 6, "sigmoid": 7, "softplus": 8}
 PK_K3, PK_K3_T, PK_K1, PK_DENSE, PK_DENSE_T, PK_CT, PK_CT_T, PK_CT4, PK_CT4_T = range(9)
 
@@ -74,6 +74,8 @@ _SIGS = {
     "bpx_debug_set_label_tiled": ([_i], _i),
     "bpx_edt_workspace": ([_i, _i, _i, _i], _i64),
     "bpx_edt": ([_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp, _i64, _vp], _i),
+    "bpx_watershed_workspace": ([_i, _i, _i], _i64),
+    "bpx_watershed": ([_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp], _i),
     "bpx_scan_blocks": ([_i64], _i),
     "bpx_select_workspace": ([], _i64),
     "bpx_select_kth_f32": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),

@@ -33,7 +33,7 @@ enum bpx_dtype { BPX_F32 = 0, BPX_BF16 = 1, BPX_F16 = 2, BPX_U8 = 3,
                  BPX_MIX16 = 4,
                  /* BPX_U16: unsigned 16-bit integers - the image of bpx_patch_gather only (a resident volume as the microscope stored it) */
                  BPX_U16 = 5,
-                 /* BPX_I32: signed 32-bit integers - the label volume of bpx_edt only (what bpx_label_u8 writes) */
+                 /* BPX_I32: signed 32-bit integers - the label volume of bpx_edt (what bpx_label_u8 writes) and the image of bpx_watershed only */
                  BPX_I32 = 6 };
 /* Block activations (biapy/models/blocks.py:1973-1998, get_activation): codes 0-3 since round 1; round 4 adds leaky_relu (slope 0.01, nn.LeakyReLU's
  * default), gelu (nn.GELU(): the exact erf form), tanh, sigmoid and softplus (beta 1, threshold 20).  "softmax" as a block activation needs a
@@ -841,6 +841,25 @@ int bpx_debug_set_label_tiled(int on); /* test / A-B hook of bpx_label_u8's merg
 int64_t bpx_edt_workspace(int Z, int Y, int X, int fp64_path);
 int bpx_edt(const void* key_d, int key_dtype, int label_mode, int Z, int Y, int X, const double* sampling, int squared, void* out_d, void* ws_d,
             int64_t ws_bytes, bpx_stream_t stream);
+
+/* ---- seeded watershed of an image from a marker volume (biapy_amd/prepost.py: watershed; csrc/watershed.hip, csrc/watershed_core.h) ----
+ * image (Z,Y,X) BPX_F32 or BPX_I32, markers (Z,Y,X) int32, mask (Z,Y,X) uint8 or NULL (every voxel), all contiguous; 2-D is Z = 1.
+ *   nodes: the voxels with mask != 0.  edges: two nodes that are neighbours at `connectivity` (1 / 2 / 3 as bpx_label_u8).  weight of an edge:
+ *   max(k(u), k(v)), k the order-preserving uint32 image of the value (int32: v + 2^31; float32: the sign-flip map, -0.0 < +0.0; NaN unspecified).
+ *   Strict total order of the edges: (weight, linear index of the raster-first endpoint u, rank of the offset among u's forward offsets in
+ *   (dz, dy, dx) lexicographic order).  A voxel with markers > 0 inside the mask is seeded with that label; other markers are ignored.
+ *   out (Z,Y,X) int32 = the label of the voxel's tree in the unique minimum spanning forest in which no tree holds two seeds (Kruskal in that
+ *   order, joining two trees unless they are the same or both seeded); 0 where the tree holds no seed and outside the mask.  Ties of the image go
+ *   to the raster-first edge.  Not scikit-image's tie-breaking (the age of a heap entry), no compactness, no watershed line.
+ * Boruvka rounds on the union-find of the labelling: 4 R + 3 launches with R = ceil(log2(max(n, 2))) + 1, fixed by (Z, Y, X, connectivity); rounds
+ * after the last one that joined anything return at once.  *rounds_d (device int32) = the number of rounds that did.  Integer atomics only: the
+ * same bits every run; nothing read back; capturable.  Z * Y * X < 2^31.
+ *   bpx_watershed_workspace : bytes of workspace: 12 per voxel (8 the pick of a tree, 4 its parent) + the round flags; NEGATIVE when an extent is
+ *                             < 1 or the volume has 2^31 voxels or more.  12.9 GB at 1024^3.
+ * Argument checks run on the host before anything is launched and set bpx_last_error. */
+int64_t bpx_watershed_workspace(int Z, int Y, int X);
+int bpx_watershed(const void* image_d, int image_dtype, const int32_t* markers_d, const uint8_t* mask_d, int Z, int Y, int X, int connectivity,
+                  int32_t* out_d, int32_t* rounds_d, void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
 
 #ifdef __cplusplus
 }
