@@ -76,6 +76,9 @@ _SIGS = {
     "bpx_edt": ([_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp, _i64, _vp], _i),
     "bpx_watershed_workspace": ([_i, _i, _i], _i64),
     "bpx_watershed": ([_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp], _i),
+    "bpx_overlap_workspace": ([_i64], _i64),
+    "bpx_label_overlap": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp], _i),
+    "bpx_debug_set_overlap_per_voxel": ([_i], _i),
     "bpx_scan_blocks": ([_i64], _i),
     "bpx_select_workspace": ([], _i64),
     "bpx_select_kth_f32": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),
@@ -216,7 +219,8 @@ def _load() -> C.CDLL:
     for env, hook in (("BPX_WGRAD_CAP", "bpx_debug_set_wgrad_cap"), ("BPX_WGRAD_K1", "bpx_debug_set_wgrad_k1"),
                       ("BPX_PW_STREAM", "bpx_debug_set_pw_stream"), ("BPX_C1_PERSIST", "bpx_debug_set_c1_persist"),
                       ("BPX_BWD_RS", "bpx_debug_set_bwd_rs"), ("BPX_FUSED_BITS", "bpx_debug_set_bwd_fused"),
-                      ("BPX_CT_BWD", "bpx_debug_set_convt_bwd"), ("BPX_LABEL_TILED", "bpx_debug_set_label_tiled")):
+                      ("BPX_CT_BWD", "bpx_debug_set_convt_bwd"), ("BPX_LABEL_TILED", "bpx_debug_set_label_tiled"),
+                      ("BPX_OVERLAP_PER_VOXEL", "bpx_debug_set_overlap_per_voxel")):
         if os.environ.get(env) is not None:
             getattr(lib, hook)(int(os.environ[env]))
     return lib

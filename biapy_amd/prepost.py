@@ -15,7 +15,9 @@ percentiles / histogram on the host.
 * ``distance_transform_edt`` / ``label_distance`` give the exact Euclidean distance map of the mask or of the labels
   (``csrc/edt.hip``): on a unit grid ``scipy.ndimage.distance_transform_edt`` bit for bit;
 * ``watershed`` floods an image from the seeds of ``label`` inside a mask (``csrc/watershed.hip``): the marker-controlled watershed those two
-  lead up to, with exactly stated semantics of its own (ties go to the raster-first edge) - product-defined, checked against a host twin.
+  lead up to, with exactly stated semantics of its own (ties go to the raster-first edge) - product-defined, checked against a host twin;
+* ``label_overlap`` / ``matching`` judge the instances: the sparse contingency table of two label volumes (``csrc/overlap.hip``) and the
+  reference's IoU matcher (tp / fp / fn, F1, panoptic quality) on top of it, with only the table's rows leaving the device.
 
 Any contiguous float32 tensor is taken as it is, 16-byte aligned or not (``stack[1]`` of a batch with an odd element count per item is not):
 the scans then read four 4-byte words where they would read one 16-byte word, and return the same bits.
@@ -202,7 +204,7 @@ def binarize(pred: torch.Tensor, threshold: Optional[float] = None) -> torch.Ten
 # ---- connected components of the binarised mask (csrc/label.hip) ----------------------------------------------------------------
 # What follows binarize() in every segmentation workflow of the reference: label(seed_map) ahead of the instance watershed, the
 # detection workflow's blobs, object counts and small-object removal of semantic masks (skimage.measure.label / scipy.ndimage.label
-# on the host there).  The watershed is watershed() below; matching and instance merging are not offered.
+# on the host there).  The watershed is watershed() below, the matcher matching() at the end; instance merging is not offered.
 
 def _label_volume(t: torch.Tensor, what: str) -> Tuple[int, int, int]:
     if t.dim() not in (2, 3):
@@ -418,3 +420,151 @@ def watershed(image: torch.Tensor, markers: torch.Tensor, mask: Optional[torch.T
     L.check(lib.bpx_watershed(img.data_ptr(), L.F32 if img.dtype == torch.float32 else L.I32, mk.data_ptr(), L.ptr(m), Z, Y, X, c, out.data_ptr(),
                               rounds.data_ptr(), ws.data_ptr(), need, L.stream_ptr()))
     return (out, rounds) if return_rounds else out
+
+
+# ---- sparse overlap table of two label volumes and the instance matcher on top of it (csrc/overlap.hip) -----------------------------------------
+# What judges the instances the steps above produce: the reference's biapy/utils/matching.py (the StarDist matcher) builds a dense
+# (1 + max_true) x (1 + max_pred) overlap matrix in a host loop, turns it into IoU and runs scipy's linear_sum_assignment over all of it.  Here
+# the table is sparse and built on the device; only its K rows come back.  Not offered: the criteria "iot" / "iop", report_matches and
+# matching_dataset's aggregation over images; instance merging across chunk faces (it can start from label_overlap of the two faces).
+
+def _overlap_inputs(a: torch.Tensor, b: torch.Tensor, max_pairs, what: str):
+    for t in (a, b):
+        if t.dtype != torch.int32:
+            raise NotImplementedError(f"biapy_amd.prepost.{what} works on the int32 labels of label() / watershed() (got {t.dtype})")
+    if a.shape != b.shape:
+        raise ValueError(f"biapy_amd.prepost.{what}: the two label tensors must have the same shape (got {tuple(a.shape)}, {tuple(b.shape)})")
+    if a.dim() < 1:
+        raise ValueError(f"biapy_amd.prepost.{what} takes tensors of rank 1 or more (got a 0-d tensor)")
+    if max_pairs is not None and int(max_pairs) < 1:
+        raise ValueError(f"max_pairs must be at least 1 (got {max_pairs})")
+    n = a.numel()
+    if n < 1 or n >= 2 ** 31:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: {n} voxels - empty volumes and volumes of 2^31 voxels or more are not supported")
+    mp = min(n, 2 ** 21) if max_pairs is None else int(max_pairs)
+    need = int(lib.bpx_overlap_workspace(mp))
+    if need < 0:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: max_pairs = {mp} is refused (the table would pass 2^31 slots)")
+    for t in (a, b):
+        if not t.is_cuda:
+            raise RuntimeError("biapy_amd.prepost runs on the MI355X only (tensor is on %s); there is no CPU path" % t.device)
+    return mp, need
+
+
+def label_overlap(a: torch.Tensor, b: torch.Tensor, max_pairs: Optional[int] = None):
+    """The sparse contingency table of two ``int32`` label tensors of the same shape (any rank >= 1; views are taken via ``.contiguous()``): every
+    distinct pair ``(a[i], b[i])`` with the number of voxels that carry it, the pairs with background included.  A label ``<= 0`` counts as
+    background 0, as ``watershed`` treats its markers.  Returns ``(pairs, counts, num)``:
+
+    * ``pairs``: ``int32`` of shape ``(max_pairs, 2)``, SORTED by ``(a, b)``; the rows from ``num`` onward are ``(-1, -1)``;
+    * ``counts``: ``int32`` of shape ``(max_pairs,)``, 0 from ``num`` onward;
+    * ``num``: the number ``K`` of distinct pairs as a 0-d ``int32`` DEVICE tensor, ``-1`` when there are more than ``max_pairs`` of them (the
+      other two results are then unspecified).
+
+    ``pairs[:K]`` / ``counts[:K]`` equal ``np.unique`` (with counts) of the packed keys ``a << 32 | b`` bit for bit.  ``max_pairs`` defaults to
+    ``min(n, 2**21)``: the table has the power of two ``>= 2 * max_pairs`` slots of 12 bytes, 48 MB at the default.  Three launches fixed by
+    ``(n, max_pairs)`` and one ``torch.sort`` of the fixed-size key array: nothing is read back, two runs give the same bits, the call can be
+    captured in a graph.
+
+    Refused before anything is launched: a CPU tensor (``RuntimeError``); other dtypes, an empty tensor, 2^31 voxels or more and a ``max_pairs``
+    whose table would pass 2^31 slots (``NotImplementedError``); shapes that differ and ``max_pairs < 1`` (``ValueError``)."""
+    mp, need = _overlap_inputs(a, b, max_pairs, "label_overlap")
+    fa, fb = a.contiguous(), b.contiguous()
+    ws = torch.empty(need, dtype=torch.uint8, device=fa.device)
+    keys = torch.empty(mp, dtype=torch.int64, device=fa.device)
+    counts = torch.empty(mp, dtype=torch.int32, device=fa.device)
+    num = torch.empty((), dtype=torch.int32, device=fa.device)
+    L.check(lib.bpx_label_overlap(fa.data_ptr(), fb.data_ptr(), fa.numel(), mp, keys.data_ptr(), counts.data_ptr(), num.data_ptr(), ws.data_ptr(),
+                                  need, L.stream_ptr()))
+    keys, order = torch.sort(keys)                       # the keys are distinct but for the INT64_MAX filler, whose counts are all 0
+    counts = counts[order]
+    filler = keys == torch.iinfo(torch.int64).max
+    pairs = torch.stack((keys >> 32, keys & 0xFFFFFFFF), dim=1).masked_fill(filler[:, None], -1).to(torch.int32)
+    return pairs, counts, num
+
+
+def _safe_divide(x: float, y: float, eps: float = 1e-10) -> float:
+    return x / y if abs(y) > eps else 0.0
+
+
+def _match_stats(pairs, counts, thresh):
+    """The reference's ``matching()`` (criterion "iou") from the sparse overlap table alone - a pure host function, no tensors: ``pairs`` (K, 2)
+    label pairs with background 0, ``counts`` (K,) voxels per pair, ``thresh`` one threshold.  Areas are the row and column sums of the table;
+    ``n_true`` / ``n_pred`` the distinct positive labels present (they need not be sequential); IoU = c / (|a| + |b| - c) in float64 over the
+    positive pairs; the reference's cost ``-(iou >= thr) - iou / (2 * min(n_true, n_pred))`` is minimised with
+    ``scipy.optimize.linear_sum_assignment`` PER CONNECTED BLOCK of the overlap graph: two labels that share no voxel have cost 0, no cost is
+    positive, so an optimum of the dense problem is a union of optima of the blocks and the dense matrix over all labels is never built."""
+    try:
+        from scipy.optimize import linear_sum_assignment
+    except ImportError as e:
+        raise ImportError("biapy_amd.prepost.matching needs scipy (scipy.optimize.linear_sum_assignment), which is not installed") from e
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    c = np.asarray(counts, dtype=np.int64).reshape(-1)
+    thr = float(thresh)
+    ut, it = np.unique(pairs[:, 0], return_inverse=True)
+    up, ip = np.unique(pairs[:, 1], return_inverse=True)
+    area_t, area_p = np.zeros(ut.size, np.int64), np.zeros(up.size, np.int64)
+    np.add.at(area_t, it, c)
+    np.add.at(area_p, ip, c)
+    n_true, n_pred = int((ut > 0).sum()), int((up > 0).sum())
+    n_matched = min(n_true, n_pred)
+    pos = (pairs[:, 0] > 0) & (pairs[:, 1] > 0) & (c > 0)
+    rows, cols, cc = it[pos], ip[pos], c[pos]
+    iou = cc.astype(np.float64) / (area_t[rows] + area_p[cols] - cc).astype(np.float64)
+    tp, sum_matched = 0, 0.0
+    if n_matched > 0 and iou.size and bool((iou >= thr).any()):
+        # connected blocks of the bipartite overlap graph: union-find over (true rows, pred columns), path halving
+        parent = np.arange(ut.size + up.size)
+
+        def find(i):
+            while parent[i] != i:
+                parent[i] = parent[parent[i]]
+                i = parent[i]
+            return i
+
+        for r, q in zip(rows.tolist(), (cols + ut.size).tolist()):
+            ra, rb = find(r), find(q)
+            if ra != rb:
+                parent[max(ra, rb)] = min(ra, rb)
+        block = np.array([find(r) for r in rows.tolist()])
+        for root in np.unique(block[iou >= thr]):        # a block without a pair at the threshold holds no match that counts
+            sel = block == root
+            br, bq, bi = rows[sel], cols[sel], iou[sel]
+            lr, jr = np.unique(br, return_inverse=True)
+            lq, jq = np.unique(bq, return_inverse=True)
+            score = np.zeros((lr.size, lq.size), np.float64)
+            score[jr, jq] = bi
+            cost = -(score >= thr).astype(np.float64) - score / (2 * n_matched)
+            ti, pi = linear_sum_assignment(cost)
+            ok = score[ti, pi] >= thr
+            tp += int(np.count_nonzero(ok))
+            sum_matched += float(np.sum(score[ti, pi][ok]))
+    fp, fn = n_pred - tp, n_true - tp
+    return dict(criterion="iou", thresh=thresh, fp=fp, tp=tp, fn=fn,
+                precision=tp / (tp + fp) if tp > 0 else 0, recall=tp / (tp + fn) if tp > 0 else 0,
+                accuracy=tp / (tp + fp + fn) if tp > 0 else 0, f1=(2 * tp) / (2 * tp + fp + fn) if tp > 0 else 0,
+                n_true=n_true, n_pred=n_pred, mean_true_score=_safe_divide(sum_matched, n_true), mean_matched_score=_safe_divide(sum_matched, tp),
+                panoptic_quality=_safe_divide(sum_matched, tp + fp / 2 + fn / 2))
+
+
+def matching(y_true: torch.Tensor, y_pred: torch.Tensor, thresh=0.5, criterion: str = "iou", max_pairs: Optional[int] = None):
+    """The reference's ``matching(y_true, y_pred, thresh, criterion)`` (``biapy/utils/matching.py``, the StarDist matcher) on two ``int32`` label
+    tensors that stay on the device: a dict with the reference's keys - ``criterion, thresh, fp, tp, fn, precision, recall, accuracy, f1, n_true,
+    n_pred, mean_true_score, mean_matched_score, panoptic_quality`` - or, for a sequence of thresholds, a list of them.  ``label_overlap`` builds
+    the sparse table on the device, its ``K`` rows (kilobytes) are read back, the assignment is solved on the host per connected block of the
+    overlap graph (``_match_stats``).  Labels need not be sequential; an empty ``y_true`` or ``y_pred`` gives the reference's zeros.
+
+    Only ``criterion="iou"`` is offered (others raise ``NotImplementedError``).  More than ``max_pairs`` distinct pairs (default
+    ``min(n, 2**21)``) raise ``RuntimeError``: call again with a larger ``max_pairs``.  The refusals of ``label_overlap`` apply; ``scipy`` is
+    imported here, not with the package, and its absence raises ``ImportError``."""
+    if criterion != "iou":
+        raise NotImplementedError(f"biapy_amd.prepost.matching offers criterion 'iou' only (got {criterion!r})")
+    mp, _ = _overlap_inputs(y_true, y_pred, max_pairs, "matching")
+    pairs, counts, num = label_overlap(y_true, y_pred, mp)
+    k = int(num)
+    if k < 0:
+        raise RuntimeError(f"biapy_amd.prepost.matching: the two volumes hold more than max_pairs = {mp} distinct label pairs; pass a larger max_pairs")
+    p, c = pairs[:k].cpu().numpy(), counts[:k].cpu().numpy()
+    if np.isscalar(thresh):
+        return _match_stats(p, c, thresh)
+    return [_match_stats(p, c, t) for t in thresh]

@@ -861,6 +861,22 @@ int64_t bpx_watershed_workspace(int Z, int Y, int X);
 int bpx_watershed(const void* image_d, int image_dtype, const int32_t* markers_d, const uint8_t* mask_d, int Z, int Y, int X, int connectivity,
                   int32_t* out_d, int32_t* rounds_d, void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
 
+/* ---- sparse overlap (contingency) table of two label volumes (biapy_amd/prepost.py: label_overlap, matching; csrc/overlap.hip, csrc/overlap_core.h) ----
+ * a, b: n contiguous int32 labels each, 1 <= n < 2^31; a label <= 0 counts as background 0 (as the markers of bpx_watershed).  The result is
+ * every distinct pair (a[i], b[i]) with the number of voxels that carry it, background pairs included: keys_d[k] = a << 32 | b (int64),
+ * counts_d[k] the count, for k in [0, K) in UNSPECIFIED order; the entries [K, max_pairs) are INT64_MAX and 0; *num_d (device int32) = K.
+ * With more than max_pairs distinct pairs *num_d = -1, the call returns normally and keys_d / counts_d are unspecified.
+ * An open-addressing table of the power of two >= 2 * max_pairs slots (64-bit key claimed by compare-and-swap, 32-bit count by atomic add) in the
+ * workspace; a wave run-length-compresses a span of 8192 voxels, carries the open run in registers and counts into its block's 512-slot table in
+ * LDS, which is added to the global table once per block: a uniform block costs one global update.
+ * Three launches (clear, count, compact) fixed by (n, max_pairs); integer atomics only; nothing read back; capturable.
+ *   bpx_overlap_workspace : bytes of workspace: 12 per slot + 16; NEGATIVE when max_pairs < 1 or the table would pass 2^31 slots (max_pairs > 2^30).
+ * Argument checks run on the host before anything is launched and set bpx_last_error. */
+int64_t bpx_overlap_workspace(int64_t max_pairs);
+int bpx_label_overlap(const int32_t* a_d, const int32_t* b_d, int64_t n, int64_t max_pairs, int64_t* keys_d, int32_t* counts_d, int32_t* num_d,
+                      void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
+int bpx_debug_set_overlap_per_voxel(int on); /* timing hook of bpx_label_overlap's count pass: 0 (default) = spans, run lengths and the carried run; 1 = one table insert per voxel; the same table (environment: BPX_OVERLAP_PER_VOXEL) */
+
 #ifdef __cplusplus
 }
 #endif
