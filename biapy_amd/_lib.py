@@ -79,6 +79,8 @@ _SIGS = {
     "bpx_overlap_workspace": ([_i64], _i64),
     "bpx_label_overlap": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp], _i),
     "bpx_debug_set_overlap_per_voxel": ([_i], _i),
+    "bpx_region_props": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "bpx_debug_set_regionprops_local": ([_i], _i),
     "bpx_scan_blocks": ([_i64], _i),
     "bpx_select_workspace": ([], _i64),
     "bpx_select_kth_f32": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),
@@ -220,7 +222,8 @@ def _load() -> C.CDLL:
                       ("BPX_PW_STREAM", "bpx_debug_set_pw_stream"), ("BPX_C1_PERSIST", "bpx_debug_set_c1_persist"),
                       ("BPX_BWD_RS", "bpx_debug_set_bwd_rs"), ("BPX_FUSED_BITS", "bpx_debug_set_bwd_fused"),
                       ("BPX_CT_BWD", "bpx_debug_set_convt_bwd"), ("BPX_LABEL_TILED", "bpx_debug_set_label_tiled"),
-                      ("BPX_OVERLAP_PER_VOXEL", "bpx_debug_set_overlap_per_voxel")):
+                      ("BPX_OVERLAP_PER_VOXEL", "bpx_debug_set_overlap_per_voxel"),
+                      ("BPX_REGIONPROPS_LOCAL", "bpx_debug_set_regionprops_local")):
         if os.environ.get(env) is not None:
             getattr(lib, hook)(int(os.environ[env]))
     return lib

@@ -17,7 +17,11 @@ percentiles / histogram on the host.
 * ``watershed`` floods an image from the seeds of ``label`` inside a mask (``csrc/watershed.hip``): the marker-controlled watershed those two
   lead up to, with exactly stated semantics of its own (ties go to the raster-first edge) - product-defined, checked against a host twin;
 * ``label_overlap`` / ``matching`` judge the instances: the sparse contingency table of two label volumes (``csrc/overlap.hip``) and the
-  reference's IoU matcher (tp / fp / fn, F1, panoptic quality) on top of it, with only the table's rows leaving the device.
+  reference's IoU matcher (tp / fp / fn, F1, panoptic quality) on top of it, with only the table's rows leaving the device;
+* ``region_props`` / ``centroids`` / ``select_objects`` measure them: area, half-open bounding box, exact coordinate sums and centroid of every
+  label (``csrc/regionprops.hip``; scikit-image's ``regionprops``, SciPy's ``find_objects`` / ``center_of_mass``, the integers bit for bit), and
+  the filter that keeps the labels a torch expression over those tensors selects - the detection workflow's centroids and the instance
+  workflow's property filter without a device-to-host copy of the label volume.
 
 Any contiguous float32 tensor is taken as it is, 16-byte aligned or not (``stack[1]`` of a batch with an odd element count per item is not):
 the scans then read four 4-byte words where they would read one 16-byte word, and return the same bits.
@@ -33,7 +37,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -568,3 +572,79 @@ def matching(y_true: torch.Tensor, y_pred: torch.Tensor, thresh=0.5, criterion: 
     if np.isscalar(thresh):
         return _match_stats(p, c, thresh)
     return [_match_stats(p, c, t) for t in thresh]
+
+
+# ---- region properties of a label volume and the property filter on top of them (csrc/regionprops.hip) -------------------------------------------
+# What every consumer of label() / watershed() does next: the detection workflow takes the centroids of its labelled blobs, the instance workflow
+# measures every instance and drops those that fail a property test, and a crop of an instance needs its box (skimage.measure.regionprops,
+# scipy.ndimage.find_objects / center_of_mass on the host there).  Offered: area, bbox, the exact coordinate sums and the centroid.  NOT offered:
+# intensity properties (a float sum by atomics depends on the order and would break "the same bits every run"; min / max need a segmented scan
+# that the closed-form runs avoid); second moments, inertia axes, eccentricity; perimeter, surface, sphericity (the reference meshes the object);
+# coords, image, convex_*; volumes of 2^31 voxels or more; multi-GPU slabs.
+
+class RegionProps(NamedTuple):
+    """``region_props``' result, every field a device tensor with one row per label ``0..N``; row 0 is the background's and holds zeros (NaN in
+    ``centroid``), as does the row of a label that no voxel carries."""
+    area: torch.Tensor        # int32 (N + 1,)
+    bbox: torch.Tensor        # int32 (N + 1, 2 * ndim): (z0, y0, x0, z1, y1, x1) half-open, (y0, x0, y1, x1) in 2-D
+    coord_sum: torch.Tensor   # int64 (N + 1, ndim): the sums of the voxels' coordinates, exact
+    centroid: torch.Tensor    # float64 (N + 1, ndim): coord_sum / area, NaN where area == 0
+
+
+def region_props(labels: torch.Tensor, num=None) -> RegionProps:
+    """Area, bounding box and centroid of every label ``1..N`` of a 2-D ``(Y, X)`` or 3-D ``(Z, Y, X)`` ``int32`` label tensor, as a
+    ``RegionProps`` named tuple of DEVICE tensors: ``area`` equals ``np.bincount`` (``component_sizes``) from row 1 on, ``bbox`` is scikit-image's
+    ``regionprops`` ``bbox`` (the slices of ``scipy.ndimage.find_objects``, half-open), ``coord_sum`` the exact integer sums of the coordinates
+    and ``centroid = coord_sum.double() / area.double()`` (scikit-image's ``centroid``, ``scipy.ndimage.center_of_mass`` of the label), NaN where
+    ``area == 0``.  The three integer results are bit for bit the same on every run.  Voxels with a label ``<= 0`` or ``> N`` contribute nothing.
+
+    ``num``: ``N`` as a Python int (no wait for the device; inside a graph an upper bound serves, the rows past the labels present are zeros), or
+    the 0-d tensor of ``label(..., return_num=True)``, which is read back here; ``None`` reads ``labels.max()`` back, as ``remove_small_objects``
+    does.  Views are taken via ``.contiguous()``.  Three launches fixed by the shape and ``N``, nothing else read back: capturable.
+
+    Refused before anything is launched: a negative ``num`` and a rank other than 2 / 3 (``ValueError``); a CPU tensor (``RuntimeError``); a dtype
+    other than ``int32``, an empty volume and 2^31 voxels or more (``NotImplementedError``).  Not offered: intensity properties, second moments
+    (inertia axes, eccentricity), perimeter / surface / sphericity, ``coords`` / ``image`` / ``convex_*``, multi-GPU slabs (see the comment above)."""
+    n_max = None if num is None else int(num)
+    if n_max is not None and n_max < 0:
+        raise ValueError(f"num must not be negative (got {n_max})")
+    Z, Y, X = _label_volume(labels, "region_props")
+    lab = _labels(labels, "region_props").contiguous()
+    if n_max is None:
+        n_max = max(int(lab.max()), 0)
+    area = torch.empty(n_max + 1, dtype=torch.int32, device=lab.device)
+    sums = torch.empty((n_max + 1, 3), dtype=torch.int64, device=lab.device)
+    bbox = torch.empty((n_max + 1, 6), dtype=torch.int32, device=lab.device)
+    L.check(lib.bpx_region_props(lab.data_ptr(), Z, Y, X, n_max, area.data_ptr(), sums.data_ptr(), bbox.data_ptr(), L.stream_ptr()))
+    if labels.dim() == 2:                                   # Z = 1: the z columns are all zeros (and ones)
+        sums, bbox = sums[:, 1:], bbox[:, [1, 2, 4, 5]]
+    return RegionProps(area, bbox, sums, sums.double() / area.double()[:, None])
+
+
+def centroids(labels: torch.Tensor, num=None) -> torch.Tensor:
+    """The centroids of the labels ``1..N`` as a ``float64`` device tensor of shape ``(N, ndim)`` - ``region_props(labels, num).centroid[1:]``,
+    what the detection workflow takes from its labelled blobs; NaN for a label that no voxel carries."""
+    return region_props(labels, num).centroid[1:]
+
+
+def select_objects(labels: torch.Tensor, keep: torch.Tensor, relabel: bool = False, return_num: bool = False):
+    """The general form of ``remove_small_objects``: a NEW ``int32`` label tensor in which every label ``l`` with ``keep[l]`` false is 0.  ``keep``
+    is a ``bool`` or ``uint8`` device tensor of length ``N + 1`` (entry 0, the background's, is ignored), typically a torch expression over the
+    tensors of ``region_props``: ``p.area >= 64``; ``(p.bbox[:, :3] > 0).all(1) & (p.bbox[:, 3:] < shape).all(1)`` for "does not touch the
+    border"; a ratio of box extents.  The survivors keep their ids; ``relabel=True`` renumbers them ``1..N'`` in the same order.  Labels above
+    ``N = len(keep) - 1`` become 0, as ``remove_small_objects`` treats labels above ``num``; a kept id that no voxel carries counts as a survivor.
+    ``return_num`` adds ``N'``, the number of survivors, as a 0-d ``int32`` device tensor.  Two launches, nothing read back: capturable."""
+    if keep.dtype not in (torch.bool, torch.uint8):
+        raise NotImplementedError(f"biapy_amd.prepost.select_objects: keep must be a bool or uint8 tensor (got {keep.dtype})")
+    if keep.dim() != 1 or keep.numel() < 1:
+        raise ValueError(f"biapy_amd.prepost.select_objects: keep must have shape (N + 1,) (got {tuple(keep.shape)})")
+    if not keep.is_cuda:
+        raise RuntimeError("biapy_amd.prepost.select_objects: keep must be on the device (it is on %s); there is no CPU path" % keep.device)
+    lab = _labels(labels, "select_objects")
+    n_max = keep.numel() - 1
+    sizes = (keep != 0).to(torch.int32)                     # bpx_label_filter with min_size 1: "size" 1 survives, 0 does not
+    sizes[:1].zero_()                                       # a fill, not a copy from the host: capturable
+    out = lab.clone(memory_format=torch.contiguous_format)
+    left = torch.empty((), dtype=torch.int32, device=lab.device)
+    L.check(lib.bpx_label_filter(out.data_ptr(), out.numel(), n_max, sizes.data_ptr(), 1, 1 if relabel else 0, left.data_ptr(), L.stream_ptr()))
+    return (out, left) if return_num else out

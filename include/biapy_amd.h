@@ -877,6 +877,21 @@ int bpx_label_overlap(const int32_t* a_d, const int32_t* b_d, int64_t n, int64_t
                       void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
 int bpx_debug_set_overlap_per_voxel(int on); /* timing hook of bpx_label_overlap's count pass: 0 (default) = spans, run lengths and the carried run; 1 = one table insert per voxel; the same table (environment: BPX_OVERLAP_PER_VOXEL) */
 
+/* ---- region properties of a label volume (biapy_amd/prepost.py: region_props, centroids, select_objects; csrc/regionprops.hip, csrc/regionprops_core.h) ----
+ * labels (Z,Y,X) int32, contiguous, 4-byte aligned; 2-D is Z = 1; Z * Y * X < 2^31; 0 <= n_max < 2^31 - 1.  For every label l in 1..n_max:
+ *   area_d[l]    = the number of voxels that carry l (int32; bpx_label_sizes' count),
+ *   sums_d[l][3] = the sums of those voxels' z, y and x (int64, exact: below 2^62),
+ *   bbox_d[l][6] = (z0, y0, x0, z1, y1, x1), half-open: scikit-image's bbox, the slices of scipy.ndimage.find_objects.
+ * Row 0 (background) is all zeros, and so is the row of a label that no voxel carries.  Voxels with a label <= 0 or > n_max contribute nothing
+ * (the convention of bpx_label_sizes and bpx_watershed).
+ * A wave run-length-compresses a span of 8192 voxels as bpx_label_overlap does, with every row start a run head as well, so that a run
+ * x0 .. x0 + L - 1 of row (z, y) adds in closed form: area L, sums (L z, L y, L x0 + L (L - 1) / 2), box min (z, y, x0), max (z, y, x0 + L - 1).
+ * Three launches (init, accumulate, finish) fixed by (Z, Y, X, n_max); the outputs are the accumulators, no workspace; integer atomics only
+ * (uint32 / uint64 add, int32 min / max): the same bits every run; nothing read back; capturable.
+ * Argument checks run on the host before anything is launched and set bpx_last_error. */
+int bpx_region_props(const int32_t* labels_d, int Z, int Y, int X, int n_max, int32_t* area_d, int64_t* sums_d, int32_t* bbox_d, bpx_stream_t stream);
+int bpx_debug_set_regionprops_local(int on); /* test / A-B hook of bpx_region_props' accumulate pass: 1 (default) = the runs of a block meet in a 256-slot table in LDS that is merged into the outputs once per block; 0 = every run straight to the outputs, faster on a volume without labels and far slower on any other; negative = back to the default; same bits (environment: BPX_REGIONPROPS_LOCAL) */
+
 #ifdef __cplusplus
 }
 #endif
