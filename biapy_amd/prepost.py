@@ -21,7 +21,12 @@ percentiles / histogram on the host.
 * ``region_props`` / ``centroids`` / ``select_objects`` measure them: area, half-open bounding box, exact coordinate sums and centroid of every
   label (``csrc/regionprops.hip``; scikit-image's ``regionprops``, SciPy's ``find_objects`` / ``center_of_mass``, the integers bit for bit), and
   the filter that keeps the labels a torch expression over those tensors selects - the detection workflow's centroids and the instance
-  workflow's property filter without a device-to-host copy of the label volume.
+  workflow's property filter without a device-to-host copy of the label volume;
+* ``binary_erosion`` / ``binary_dilation`` / ``binary_opening`` / ``binary_closing``, ``erosion`` / ``dilation``, ``find_boundaries``,
+  ``binary_fill_holes`` and ``clear_border`` are the steps between those calls (``csrc/morph.hip``: one 3 x 3 x 3 stencil pass over ``uint8``,
+  ``int32`` or ``float32``; the structuring element is ``generate_binary_structure(ndim, connectivity)``): ``scipy.ndimage``'s ``binary_*``,
+  ``grey_erosion`` / ``grey_dilation`` and ``binary_fill_holes`` bit for bit, Euclidean balls (``radius=``) through the exact distance
+  transform, hole filling and border clearing through ``label`` / ``select_objects`` and the labels on the volume's faces.
 
 Any contiguous float32 tensor is taken as it is, 16-byte aligned or not (``stack[1]`` of a batch with an odd element count per item is not):
 the scans then read four 4-byte words where they would read one 16-byte word, and return the same bits.
@@ -648,3 +653,216 @@ def select_objects(labels: torch.Tensor, keep: torch.Tensor, relabel: bool = Fal
     left = torch.empty((), dtype=torch.int32, device=lab.device)
     L.check(lib.bpx_label_filter(out.data_ptr(), out.numel(), n_max, sizes.data_ptr(), 1, 1 if relabel else 0, left.data_ptr(), L.stream_ptr()))
     return (out, left) if return_num else out
+
+
+# ---- morphology: erosion, dilation, boundaries, hole filling and border clearing (csrc/morph.hip) -------------------------------------------------
+# The steps BETWEEN the calls above in the instance and detection workflows: seed maps are eroded before label(), holes in the foreground are
+# filled, instances that touch the border are dropped, instance targets get their contour channel from find_boundaries, masks are opened or
+# closed to remove speckle (scipy.ndimage.binary_* / grey_*, skimage.segmentation.find_boundaries / clear_border on the host there).
+# ``connectivity`` is always an int with label()'s meaning: the element is scipy.ndimage.generate_binary_structure(ndim, connectivity).
+# NOT offered: arbitrary ``structure`` / ``footprint`` arrays; ``mask=`` and ``origin=``; ``iterations < 1`` (SciPy's "until stable" needs a
+# read-back); grey ``mode="constant"`` (out-of-volume neighbours are ignored: SciPy's default "reflect" for these elements); ball footprints on
+# grey input; find_boundaries' "outer" / "subpixel"; clear_border's ``buffer_size`` and ``mask``; the median filter; volumes of 2^31 voxels or
+# more; multi-GPU slabs; the watershed_by_channels threshold logic itself, which is now a short sequence of these calls.
+
+_MORPH_ERODE, _MORPH_DILATE, _MORPH_BOUNDARY = 0, 1, 2            # include/biapy_amd.h: bpx_morph's op
+_MORPH_BINARY, _MORPH_ABSORB, _MORPH_INNER = 1, 2, 4               # and its flags
+_MORPH_DT = {torch.uint8: L.U8, torch.int32: L.I32, torch.float32: L.F32}
+
+
+def _morph_input(x: torch.Tensor, what: str, dtypes, names: str) -> Tuple[int, int, int]:
+    if x.dtype not in dtypes:
+        raise NotImplementedError(f"biapy_amd.prepost.{what} works on {names} tensors (got {x.dtype})")
+    Z, Y, X = _label_volume(x, what)
+    if x.numel() < 1:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: a {tuple(x.shape)} volume has an empty axis")
+    return Z, Y, X
+
+
+def _on_device(x: torch.Tensor) -> torch.Tensor:
+    """The last refusal, after every argument has been checked."""
+    if not x.is_cuda:
+        raise RuntimeError("biapy_amd.prepost runs on the MI355X only (tensor is on %s); there is no CPU path" % x.device)
+    return x
+
+
+def _connectivity(x: torch.Tensor, connectivity) -> int:
+    c = int(connectivity)
+    if not 1 <= c <= x.dim():
+        raise ValueError(f"connectivity must be in 1..{x.dim()} for a {x.dim()}-D tensor (got {connectivity})")
+    return c
+
+
+def _morph(src: torch.Tensor, dst: torch.Tensor, shape, ndim: int, c: int, op: int, flags: int = 0, background: int = 0) -> torch.Tensor:
+    """One launch of ``bpx_morph`` from the contiguous ``src`` into ``dst``."""
+    Z, Y, X = shape
+    L.check(lib.bpx_morph(src.data_ptr(), _MORPH_DT[src.dtype], Z, Y, X, ndim, c, op, flags, int(background), dst.data_ptr(), L.stream_ptr()))
+    return dst
+
+
+def _ball(mask: torch.Tensor, radius, dilate: bool) -> torch.Tensor:
+    """Erosion / dilation by the Euclidean ball ``dz^2 + dy^2 + dx^2 <= r^2`` from the exact squared distance transform: a voxel survives the
+    erosion when its nearest zero is farther than ``r``, and the dilation reaches it when its nearest one is no farther.  No special case for
+    a mask without any zero (erosion) or any one (dilation): the transform then returns its sentinel INT32_MAX, which is "farther than any r",
+    so the erosion keeps every voxel and the dilation sets none - the right answers."""
+    r2 = min(int(math.floor(float(radius) ** 2)), 2 ** 31 - 2)                 # below the sentinel; no distance in a volume the transform accepts reaches it
+    if dilate:
+        return (distance_transform_edt(mask == 0, squared=True) <= r2).to(torch.uint8)
+    return (distance_transform_edt(mask, squared=True) > r2).to(torch.uint8)
+
+
+def _binary(mask: torch.Tensor, what: str, dilate: bool, connectivity, iterations, border_value, radius) -> torch.Tensor:
+    shape = _morph_input(mask, what, (torch.uint8, torch.bool), "uint8 or bool")
+    if border_value not in (0, 1):
+        raise ValueError(f"border_value must be 0 or 1 (got {border_value!r})")
+    if radius is not None:
+        if int(connectivity) != 1 or int(iterations) != 1:
+            raise ValueError(f"biapy_amd.prepost.{what}: radius is given INSTEAD of connectivity / iterations (got connectivity={connectivity}, "
+                             f"iterations={iterations})")
+        if int(border_value) != (0 if dilate else 1):
+            raise NotImplementedError(f"biapy_amd.prepost.{what}: radius= is offered with border_value={0 if dilate else 1} only - the other value "
+                                      "needs the black border the distance transform does not offer")
+        if not (math.isfinite(float(radius)) and float(radius) >= 0.0):
+            raise ValueError(f"radius must be a finite number >= 0 (got {radius!r})")
+        return _ball(_on_device(mask), radius, dilate)
+    c = _connectivity(mask, connectivity)
+    k = int(iterations)
+    if k < 1:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: iterations must be >= 1 (got {iterations}); SciPy's 'until stable' needs a read-back "
+                                  "and is not offered")
+    src = _on_device(mask).contiguous()
+    if src.dtype == torch.bool:
+        src = src.view(torch.uint8)
+    absorbing = 1 if dilate else 0
+    flags = _MORPH_BINARY | (_MORPH_ABSORB if int(border_value) == absorbing else 0)
+    out = torch.empty(mask.shape, dtype=torch.uint8, device=mask.device)
+    other = torch.empty_like(out) if k > 1 else None
+    for i in range(k):                                             # k launches; the last one writes `out`
+        dst = out if (k - 1 - i) % 2 == 0 else other
+        src = _morph(src, dst, shape, mask.dim(), c, _MORPH_DILATE if dilate else _MORPH_ERODE, flags)
+    return out
+
+
+def binary_erosion(mask: torch.Tensor, connectivity: int = 1, iterations: int = 1, border_value: int = 0, radius=None) -> torch.Tensor:
+    """``scipy.ndimage.binary_erosion(mask, generate_binary_structure(mask.ndim, connectivity), iterations, border_value=border_value)`` of a
+    2-D / 3-D ``uint8`` or ``bool`` device mask (every nonzero value is foreground) as a ``uint8`` 0 / 1 mask, bit for bit.  ``iterations = k
+    >= 1`` is ``k`` launches that ping-pong between the result and one scratch volume.
+
+    ``radius=r``, given INSTEAD of ``connectivity`` / ``iterations``, erodes by the Euclidean ball ``dz^2 + dy^2 + dx^2 <= r^2`` (scikit-image's
+    ``ball(r)`` / ``disk(r)``) by thresholding the exact squared distance transform: ``distance_transform_edt(mask, squared=True) > r^2``.  The
+    transform has no black border, so this is offered for ``border_value=1`` only (dilation: ``border_value=0``).
+
+    Nothing is read back, two runs give the same bits, the call can be captured in a graph.  Refused before anything is launched: a CPU tensor
+    (``RuntimeError``); other dtypes, an empty axis, 2^31 voxels or more, ``iterations < 1`` (SciPy's "until stable") and ``radius`` with the
+    other border value (``NotImplementedError``); other ranks, a connectivity outside ``1..ndim``, a ``border_value`` other than 0 / 1 and
+    ``radius`` together with ``connectivity`` / ``iterations`` (``ValueError``).  ``structure``, ``mask`` and ``origin`` are not offered."""
+    return _binary(mask, "binary_erosion", False, connectivity, iterations, border_value, radius)
+
+
+def binary_dilation(mask: torch.Tensor, connectivity: int = 1, iterations: int = 1, border_value: int = 0, radius=None) -> torch.Tensor:
+    """``scipy.ndimage.binary_dilation`` with the parameters, the result and the refusals of ``binary_erosion``.  ``radius=r`` is
+    ``distance_transform_edt(mask == 0, squared=True) <= r^2`` and is offered for ``border_value=0`` only."""
+    return _binary(mask, "binary_dilation", True, connectivity, iterations, border_value, radius)
+
+
+def binary_opening(mask: torch.Tensor, connectivity: int = 1, iterations: int = 1, border_value: int = 0) -> torch.Tensor:
+    """``scipy.ndimage.binary_opening``: the erosion, then the dilation of its result, both with the same ``iterations`` and ``border_value`` -
+    the composition SciPy makes, bit for bit.  Removes foreground speckle smaller than the element."""
+    return binary_dilation(binary_erosion(mask, connectivity, iterations, border_value), connectivity, iterations, border_value)
+
+
+def binary_closing(mask: torch.Tensor, connectivity: int = 1, iterations: int = 1, border_value: int = 0) -> torch.Tensor:
+    """``scipy.ndimage.binary_closing``: the dilation, then the erosion of its result, both with the same ``iterations`` and ``border_value``.
+    Closes gaps smaller than the element."""
+    return binary_erosion(binary_dilation(mask, connectivity, iterations, border_value), connectivity, iterations, border_value)
+
+
+def _grey(x: torch.Tensor, what: str, connectivity, op: int) -> torch.Tensor:
+    shape = _morph_input(x, what, (torch.uint8, torch.int32, torch.float32), "uint8, int32 or float32")
+    c = _connectivity(x, connectivity)
+    return _morph(_on_device(x).contiguous(), torch.empty(x.shape, dtype=x.dtype, device=x.device), shape, x.dim(), c, op)
+
+
+def erosion(x: torch.Tensor, connectivity: int = 1) -> torch.Tensor:
+    """``scipy.ndimage.grey_erosion(x, footprint=generate_binary_structure(x.ndim, connectivity))`` (``skimage.morphology.erosion``) of a 2-D /
+    3-D ``uint8``, ``int32`` or ``float32`` device tensor: the minimum over the element, in the input's type; out-of-volume neighbours are
+    ignored (SciPy's default ``mode="reflect"`` for these elements).  ``float32``: equal as values - which of ``-0.0`` / ``+0.0`` is chosen is
+    unspecified, and so is NaN.  One launch, capturable; the refusals of ``binary_erosion``."""
+    return _grey(x, "erosion", connectivity, _MORPH_ERODE)
+
+
+def dilation(x: torch.Tensor, connectivity: int = 1) -> torch.Tensor:
+    """``scipy.ndimage.grey_dilation(x, footprint=generate_binary_structure(x.ndim, connectivity))``: the maximum over the element, otherwise as
+    ``erosion``.  On an ``int32`` label volume this is "THE LARGEST NEIGHBOURING ID WINS": a background voxel next to labels 3 and 7 becomes 7,
+    and so does a voxel of label 3 next to label 7 - labels grow into the background AND into smaller ids."""
+    return _grey(x, "dilation", connectivity, _MORPH_DILATE)
+
+
+def find_boundaries(labels: torch.Tensor, connectivity: int = 1, mode: str = "thick", background: int = 0) -> torch.Tensor:
+    """The boundary map of a 2-D / 3-D label tensor (``int32``; ``uint8`` / ``bool`` and ``float32`` are taken too) as ``uint8`` 0 / 1, in one
+    pass: ``mode="thick"`` is ``dilation(labels, connectivity) != erosion(labels, connectivity)`` - a voxel whose element holds two different
+    values; ``mode="inner"`` is that AND ``labels != background``, the boundary voxels that belong to an object.  The call shape of
+    ``skimage.segmentation.find_boundaries``; the definition is this product's, stated here and checked against its own statement.  ``"outer"``
+    and ``"subpixel"`` raise ``NotImplementedError``.  Negative labels are ordinary values.  One launch, capturable."""
+    if mode not in ("thick", "inner", "outer", "subpixel"):
+        raise ValueError(f"mode must be 'thick' or 'inner' (got {mode!r})")
+    if mode in ("outer", "subpixel"):
+        raise NotImplementedError(f"biapy_amd.prepost.find_boundaries offers the modes 'thick' and 'inner' (got {mode!r})")
+    shape = _morph_input(labels, "find_boundaries", (torch.int32, torch.uint8, torch.bool, torch.float32), "int32, uint8, bool or float32")
+    c = _connectivity(labels, connectivity)
+    bg = int(background)
+    if not -2 ** 31 <= bg < 2 ** 31:
+        raise ValueError(f"background must fit int32 (got {background})")
+    src = _on_device(labels).contiguous()
+    if src.dtype == torch.bool:
+        src = src.view(torch.uint8)
+    out = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+    return _morph(src, out, shape, labels.dim(), c, _MORPH_BOUNDARY, _MORPH_INNER if mode == "inner" else 0, bg)
+
+
+def _num_labels(lab: torch.Tensor, num) -> int:
+    n_max = max(int(lab.max()), 0) if num is None else int(num)
+    if n_max < 0:
+        raise ValueError(f"num must not be negative (got {n_max})")
+    return n_max
+
+
+def _border_labels(lab: torch.Tensor, n_max: int) -> torch.Tensor:
+    """A ``bool`` tensor of length ``n_max + 1``: entry ``l`` is true when a voxel on one of the volume's six faces (four edges in 2-D) carries
+    label ``l``.  Torch indexing over the faces only; labels outside ``1..n_max`` land on entry 0, which nobody reads.  Capturable."""
+    flags = torch.zeros(n_max + 1, dtype=torch.uint8, device=lab.device)
+    for axis in range(lab.dim()):
+        for side in (0, lab.shape[axis] - 1):
+            face = lab.select(axis, side).reshape(-1).long()
+            flags.index_fill_(0, torch.where((face > 0) & (face <= n_max), face, torch.zeros_like(face)), 1)
+    return flags != 0
+
+
+def clear_border(labels: torch.Tensor, num=None, relabel: bool = False, return_num: bool = False):
+    """``skimage.segmentation.clear_border(labels)`` on a 2-D / 3-D ``int32`` label tensor: a NEW tensor in which every label that has a voxel on
+    the volume's border is 0.  The survivors keep their ids; ``relabel=True`` renumbers them ``1..N'`` in the same order, ``return_num`` adds
+    ``N'`` as a 0-d ``int32`` device tensor - ``select_objects`` on the flags of the faces.  ``num`` as in ``region_props``: the largest label as
+    a Python int (inside a graph an upper bound serves), the 0-d tensor of ``label``, or ``None``, which reads ``labels.max()`` back; labels above
+    it become 0.  ``buffer_size`` and ``mask`` are not offered."""
+    n_max = None if num is None else _num_labels(labels, num)
+    _label_volume(labels, "clear_border")
+    lab = _labels(labels, "clear_border")
+    if n_max is None:
+        n_max = _num_labels(lab, None)
+    return select_objects(lab, ~_border_labels(lab, n_max), relabel=relabel, return_num=return_num)
+
+
+def binary_fill_holes(mask: torch.Tensor, num=None) -> torch.Tensor:
+    """``scipy.ndimage.binary_fill_holes(mask)`` of a 2-D / 3-D ``uint8`` or ``bool`` device mask as a ``uint8`` 0 / 1 mask, bit for bit: the
+    background is labelled at connectivity 1 (``label(mask == 0, 1)``), its components that touch no face of the volume are the holes
+    (``select_objects``), and they are OR-ed into the mask.  A hole open to the border through one voxel is no hole; one open only through a
+    diagonal is.  ``num``: the number of background components - ``None`` reads that one scalar back; an int is an upper bound of it that
+    makes the call capturable (components numbered above it would stay unfilled); a 0-d tensor is read back."""
+    _morph_input(mask, "binary_fill_holes", (torch.uint8, torch.bool), "uint8 or bool")
+    if num is not None and int(num) < 0:
+        raise ValueError(f"num must not be negative (got {int(num)})")
+    fg = _on_device(mask) != 0
+    lab, n = label(~fg, connectivity=1, return_num=True)
+    n_max = int(n) if num is None else int(num)
+    holes = select_objects(lab, ~_border_labels(lab, n_max))
+    return ((holes > 0) | fg).to(torch.uint8)

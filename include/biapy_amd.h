@@ -892,6 +892,23 @@ int bpx_debug_set_overlap_per_voxel(int on); /* timing hook of bpx_label_overlap
 int bpx_region_props(const int32_t* labels_d, int Z, int Y, int X, int n_max, int32_t* area_d, int64_t* sums_d, int32_t* bbox_d, bpx_stream_t stream);
 int bpx_debug_set_regionprops_local(int on); /* test / A-B hook of bpx_region_props' accumulate pass: 1 (default) = the runs of a block meet in a 256-slot table in LDS that is merged into the outputs once per block; 0 = every run straight to the outputs, faster on a volume without labels and far slower on any other; negative = back to the default; same bits (environment: BPX_REGIONPROPS_LOCAL) */
 
+/* ---- morphology: erosion, dilation and the boundary map (biapy_amd/prepost.py: binary_erosion, binary_dilation, binary_opening, binary_closing,
+ * erosion, dilation, find_boundaries; csrc/morph.hip, csrc/morph_core.h) ----
+ * in (Z,Y,X) contiguous, dtype BPX_U8, BPX_I32 or BPX_F32 (the 4-byte types 4-byte aligned; uint8 at any address); ndim 3, or 2 with Z = 1;
+ * Z * Y * X < 2^31.  The structuring element is scipy.ndimage.generate_binary_structure(ndim, connectivity), 1 <= connectivity <= ndim: the row
+ * (dz, dy) of the 3 x 3 (x 3) neighbourhood, k = |dz| + |dy|, belongs to it when k <= connectivity (ndim 2: only dz = 0) and contributes
+ * x - 1, x, x + 1 when k + 1 <= connectivity, x alone otherwise.
+ *   op 0 (erode): out = the minimum over the element, 1 (dilate): the maximum - out has the input's type;
+ *   op 2 (boundary): out is uint8, 1 where the minimum and the maximum differ; with flag 4 (inner) only where in != background as well.
+ * Out-of-volume neighbours are ignored (scipy's grey filters in mode="reflect" for these elements; binary erosion with border_value=1, binary
+ * dilation with border_value=0); with flag 2 (absorbing border; binary only) they count as 0 for erosion and 1 for dilation (scipy's
+ * border_value=0 erosion, border_value=1 dilation).  Flag 1 (binary; uint8, erode / dilate only): every nonzero byte is 1, out holds 0 / 1.
+ * float32: equal as values; which of -0.0 / +0.0 is chosen and NaN are unspecified.
+ * One launch, 16 bytes of a row per lane; no atomics, no workspace; the same bits every run; nothing read back; capturable.  out_d must not
+ * be in_d.  Argument checks run on the host before anything is launched and set bpx_last_error. */
+int bpx_morph(const void* in_d, int dtype, int Z, int Y, int X, int ndim, int connectivity, int op, int flags, int background, void* out_d,
+              bpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
