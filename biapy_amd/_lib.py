@@ -82,6 +82,8 @@ _SIGS = {
     "bpx_region_props": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "bpx_debug_set_regionprops_local": ([_i], _i),
     "bpx_morph": ([_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
+    "bpx_peaks_workspace": ([_i, _i, _i], _i64),
+    "bpx_peak_local_max": ([_vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp], _i),
     "bpx_scan_blocks": ([_i64], _i),
     "bpx_select_workspace": ([], _i64),
     "bpx_select_kth_f32": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),

@@ -26,7 +26,11 @@ percentiles / histogram on the host.
   ``binary_fill_holes`` and ``clear_border`` are the steps between those calls (``csrc/morph.hip``: one 3 x 3 x 3 stencil pass over ``uint8``,
   ``int32`` or ``float32``; the structuring element is ``generate_binary_structure(ndim, connectivity)``): ``scipy.ndimage``'s ``binary_*``,
   ``grey_erosion`` / ``grey_dilation`` and ``binary_fill_holes`` bit for bit, Euclidean balls (``radius=``) through the exact distance
-  transform, hole filling and border clearing through ``label`` / ``select_objects`` and the labels on the volume's faces.
+  transform, hole filling and border clearing through ``label`` / ``select_objects`` and the labels on the volume's faces;
+* ``peak_local_max`` / ``peak_mask`` find the local maxima of a probability or distance map (``csrc/peaks.hip``): the detection workflow's
+  points as a sorted, compact list that is never read back, and the markers of the "distance map -> peaks -> ``label`` -> ``watershed``"
+  recipe as a 0 / 1 volume.  The call shape of ``skimage.feature.peak_local_max`` with a box of per-axis radii and semantics of its own (among
+  equal values the raster-first voxel wins, so no two peaks lie in each other's box) - product-defined, checked against a host twin.
 
 Any contiguous float32 tensor is taken as it is, 16-byte aligned or not (``stack[1]`` of a batch with an odd element count per item is not):
 the scans then read four 4-byte words where they would read one 16-byte word, and return the same bits.
@@ -866,3 +870,158 @@ def binary_fill_holes(mask: torch.Tensor, num=None) -> torch.Tensor:
     n_max = int(n) if num is None else int(num)
     holes = select_objects(lab, ~_border_labels(lab, n_max))
     return ((holes > 0) | fg).to(torch.uint8)
+
+
+# ---- local maxima: the detection workflow's points and the watershed's markers (csrc/peaks.hip) ----------------------------------------------------
+# The reference's default point-creation function is skimage.feature.peak_local_max(prob, min_distance, threshold_abs, exclude_border) on the
+# probability map, and the same call on the distance map gives the markers watershed() needs; both ran on the host.  A local-maximum filter
+# with a radius and a deterministic tie rule (the raster-first voxel of equal values wins), a 0 / 1 volume for label() and a compact, sorted
+# point list that is never read back.  NOT offered: ``threshold_rel``, ``labels=``, ``footprint=`` and ``p_norm`` (the distance is the box's:
+# Chebyshev, per axis); ``blob_log``; the reference's remove_close_points and its point-matching detection metric (host work on kilobytes);
+# volumes of 2^31 voxels or more; multi-GPU slabs.
+
+_PEAKS_MAX_RADIUS = 64                                                # csrc/peaks_core.h: PEAKS_MAX_RADIUS
+
+
+def _per_axis(value, ndim: int, name: str) -> Tuple[int, ...]:
+    if isinstance(value, (tuple, list)):
+        if len(value) != ndim:
+            raise ValueError(f"{name} must be an int or one int per axis of the {ndim}-D image (got {len(value)} values)")
+        return tuple(int(v) for v in value)
+    return (int(value),) * ndim
+
+
+def _peaks_call(image: torch.Tensor, what: str, min_distance, threshold_abs, exclude_border, sizes=()):
+    """The checks both calls share, in the house order, then the volume, the radii, the margins and the threshold as ``bpx_peak_local_max`` takes
+    them.  ``sizes``: ``(name, value)`` pairs that must be ``None`` or at least 1."""
+    if image.dim() not in (2, 3):
+        raise ValueError(f"biapy_amd.prepost.{what} takes a 2-D (Y, X) or 3-D (Z, Y, X) tensor (got {image.dim()} dimensions)")
+    nd = image.dim()
+    radii = _per_axis(min_distance, nd, "min_distance")
+    if any(r < 0 or r > _PEAKS_MAX_RADIUS for r in radii):
+        raise ValueError(f"min_distance must be in 0..{_PEAKS_MAX_RADIUS} on every axis (got {min_distance!r})")
+    if exclude_border is True:
+        border = radii
+    elif exclude_border is False:
+        border = (0,) * nd
+    else:
+        border = _per_axis(exclude_border, nd, "exclude_border")
+    if any(b < 0 for b in border):
+        raise ValueError(f"exclude_border must not be negative (got {exclude_border!r})")
+    for name, v in sizes:
+        if v is not None and int(v) < 1:
+            raise ValueError(f"{name} must be at least 1 (got {v})")
+    if threshold_abs is not None and math.isnan(float(threshold_abs)):
+        raise ValueError("threshold_abs must not be NaN")
+    if image.dtype not in (torch.float32, torch.int32):
+        raise NotImplementedError(f"biapy_amd.prepost.{what} works on float32 or int32 images (got {image.dtype})")
+    if image.numel() < 1:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: a {tuple(image.shape)} volume has an empty axis")
+    if image.numel() >= 2 ** 31:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: {image.numel()} voxels - volumes of 2^31 voxels or more are not supported (int32 indices)")
+    img = _on_device(image).contiguous()
+    if threshold_abs is None:                                          # skimage: image.min(); one scalar read back - not capturable
+        thr = minmax(img)[0] if img.dtype == torch.float32 else float(int(img.min()))
+        if math.isnan(thr):
+            raise ValueError(f"biapy_amd.prepost.{what}: the image holds NaN, so threshold_abs=None (the image's minimum) is NaN; pass a threshold")
+    else:
+        thr = float(threshold_abs)
+    pad = (0,) * (3 - nd)
+    return img, (1,) * (3 - nd) + tuple(image.shape), pad + radii, pad + border, thr
+
+
+def _peaks_run(img: torch.Tensor, shape, radii, border, thr: float, mask: Optional[torch.Tensor], keys: Optional[torch.Tensor]) -> torch.Tensor:
+    """``bpx_peak_local_max`` into ``mask`` and / or ``keys``; returns the number of peaks (0-d ``int32``, counted past ``keys``' end as well)."""
+    Z, Y, X = shape
+    need = int(lib.bpx_peaks_workspace(Z, Y, X))
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=img.device)
+    count = torch.empty((), dtype=torch.int32, device=img.device)
+    L.check(lib.bpx_peak_local_max(img.data_ptr(), L.F32 if img.dtype == torch.float32 else L.I32, Z, Y, X, radii[0], radii[1], radii[2], thr,
+                                   border[0], border[1], border[2], L.ptr(mask), L.ptr(keys), 0 if keys is None else keys.numel(), count.data_ptr(),
+                                   ws.data_ptr(), need, L.stream_ptr()))
+    return count
+
+
+def peak_mask(image: torch.Tensor, min_distance=1, threshold_abs=None, exclude_border=True) -> torch.Tensor:
+    """The peaks of ``peak_local_max`` (same parameters, same definition) as a ``uint8`` 0 / 1 tensor of ``image``'s shape - what
+    ``skimage.feature.peak_local_max`` returned with ``indices=False``.  ``label(peak_mask(edt, d))`` are the markers of ``watershed``: every
+    peak is alone in its box, so at connectivity 1 and ``min_distance >= 1`` each becomes a marker of its own."""
+    img, shape, radii, border, thr = _peaks_call(image, "peak_mask", min_distance, threshold_abs, exclude_border)
+    mask = torch.empty(image.shape, dtype=torch.uint8, device=img.device)
+    _peaks_run(img, shape, radii, border, thr, mask, None)
+    return mask
+
+
+def peak_local_max(image: torch.Tensor, min_distance=1, threshold_abs=None, exclude_border=True, num_peaks: Optional[int] = None,
+                   max_peaks: Optional[int] = None, return_values: bool = False):
+    """The local maxima of a 2-D ``(Y, X)`` or 3-D ``(Z, Y, X)`` ``float32`` or ``int32`` device tensor: the call shape of
+    ``skimage.feature.peak_local_max(image, min_distance, threshold_abs, exclude_border, num_peaks)``, with semantics of its own, stated exactly
+    and checked against a host twin (``tests/peaks_ref.py``).  With the radii ``r = min_distance`` (an int, or one int per axis - this package's
+    extension for anisotropic volumes; each in ``0..64``):
+
+    * the KEY of voxel ``v`` is ``(k(v) << 32) | (0xFFFFFFFF - linear_index(v))`` as ``uint64``, ``k`` being ``watershed``'s order-preserving
+      ``uint32`` image of the value (``int32``: ``v + 2^31``; ``float32``: the sign-flip map, so ``-0.0 < +0.0``; NaN is unspecified): a larger
+      key is a larger value, and among equal values the raster-first voxel;
+    * a voxel is a PEAK when its key is the maximum of the keys in the box ``[z-rz, z+rz] x [y-ry, y+ry] x [x-rx, x+rx]`` clipped to the volume,
+      its value is ``> threshold_abs`` (compared in ``double``, exact for both dtypes), and it lies at least ``b`` voxels from both faces of
+      every axis, ``b`` the ``exclude_border`` margin of that axis - on an axis of extent ``<= 2 b`` no voxel does.
+
+    What follows from that:
+
+    * no two peaks ever lie in each other's box (each key would have to exceed the other), so scikit-image's ``ensure_spacing`` pass has nothing
+      left to do and is not made;
+    * on an image without two equal values inside any box the peaks are scikit-image's:
+      ``(image == maximum_filter(image, size=2r+1, mode="nearest")) & (image > threshold_abs)`` with the border cleared;
+    * ON TIES THE PEAKS ARE A SUBSET of that mask: a constant plateau the size of a box yields its raster-first voxel only, where
+      scikit-image keeps several spaced points of a long plateau.  A ``1 x 21`` row with a plateau at ``x = 3..14`` and radii ``(0, 2)`` gives
+      the one peak ``(0, 3)``; scikit-image's mask holds 12 voxels there.
+
+    ``exclude_border`` follows scikit-image: ``True`` is ``min_distance``, ``False`` is 0, or an int, or one int per axis.  ``threshold_abs=None``
+    follows it too and means ``image.min()`` (the voxels that carry the minimum are no peaks): THAT CALL FORM READS ONE SCALAR BACK and cannot
+    be captured in a graph; with a given threshold (``-inf`` for none) nothing is read back, two runs give the same bits and the call can be
+    captured.  ``threshold_rel``, ``labels``, ``footprint`` and ``p_norm`` are not offered.
+
+    Returns ``(coords, num)``, or ``(coords, values, num)`` with ``return_values``:
+
+    * ``coords``: ``int32`` of shape ``(max_peaks, ndim)``, SORTED by value descending, then by linear index ascending (one ``torch.sort`` of
+      the key array, descending); the rows from ``num`` onward are ``-1``;
+    * ``values``: ``image``'s dtype, the peaks' values decoded from the keys bit for bit; 0 from ``num`` onward;
+    * ``num``: the number of peaks as a 0-d ``int32`` DEVICE tensor, ``-1`` when there are more than ``max_peaks`` of them (the other results
+      are then unspecified).
+
+    ``max_peaks`` defaults to ``min(n, 2**20)``.  ``num_peaks=k`` keeps the first ``k`` rows: the results have ``min(k, max_peaks)`` rows and
+    ``num`` is ``min(num, k)``.
+
+    One launch that clears the outputs and one pass per axis with a nonzero radius and more than one voxel (one pass when there is none), fixed by the shape and the radii
+    (``csrc/peaks.hip``); at most ``2 r + 4`` loads per voxel and axis, never the box.  The workspace is 16 bytes per voxel (two key volumes).
+
+    Refused before anything is launched: other ranks, a ``min_distance`` / ``exclude_border`` tuple of another length, a radius outside
+    ``0..64``, a negative margin, ``max_peaks`` / ``num_peaks < 1`` and a NaN threshold (``ValueError``); other dtypes, an empty axis and 2^31
+    voxels or more (``NotImplementedError``); last, a CPU tensor (``RuntimeError``)."""
+    img, shape, radii, border, thr = _peaks_call(image, "peak_local_max", min_distance, threshold_abs, exclude_border,
+                                                 (("max_peaks", max_peaks), ("num_peaks", num_peaks)))
+    n = img.numel()
+    mp = min(n, 2 ** 20) if max_peaks is None else min(int(max_peaks), 2 ** 31 - 1)
+    keys = torch.empty(mp, dtype=torch.int64, device=img.device)       # uint64 bits
+    count = _peaks_run(img, shape, radii, border, thr, None, keys)
+    top = torch.iinfo(torch.int64).min                                 # bit 63: signed order of key ^ top = unsigned order of key
+    keys = torch.sort(keys ^ top, descending=True).values ^ top       # the filler 0 is below every key
+    num = torch.where(count > mp, torch.full_like(count, -1), count)
+    if num_peaks is not None:
+        keys = keys[:int(num_peaks)]
+        num = torch.clamp(num, max=int(num_peaks))
+    filler = keys == 0
+    index = 0xFFFFFFFF - (keys & 0xFFFFFFFF)
+    _, Y, X = shape
+    zyx = torch.stack((index // (Y * X), index // X % Y, index % X), dim=1)[:, 3 - image.dim():]
+    coords = zyx.masked_fill(filler[:, None], -1).to(torch.int32)
+    if not return_values:
+        return coords, num
+    k = (keys >> 32) & 0xFFFFFFFF                                      # the value's order-preserving uint32 image, in int64
+    if img.dtype == torch.float32:
+        bits = torch.where(k >= 2 ** 31, k - 2 ** 31, 0xFFFFFFFF - k)  # the sign-flip map back
+        bits = bits - ((bits >> 31) << 32)                             # the same 32 bits as a signed number
+        values = bits.masked_fill(filler, 0).to(torch.int32).view(torch.float32)
+    else:
+        values = (k - 2 ** 31).masked_fill(filler, 0).to(torch.int32)
+    return coords, values, num

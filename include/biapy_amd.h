@@ -909,6 +909,27 @@ int bpx_debug_set_regionprops_local(int on); /* test / A-B hook of bpx_region_pr
 int bpx_morph(const void* in_d, int dtype, int Z, int Y, int X, int ndim, int connectivity, int op, int flags, int background, void* out_d,
               bpx_stream_t stream);
 
+/* ---- local maxima (biapy_amd/prepost.py: peak_mask, peak_local_max; csrc/peaks.hip, csrc/peaks_core.h) ----
+ * img (Z,Y,X) contiguous, dtype BPX_F32 or BPX_I32, 4-byte aligned (16-byte accesses where the address allows, the same bits otherwise);
+ * Z * Y * X < 2^31; a 2-D image is Z = 1, rz = 0.  The key of voxel v is (k(v) << 32) | (0xFFFFFFFF - linear_index(v)) as uint64, k the
+ * order-preserving uint32 image of the value that bpx_watershed uses (int32: v + 2^31; float32: the sign-flip map, -0.0 < +0.0; NaN
+ * unspecified).  Voxel v is a PEAK when its key is the maximum of the keys in the box [z-rz, z+rz] x [y-ry, y+ry] x [x-rx, x+rx] clipped to
+ * the volume (radii 0..64), its value is > threshold (compared in double; -inf: no threshold) and it lies at least bz / by / bx voxels from both
+ * faces of its axis (no voxel on an axis of extent <= 2 b).  Among equal values the raster-first voxel wins, so no two peaks lie in each
+ * other's box.
+ *   mask_d  : uint8 (Z,Y,X), 1 at the peaks and 0 elsewhere; may be null.
+ *   keys_d  : uint64[max_peaks], 8-byte aligned: the peaks' keys in an order that may vary between runs (the set does not), 0 in the unused
+ *             slots (no voxel carries key 0); may be null.  Past max_peaks keys are dropped.
+ *   *num_d  : the number of peaks, counted beyond max_peaks as well (more than max_peaks: the key array holds some max_peaks of them).
+ * One pass per axis with a nonzero radius and more than one voxel (one pass when there is none) after one launch that clears the outputs: launches fixed by (Z, Y, X, radii),
+ * at most 2 r + 4 loads per voxel and axis, never the box.  The workspace holds at most two key volumes:
+ *   bpx_peaks_workspace : bytes of workspace (16 per voxel); NEGATIVE when an extent is < 1 or the volume has 2^31 voxels or more.
+ * Integer atomics only (one per block with a peak); nothing read back; capturable.  Argument checks run on the host before anything is
+ * launched and set bpx_last_error. */
+int64_t bpx_peaks_workspace(int Z, int Y, int X);
+int bpx_peak_local_max(const void* img_d, int dtype, int Z, int Y, int X, int rz, int ry, int rx, double threshold, int bz, int by, int bx,
+                       void* mask_d, void* keys_d, int max_peaks, int* num_d, void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
