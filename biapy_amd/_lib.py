@@ -74,6 +74,8 @@ _SIGS = {
     "bpx_debug_set_label_tiled": ([_i], _i),
     "bpx_edt_workspace": ([_i, _i, _i, _i], _i64),
     "bpx_edt": ([_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp, _i64, _vp], _i),
+    "bpx_edt_index_workspace": ([_i, _i, _i, _i], _i64),
+    "bpx_edt_index": ([_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp, _vp, _i64, _vp], _i),
     "bpx_watershed_workspace": ([_i, _i, _i], _i64),
     "bpx_watershed": ([_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp], _i),
     "bpx_overlap_workspace": ([_i64], _i64),

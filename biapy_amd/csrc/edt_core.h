@@ -120,6 +120,16 @@ template <class M, class S> struct EdtEnvelope {
       while (q >= 0 && tt >= x) pop();                                    // the stretches that begin at x (or, all of them beyond e gone, later)
     }
   }
+  // the same, telling which site wins: write(x, value, tp) with tp the winning site's column position, -1 where there is none.  While write
+  // runs, the winning site is the top entry - what the last put or get of the policy handed over (edt_column_sites reads its payload there).
+  template <class W> EDT_HD void flush_site(int s, int e, W&& write) {
+    while (q >= 0 && tt > e) pop();
+    for (int x = e; x >= s; --x) {
+      if (q < 0) { write(x, M::inf(), -1); continue; }
+      write(x, M::narrow(m.cost(x, tp, th)), tp);
+      while (q >= 0 && tt >= x) pop();
+    }
+  }
 };
 
 // ---- one column ---------------------------------------------------------------------------------------------------------------------
@@ -154,4 +164,56 @@ EDT_HD void edt_column(const M& m, S& st, int n, KeyF&& key, LoadF&& load, Store
     }
   }
   if (kprev != 0) env.flush(s, n - 1, store);
+}
+
+// ---- the nearest source (edt_index.hip) ---------------------------------------------------------------------------------------------------
+// Binary keys: 0 = a source, 1 = any other voxel.  Every voxel also gets the linear index of the source that realises its value; among equally
+// near sources the one with the smallest linear index, -1 where there is none.  The separable passes deliver exactly that when each of them
+// resolves ties to the smaller position: the row pass prefers the left source, a column pass the smaller y' among equal costs - which the
+// envelope does on the integer path, where push pops only a top that is strictly worse and first_better is the first position at which the later
+// site is strictly better.  On the fp64 path costs that differ by rounding only may go either way.
+//
+// The row: dl / dr = steps to the source on the left / right (0 = none), `at` = the voxel's linear index.  The left one on a tie.
+EDT_HD int64_t edt_row_steps(int64_t dl, int64_t dr) { return dl == 0 ? dr : (dr == 0 || dl <= dr ? dl : dr); }
+EDT_HD int32_t edt_row_site(int64_t at, int64_t dl, int64_t dr) {
+  if (dl != 0 && (dr == 0 || dl <= dr)) return (int32_t)(at - dl);
+  return dr != 0 ? (int32_t)(at + dr) : -1;
+}
+
+// One column with a payload per site.  The stack policy carries it: S has two int members, `cur` - stored with the entry by the next put -
+// and `top` - the payload of the entry the last put or get handed over, i.e. of the envelope's top.  site(i): the payload the pass before left
+// at position i (at a source: its own linear index, which is why the two foreign voxels bounding a run need no lookup of their own);
+// store(i, v, payload): the new value and the payload of the site that realises it, -1 where the value is inf.  In place is fine for the
+// values and for the payloads alike: a position is loaded before anything at or beyond it is stored, and the sites travel in the stack.
+// Sources are never stored (they keep value 0 and their own index) unless write_bg.
+template <class M, class S, class KeyF, class LoadF, class SiteF, class StoreF>
+EDT_HD void edt_column_sites(const M& m, S& st, int n, KeyF&& key, LoadF&& load, SiteF&& site, StoreF&& store, bool write_bg) {
+  typedef typename M::val val;
+  EdtEnvelope<M, S> env(m, st, n);
+  auto write = [&](int x, val v, int tp) { store(x, v, tp < 0 ? -1 : st.top); };
+  int s = 0, kprev = 0, pprev = -1;
+  for (int i0 = 0; i0 < n; i0 += EDT_BATCH) {
+    int kk[EDT_BATCH], pp[EDT_BATCH];
+    val ff[EDT_BATCH];
+    EDT_UNROLL
+    for (int j = 0; j < EDT_BATCH; ++j) {
+      kk[j] = 0; ff[j] = 0; pp[j] = -1;
+      if (j < n - i0) { kk[j] = key(i0 + j); ff[j] = load(i0 + j); pp[j] = site(i0 + j); }
+    }
+    EDT_UNROLL
+    for (int j = 0; j < EDT_BATCH; ++j) {
+      if (j >= n - i0) break;
+      const int i = i0 + j, k = kk[j], p = pp[j];
+      if (i > 0 && k != kprev) {
+        if (kprev != 0) { st.cur = p; env.push(s, i, 0); env.flush_site(s, i - 1, write); }     // the source after the run
+        s = i;
+        env.reset();
+        if (k != 0) { st.cur = pprev; env.push(s, i - 1, 0); }                                   // the source before the run
+      }
+      if (k != 0) { st.cur = p; env.push(s, i, ff[j]); }
+      else if (write_bg) store(i, (val)0, p);
+      kprev = k; pprev = p;
+    }
+  }
+  if (kprev != 0) env.flush_site(s, n - 1, write);
 }

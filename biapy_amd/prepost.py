@@ -14,6 +14,9 @@ percentiles / histogram on the host.
   ``scipy.ndimage.label``'s numbering bit for bit (``csrc/label.hip``), so the mask no longer leaves the device to be labelled;
 * ``distance_transform_edt`` / ``label_distance`` give the exact Euclidean distance map of the mask or of the labels
   (``csrc/edt.hip``): on a unit grid ``scipy.ndimage.distance_transform_edt`` bit for bit;
+* ``distance_transform_edt(return_indices=...)`` adds the nearest background voxel itself (``csrc/edt_index.hip``; among equally near ones the
+  raster-first - product-defined, checked against a host twin), and ``expand_labels`` / ``voronoi_on_mask`` on top of it grow the instances by
+  a distance without merging them and hand every masked voxel to its nearest instance;
 * ``watershed`` floods an image from the seeds of ``label`` inside a mask (``csrc/watershed.hip``): the marker-controlled watershed those two
   lead up to, with exactly stated semantics of its own (ties go to the raster-first edge) - product-defined, checked against a host twin;
 * ``label_overlap`` / ``matching`` judge the instances: the sparse contingency table of two label volumes (``csrc/overlap.hip``) and the
@@ -297,12 +300,15 @@ def remove_small_objects(labels: torch.Tensor, min_size: int = 64, relabel: bool
     return (out, left) if return_num else out
 
 
-# ---- exact Euclidean distance transform of the mask or of the labels (csrc/edt.hip) ----------------------------------------------------
+# ---- exact Euclidean distance transform of the mask or of the labels (csrc/edt.hip, csrc/edt_index.hip) -----------------------------------
 # What the instance workflow of the reference starts from after label(): the distance ("D") channel of its targets and the seeds of the
-# marker-controlled watershed (scipy.ndimage.distance_transform_edt / the edt package on the host there).  Not offered: return_indices, a
-# black border, more than 3 dimensions and any normalisation of the D channel - that stays with the caller.  The watershed is watershed() below.
+# marker-controlled watershed (scipy.ndimage.distance_transform_edt / the edt package on the host there), and - with the nearest background
+# voxel beside the distance - skimage.segmentation.expand_labels and the reference's "Voronoi on mask" step.  Not offered: indices for
+# label_distance, SciPy's choice among equally near voxels (the raster-first one is returned), a black border, more than 3 dimensions, 2^31
+# voxels or more, multi-GPU slabs and any normalisation of the D channel - that stays with the caller.  The watershed is watershed() below.
 
-def _edt(t: torch.Tensor, what: str, label_mode: bool, sampling, squared: bool) -> torch.Tensor:
+def _edt(t: torch.Tensor, what: str, label_mode: bool, sampling, squared: bool, distances: bool = True, indices: bool = False, invert: bool = False):
+    """The distances (``indices=False``: through ``bpx_edt``, as ever), or ``(distances or None, linear indices)`` through ``bpx_edt_index``."""
     if t.dim() not in (2, 3):
         raise ValueError(f"biapy_amd.prepost.{what} takes a 2-D (Y, X) or 3-D (Z, Y, X) tensor (got {t.dim()} dimensions)")
     samp = None
@@ -319,21 +325,38 @@ def _edt(t: torch.Tensor, what: str, label_mode: bool, sampling, squared: bool) 
     Z, Y, X = _label_volume(t, what)
     if t.numel() < 1:
         raise NotImplementedError(f"biapy_amd.prepost.{what}: a {tuple(t.shape)} volume has an empty axis")
-    need = int(lib.bpx_edt_workspace(Z, Y, X, 0 if samp is None else 1))
+    need = int((lib.bpx_edt_index_workspace if indices else lib.bpx_edt_workspace)(Z, Y, X, 0 if samp is None else 1))
     if need < 0:
         raise NotImplementedError(f"biapy_amd.prepost.{what}: a {tuple(t.shape)} volume is refused on the exact integer path - Z^2 + Y^2 + X^2 must "
                                   "stay below 2^31 - 1 (the squared distance would reach the sentinel)")
     k = t.contiguous()
     if k.dtype == torch.bool:
         k = k.view(torch.uint8)
+    dtype = L.I32 if k.dtype == torch.int32 else L.U8
+    if indices and not distances and samp is None:
+        need += 4 * t.numel()                                         # the integer path keeps its values in the distances: without them, in the workspace
     ws = torch.empty(need, dtype=torch.uint8, device=k.device)
-    out = torch.empty(t.shape, dtype=torch.int32 if (squared and samp is None) else torch.float32, device=k.device)
-    L.check(lib.bpx_edt(k.data_ptr(), L.I32 if k.dtype == torch.int32 else L.U8, 1 if label_mode else 0, Z, Y, X, samp, 1 if squared else 0,
-                        out.data_ptr(), ws.data_ptr(), need, L.stream_ptr()))
-    return out
+    out = torch.empty(t.shape, dtype=torch.int32 if (squared and samp is None) else torch.float32, device=k.device) if distances else None
+    if not indices:
+        L.check(lib.bpx_edt(k.data_ptr(), dtype, 1 if label_mode else 0, Z, Y, X, samp, 1 if squared else 0, out.data_ptr(), ws.data_ptr(), need,
+                            L.stream_ptr()))
+        return out
+    idx = torch.empty(t.shape, dtype=torch.int32, device=k.device)
+    L.check(lib.bpx_edt_index(k.data_ptr(), dtype, 1 if invert else 0, Z, Y, X, samp, 1 if squared else 0, out.data_ptr() if distances else None,
+                              idx.data_ptr(), ws.data_ptr(), need, L.stream_ptr()))
+    return out, idx
 
 
-def distance_transform_edt(mask: torch.Tensor, sampling=None, squared: bool = False) -> torch.Tensor:
+def _unravel(idx: torch.Tensor) -> torch.Tensor:
+    """(ndim, *shape) int32 coordinates of a linear-index volume; -1 stays -1 on every axis."""
+    coords, rest = [], idx
+    for n in reversed(idx.shape):
+        coords.append(torch.where(idx < 0, idx, rest % n))
+        rest = torch.div(rest, n, rounding_mode="floor")
+    return torch.stack(coords[::-1])
+
+
+def distance_transform_edt(mask: torch.Tensor, sampling=None, squared: bool = False, return_distances: bool = True, return_indices=False):
     """``scipy.ndimage.distance_transform_edt(mask, sampling=sampling)`` of a binary 2-D / 3-D ``uint8`` or ``bool`` device tensor: for every
     nonzero voxel the Euclidean distance to the nearest zero voxel, 0 on the zero voxels.  As in SciPy the volume border is no source.
 
@@ -342,16 +365,91 @@ def distance_transform_edt(mask: torch.Tensor, sampling=None, squared: bool = Fa
     ``sampling=(sz, sy, sx)`` (``(sy, sx)`` in 2-D; positive finite floats, anything else raises ``ValueError``) the work is done in fp64 and
     the result is the ``float32`` distance, or its square; a given ``sampling`` always takes that path, ``(1, 1, 1)`` too.
 
+    ``return_indices`` adds WHICH zero voxel is the nearest (``csrc/edt_index.hip``).  ``"linear"`` returns an ``int32`` tensor of the mask's
+    shape holding that voxel's linear index (C order), which is a third of the memory and what ``expand_labels`` / ``voronoi_on_mask`` use;
+    ``True`` returns SciPy's form, an ``int32`` tensor of shape ``(ndim, *mask.shape)`` holding its coordinates.  With both results asked for
+    the order is SciPy's, ``(distances, indices)``; ``return_distances=False`` returns the indices alone, and without indices raises
+    ``ValueError``.  The distances beside indices are those of the plain call, bit for bit.  THE RULE for the index: among equally near zero
+    voxels the one with the smallest linear index - the raster-first ``(z, y, x)`` - is returned; a zero voxel's index is its own.  SciPy
+    breaks such ties another way, so on the exact path the returned voxel is at SciPy's distance but need not be SciPy's voxel.  With
+    ``sampling`` the returned voxel is a nearest zero up to the fp64 path's rounding; which of several zeros whose fp64 costs differ only by
+    rounding is returned is UNSPECIFIED.
+
     ONE DIFFERENCE from SciPy: a mask without any zero voxel has no nearest zero, and every voxel gets a sentinel - ``INT32_MAX`` in the
-    ``int32`` result, ``+inf`` in the ``float32`` ones - where SciPy returns distances to a fictitious point.
+    ``int32`` result, ``+inf`` in the ``float32`` ones, ``-1`` in the indices (every coordinate) - where SciPy returns distances to a
+    fictitious point.
 
     Three launches fixed by the shape and the path, nothing read back, the same bits every run: the call can be captured in a graph.
     Refused before anything is launched: a CPU tensor (``RuntimeError``); other dtypes, an empty axis, 2^31 voxels or more and, on the exact
-    path, ``Z^2 + Y^2 + X^2 >= 2^31 - 1`` (``NotImplementedError``); other ranks (``ValueError``).  ``return_indices`` is not offered."""
+    path, ``Z^2 + Y^2 + X^2 >= 2^31 - 1`` (``NotImplementedError``); other ranks (``ValueError``)."""
     if mask.dtype not in (torch.uint8, torch.bool):
         raise NotImplementedError(f"biapy_amd.prepost.distance_transform_edt works on uint8 or bool masks (got {mask.dtype}); binarize() makes "
                                   "one, label_distance() takes int32 labels")
-    return _edt(mask, "distance_transform_edt", False, sampling, squared)
+    linear = isinstance(return_indices, str) and return_indices == "linear"
+    if not linear and not isinstance(return_indices, (bool, np.bool_)):
+        raise ValueError(f'biapy_amd.prepost.distance_transform_edt: return_indices must be False, True or "linear" (got {return_indices!r})')
+    if not return_indices and not return_distances:
+        raise ValueError("biapy_amd.prepost.distance_transform_edt: at least one of return_distances / return_indices must be asked for")
+    if not return_indices:
+        return _edt(mask, "distance_transform_edt", False, sampling, squared)
+    dist, idx = _edt(mask, "distance_transform_edt", False, sampling, squared, distances=bool(return_distances), indices=True)
+    if not linear:
+        idx = _unravel(idx)
+    return (dist, idx) if return_distances else idx
+
+
+def _nearest_label(labels: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """labels at the linear indices ``idx`` (-1: a volume without any label, whose voxel 0 is background too)."""
+    return torch.index_select(labels.contiguous().view(-1), 0, idx.clamp_min(0).view(-1)).view(labels.shape)
+
+
+def expand_labels(labels: torch.Tensor, distance=1, sampling=None) -> torch.Tensor:
+    """``skimage.segmentation.expand_labels(labels, distance=distance, spacing=sampling)`` of a 2-D / 3-D ``int32`` label tensor: a NEW ``int32``
+    tensor in which every background voxel whose nearest labelled voxel is no farther than ``distance`` takes that voxel's label; labelled
+    voxels keep theirs, so instances grow without merging.  It is ``distance_transform_edt(labels == 0, return_indices="linear")`` - taken on
+    the labels themselves, no inverted copy is made - followed by a gather.
+
+    On the exact path (``sampling=None``) the test is ``squared distance <= floor(distance^2)``, in integers.  With ``sampling`` it is
+    ``float32 distance <= float32(distance)``.  A ``distance`` beyond every distance of the volume grows into
+    all of the background.  BETWEEN TWO LABELS AT THE SAME DISTANCE the one whose nearest voxel is raster-first (smallest
+    linear index) wins - scikit-image inherits SciPy's choice there.  A volume without any label comes back all zeros.
+
+    The transform's three launches and a few element-wise torch ops over the linear index; nothing is read back, the call can be captured.
+    ``distance`` negative, NaN or infinite raises ``ValueError``; the other refusals are those of ``label_distance``."""
+    if labels.dtype != torch.int32:
+        raise NotImplementedError(f"biapy_amd.prepost.expand_labels works on the int32 labels of label() (got {labels.dtype})")
+    try:
+        d = float(distance)
+    except (TypeError, ValueError):
+        d = float("nan")
+    if not (math.isfinite(d) and d >= 0.0):
+        raise ValueError(f"biapy_amd.prepost.expand_labels: distance must be a finite number >= 0 (got {distance!r})")
+    dist, idx = _edt(labels, "expand_labels", False, sampling, sampling is None, indices=True, invert=True)
+    if sampling is None:
+        take = dist <= min(math.floor(min(d, 46341.0) ** 2), 2 ** 31 - 2)   # 46341^2 passes every finite value; below the sentinel of a volume without labels
+    else:
+        take = dist <= float(np.float32(min(d, 3.0e38)))              # finite in float32: below the +inf of a volume without labels
+    near = _nearest_label(labels, idx)
+    return torch.where(take, near, torch.zeros_like(near))
+
+
+def voronoi_on_mask(labels: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """The reference's "Voronoi on mask" post-processing: every voxel with ``mask != 0`` gets the label of its nearest labelled voxel (its own if
+    it has one), voxels outside the mask get 0.  ``labels``: 2-D / 3-D ``int32``; ``mask``: ``uint8`` / ``bool`` of the same shape (else
+    ``ValueError``).  Nearest on the unit grid, exactly; between two labels at the same distance the one whose nearest voxel is raster-first
+    wins.  A label volume without any label gives all zeros.  Returns a NEW ``int32`` tensor; nothing is read back, the call can be captured.
+    The other refusals are those of ``label_distance``."""
+    if labels.dtype != torch.int32:
+        raise NotImplementedError(f"biapy_amd.prepost.voronoi_on_mask works on the int32 labels of label() (got {labels.dtype})")
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise NotImplementedError(f"biapy_amd.prepost.voronoi_on_mask works on uint8 or bool masks (got {mask.dtype})")
+    if mask.shape != labels.shape:
+        raise ValueError(f"biapy_amd.prepost.voronoi_on_mask: labels and mask differ in shape ({tuple(labels.shape)} and {tuple(mask.shape)})")
+    if labels.is_cuda and mask.device != labels.device:
+        raise RuntimeError("biapy_amd.prepost runs on the MI355X only (mask is on %s, labels on %s); there is no CPU path" % (mask.device, labels.device))
+    _, idx = _edt(labels, "voronoi_on_mask", False, None, True, distances=False, indices=True, invert=True)
+    near = _nearest_label(labels, idx)
+    return torch.where(mask != 0, near, torch.zeros_like(near))
 
 
 def label_distance(labels: torch.Tensor, sampling=None, squared: bool = False) -> torch.Tensor:
@@ -393,7 +491,7 @@ def watershed(image: torch.Tensor, markers: torch.Tensor, mask: Optional[torch.T
     plateau between two seeds is NOT split in the middle (a flat line of 21 voxels with seeds at both ends: 20 go to the first seed).  The recipe
     for saturated maps is an ``int32`` image ``(q << 15) | min(d, 32767)`` with ``q`` the quantised value and ``d`` a distance to the nearest
     marker (``distance_transform_edt(markers == 0, squared=True)`` serves): it splits plateaus along the markers' Voronoi boundary (the same
-    line: 11 / 10).
+    line: 11 / 10).  ``voronoi_on_mask(markers, mask)`` gives that Voronoi split itself, as labels.
 
     Boruvka rounds on ``label``'s union-find (``csrc/watershed.hip``): ``4 R + 3`` launches with ``R = ceil(log2(max(n, 2))) + 1``, fixed by the
     shape and the connectivity; the rounds after the last one that joined anything return at once.  Nothing is read back, two runs give the same

@@ -842,6 +842,26 @@ int64_t bpx_edt_workspace(int Z, int Y, int X, int fp64_path);
 int bpx_edt(const void* key_d, int key_dtype, int label_mode, int Z, int Y, int X, const double* sampling, int squared, void* out_d, void* ws_d,
             int64_t ws_bytes, bpx_stream_t stream);
 
+/* ---- the same transform with the nearest source (biapy_amd/prepost.py: distance_transform_edt(return_indices=...), expand_labels,
+ *      voronoi_on_mask; csrc/edt_index.hip) ----
+ * keys (Z,Y,X) contiguous, BPX_U8 or BPX_I32; 2-D is Z = 1.  A voxel is a SOURCE when its value is 0; with invert != 0, when it is nonzero.
+ *   index_d (Z,Y,X) int32: for every voxel the linear index (C order) of the source u with the least |u - v|^2, |.| as in bpx_edt; among equally
+ *   near sources the one with the SMALLEST LINEAR INDEX (the raster-first one; not scipy's choice).  A source's index is its own.  A volume
+ *   without any source gets -1 everywhere, beside the distance sentinel.  On the fp64 path the source returned is a nearest one up to that path's
+ *   rounding; which of several sources whose fp64 costs differ by rounding only is returned is unspecified.
+ *   dist_d: the distances of bpx_edt for key = "not a source" (int32 squared / float32, the same bits), or NULL for the indices alone.
+ * Three launches fixed by (Z, Y, X) and the path, no atomics, nothing read back, the same bits every run, capturable.  Z * Y * X < 2^31; on the
+ *   integer path Z^2 + Y^2 + X^2 < 2^31 - 1.
+ *   bpx_edt_index_workspace : bytes of workspace OF A CALL WITH dist_d; an integer-path call with dist_d == NULL needs this PLUS 4 * Z * Y * X bytes
+ *                       (bpx_edt_index refuses less).  NEGATIVE for a refused shape, as bpx_edt_workspace.  The index travels in the envelope's stack
+ *                       entries: integer path 12 * E, E = max(T(Z * X) * Y, T(Y * X) * Z) with T(columns) = min(98304, a quarter of the columns
+ *                       rounded up to 64); the fp64 path 8 bytes per voxel + 20 * E, with or without dist_d.  The 4 more bytes per voxel without dist_d are
+ *                       the home of the integer path's values, which otherwise live in dist_d.
+ * Argument checks run on the host before anything is launched and set bpx_last_error. */
+int64_t bpx_edt_index_workspace(int Z, int Y, int X, int fp64_path);
+int bpx_edt_index(const void* key_d, int key_dtype, int invert, int Z, int Y, int X, const double* sampling, int squared, void* dist_d,
+                  int32_t* index_d, void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
+
 /* ---- seeded watershed of an image from a marker volume (biapy_amd/prepost.py: watershed; csrc/watershed.hip, csrc/watershed_core.h) ----
  * image (Z,Y,X) BPX_F32 or BPX_I32, markers (Z,Y,X) int32, mask (Z,Y,X) uint8 or NULL (every voxel), all contiguous; 2-D is Z = 1.
  *   nodes: the voxels with mask != 0.  edges: two nodes that are neighbours at `connectivity` (1 / 2 / 3 as bpx_label_u8).  weight of an edge:
