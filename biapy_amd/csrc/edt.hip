@@ -2,207 +2,29 @@
 // label_distance).  out(v) = 0 where key(v) == 0, else the least |u - v|^2 over the voxels u with key(u) != key(v) - its square root on
 // request - and a sentinel (INT32_MAX / +inf) where the volume holds no voxel of another key.  The volume border is no source.  Binary mode:
 // key = (value != 0), scipy.ndimage.distance_transform_edt bit for bit on a unit grid.  Label mode: key = value, each voxel's distance to the
-// nearest voxel that does not carry its label.  The rule, its separability and the one-dimensional pieces: edt_core.h.
-//
-// THREE LAUNCHES, fixed by the shape and the path alone; no atomics, no data-dependent waiting, every loop bounded by an extent:
-//   row pass     one wave per row, lanes along X (coalesced).  A forward sweep over the row's 64-voxel chunks finds every voxel's run start from
-//                a ballot of the key changes (the last start carried across chunks) and stores the steps to the left foreign voxel; a backward
-//                sweep finds the run end the same way and stores g = min(left, right)^2.
-//   column pass  (Y, then Z) one thread per column, consecutive lanes on consecutive x, so every load and store of a wave is one contiguous
-//                row segment.  Per run of equal nonzero keys: the lower envelope of the run's parabolas and of the foreign voxel on each side
-//                (edt_core.h), built on the way up, queried on the way back.  A persistent grid of T threads loops over the columns; a thread's
-//                stack keeps its first 32 (fp64: 16) entries in LDS and owns slab entries [q * T + t] of the workspace beyond, q < the column length.
-// INTEGER PATH (sampling == NULL): int32 values in place in out_d; the Z pass overwrites each int32 with its final int32 or float32.  64-bit
-// candidate sums; Z^2 + Y^2 + X^2 < 2^31 - 1 is required so that every finite value is below the sentinel (positions then fit 16 bits).
-// FP64 PATH (sampling given): fp64 values in an 8-byte array in the workspace; the Z pass writes float32(value) or float32(sqrt(value)).
+// nearest voxel that does not carry its label.  The rule, its separability and the one-dimensional pieces: edt_core.h.  The three launches,
+// the two paths and the kernels, shared with edt_index.hip: edt_kernels.h.  Here: the entry points of the form without indices.
 // WORKSPACE: per column pass T * (column length) stack entries of 8 (integer) / 16 (fp64) bytes with T = edt_threads(columns) <= 131072 and
 // <= a quarter of the columns (rounded up to a wave), the larger of the two passes: at most half the bytes of the output on the integer
-// path (plus one wave's stacks), 1 GiB at 1024^3.  The fp64 path adds 8 bytes per voxel.
-#include <algorithm>
-#include <cmath>
+// path (plus one wave's stacks), 1 GiB at 1024^3.  The fp64 path adds 8 bytes per voxel, in front of the stacks.
+#include "edt_kernels.h"
 
-#include "bpx_common.h"
-#include "edt_core.h"
-
-namespace {
-
-constexpr int EDT_MAX_THREADS = 131072;   // threads in flight of a column pass: 512 per CU
-
-struct Keys {               // the input volume: uint8 or int32; binary = every nonzero value is the same key
-  const void* p;
-  int i32, binary;
-  __device__ __forceinline__ int at(int64_t i) const {
-    const int v = i32 ? reinterpret_cast<const int*>(p)[i] : (int)reinterpret_cast<const uint8_t*>(p)[i];
-    return binary ? (v != 0) : v;
-  }
-};
-
-// Thread-private stack.  The first LDS_DEPTH entries live in LDS at [q * 64 + lane] (a column pass runs one wave per workgroup), where the
-// pushes and pops of nearly every run stay; deeper entries go to the workspace slab, entry q of thread t at [q * T + t] (the lanes of a wave
-// at one depth are contiguous).  PT: position and t packed into its two halves; H: the height.
-template <class PT, class H, int LDS_DEPTH> struct Stack {
-  static constexpr int DEPTH = LDS_DEPTH;
-  typedef PT pt_t;
-  typedef __attribute__((address_space(3))) PT lds_pt_t;     // typed as LDS: through generic pointers the compiler folds the two branches below
-  typedef __attribute__((address_space(3))) H lds_h_t;       // into one FLAT access of a selected address, which waits on the memory counter too
-  PT* pt;
-  H* h;
-  int64_t T, tid;
-  lds_pt_t* lpt;            // LDS, already at the lane
-  lds_h_t* lh;
-  static __device__ __forceinline__ PT pack(int pos, int t) { return (PT)(uint32_t)pos | ((PT)(uint32_t)t << (sizeof(PT) * 4)); }   // integer path: both <= 46340
-  __device__ __forceinline__ void put(int q, int pos, int t, H hh) {
-    const PT w = pack(pos, t);
-    if (q < LDS_DEPTH) { lpt[q * 64] = w; lh[q * 64] = hh; }
-    else { const int64_t i = (int64_t)q * T + tid; pt[i] = w; h[i] = hh; }
-  }
-  __device__ __forceinline__ void get(int q, int& pos, int& t, H& hh) const {
-    PT w;
-    if (q < LDS_DEPTH) { w = lpt[q * 64]; hh = lh[q * 64]; }
-    else { const int64_t i = (int64_t)q * T + tid; w = pt[i]; hh = h[i]; }
-    pos = (int)(w & (((PT)1 << (sizeof(PT) * 4)) - 1));
-    t = (int)(w >> (sizeof(PT) * 4));
-  }
-};
-typedef Stack<uint32_t, int32_t, 32> StackInt;   // 16 KiB of LDS per wave either way: 8 waves per CU at 131072 threads in flight
-typedef Stack<uint64_t, double, 16> StackF64;
-
-// One wave per row (grid-stride over the rows).  val[] takes the steps to the left foreign voxel first, then g.
-template <class M> __global__ void __launch_bounds__(256) edt_row_kernel(Keys keys, M m, int64_t rows, int X, typename M::val* __restrict__ val) {
-  typedef typename M::val V;
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * 4;
-  const int chunks = (int)(((int64_t)X + 63) / 64);
-  for (int64_t r = wave; r < rows; r += waves) {           // wave-uniform
-    const int64_t row = r * X;
-    int64_t carry = 0;
-    int edge = 0;                                          // the key next to the chunk, from the chunk before
-    for (int c = 0; c < chunks; ++c) {
-      const int64_t base = (int64_t)c * 64, x = base + lane;
-      const bool in = x < X;
-      const int k = in ? keys.at(row + x) : 0;
-      const int up = __shfl_up(k, 1, 64);                  // every lane takes part: a shuffle inside the conditional would read lane 0 while it is masked off
-      const int left = lane ? up : edge;
-      const unsigned long long bnd = __ballot(in && x > 0 && k != left);
-      const int64_t start = edt_run_start(bnd, lane, base, carry);
-      if (in) val[row + x] = (V)edt_left_steps(x, start);
-      if (bnd) carry = base + 63 - __builtin_clzll(bnd);
-      edge = __shfl(k, 63, 64);
-    }
-    carry = (int64_t)X - 1;
-    for (int c = chunks - 1; c >= 0; --c) {
-      const int64_t base = (int64_t)c * 64, x = base + lane;
-      const bool in = x < X;
-      const int k = in ? keys.at(row + x) : 0;
-      const int down = __shfl_down(k, 1, 64);
-      const int right = lane < 63 ? down : edge;
-      const unsigned long long bnd = __ballot(in && x < (int64_t)X - 1 && k != right);
-      const int64_t end = edt_run_end(bnd, lane, base, carry);
-      if (in) {
-        const int64_t dl = (int64_t)val[row + x], dr = edt_right_steps(x, end, X);     // the lane's own store of the forward sweep
-        const int64_t d = dl == 0 ? dr : (dr == 0 ? dl : (dl < dr ? dl : dr));
-        val[row + x] = k == 0 ? (V)0 : (d == 0 ? M::inf() : m.steps(d));
-      }
-      if (bnd) carry = base + __builtin_ctzll(bnd);
-      edge = __shfl(k, 0, 64);
-    }
-  }
-}
-
-// One thread per column, T threads looping over `cols` columns.  Column c: `len` positions from (c / inner) * outer + c % inner, `stride` apart
-// (Y pass: inner = X, outer = Y * X, stride = X; Z pass: inner = Y * X, outer = 0, stride = Y * X).
-// FINAL = 0: in place in val.  FINAL = 1: the last pass, which writes the result: the integer path in place (an int32, or the bits of a
-// float32, over the int32 just read), the fp64 path to outf.
-template <class M, class S, int FINAL>
-__global__ void __launch_bounds__(64) edt_column_kernel(Keys keys, M m, S slab, int64_t cols, int len, int64_t inner, int64_t outer, int64_t stride,
-                                                        typename M::val* val, float* outf, int squared) {
-  typedef typename M::val V;
-  constexpr bool FP64 = sizeof(V) == 8;
-  __shared__ typename S::pt_t lds_pt[S::DEPTH * 64];
-  __shared__ V lds_h[S::DEPTH * 64];
-  const int64_t tid = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  S st{slab.pt, slab.h, slab.T, tid, (typename S::lds_pt_t*)lds_pt + threadIdx.x, (typename S::lds_h_t*)lds_h + threadIdx.x};
-  for (int64_t c = tid; c < cols; c += st.T) {
-    const int64_t base = (c / inner) * outer + c % inner;
-    edt_column(
-        m, st, len, [&](int i) { return keys.at(base + (int64_t)i * stride); }, [&](int i) { return val[base + (int64_t)i * stride]; },
-        [&](int i, V v) {
-          const int64_t o = base + (int64_t)i * stride;
-          if (!FINAL) val[o] = v;
-          else if (FP64) outf[o] = (float)(squared ? (double)v : sqrt((double)v));
-          else if (squared) val[o] = v;
-          else val[o] = (V)__float_as_int(v == M::inf() ? INFINITY : (float)sqrt((double)v));
-        },
-        FINAL && FP64);
-  }
-}
-
-int64_t voxels_of(int Z, int Y, int X) { return (Z < 1 || Y < 1 || X < 1) ? 0 : (int64_t)Z * Y * X; }
-
-// threads in flight of a column pass over `cols` columns: a quarter of them, in whole waves, at most EDT_MAX_THREADS
-int64_t edt_threads(int64_t cols) { return std::min<int64_t>(EDT_MAX_THREADS, cdiv64(cdiv64(cols, 4), 64) * 64); }
-// stack entries of the workspace: the larger of the two column passes' (threads x column length)
-int64_t edt_entries(int Z, int Y, int X) { return std::max(edt_threads((int64_t)Z * X) * Y, edt_threads((int64_t)Y * X) * Z); }
-
-bool sq_limit_ok(int Z, int Y, int X) { return (int64_t)Z * Z + (int64_t)Y * Y + (int64_t)X * X < EDT_SQ_LIMIT; }
-
-template <class M, class S>
-void launch_columns(const Keys& keys, const double* w, S st /* T per pass */, int Z, int Y, int X, typename M::val* val, float* outf, int squared, hipStream_t s) {
-  const int64_t plane = (int64_t)Y * X;
-  M my, mz;
-  if constexpr (sizeof(typename M::val) == 8) { my.w = w[1]; mz.w = w[0]; }
-  st.T = edt_threads((int64_t)Z * X);
-  edt_column_kernel<M, S, 0><<<(unsigned)(st.T / 64), 64, 0, s>>>(keys, my, st, (int64_t)Z * X, Y, (int64_t)X, plane, (int64_t)X, val, outf, squared);
-  st.T = edt_threads(plane);
-  edt_column_kernel<M, S, 1><<<(unsigned)(st.T / 64), 64, 0, s>>>(keys, mz, st, plane, Z, plane, 0, plane, val, outf, squared);
-}
-
-}  // namespace
-
-extern "C" int64_t bpx_edt_workspace(int Z, int Y, int X, int fp64_path) {
-  const int64_t n = voxels_of(Z, Y, X);
-  if (n < 1 || n >= ((int64_t)1 << 31)) return -1;
-  if (!fp64_path && !sq_limit_ok(Z, Y, X)) return -1;
-  const int64_t entries = edt_entries(Z, Y, X);
-  return fp64_path ? n * 8 + entries * 16 : entries * 8;
-}
+extern "C" int64_t bpx_edt_workspace(int Z, int Y, int X, int fp64_path) { return edt_workspace<false>(Z, Y, X, fp64_path); }
 
 extern "C" int bpx_edt(const void* key_d, int key_dtype, int label_mode, int Z, int Y, int X, const double* sampling, int squared, void* out_d,
                        void* ws_d, int64_t ws_bytes, bpx_stream_t stream) {
   const char* fn = "bpx_edt";
   BPX_CHECK(key_d && out_d && ws_d, "%s: null pointer", fn);
-  BPX_CHECK(key_dtype == BPX_U8 || key_dtype == BPX_I32, "%s: keys must be BPX_U8 or BPX_I32 (got dtype %d)", fn, key_dtype);
-  BPX_CHECK(Z >= 1 && Y >= 1 && X >= 1, "%s: extents must be at least 1 (got %d x %d x %d)", fn, Z, Y, X);
-  const int64_t n = voxels_of(Z, Y, X);
-  BPX_CHECK(n < ((int64_t)1 << 31), "%s: %lld voxels: volumes of 2^31 voxels or more are not supported (int32 indices)", fn, (long long)n);
-  if (sampling) {
-    for (int a = 0; a < 3; ++a)
-      BPX_CHECK(std::isfinite(sampling[a]) && sampling[a] > 0.0, "%s: sampling must be positive and finite (got %g, %g, %g)", fn, sampling[0],
-                sampling[1], sampling[2]);
-  } else {
-    BPX_CHECK(sq_limit_ok(Z, Y, X), "%s: %d x %d x %d: Z^2 + Y^2 + X^2 must stay below 2^31 - 1 on the integer path (the squared distance would reach the sentinel)",
-              fn, Z, Y, X);
-  }
-  const int fp64 = sampling ? 1 : 0;
-  const int64_t need = bpx_edt_workspace(Z, Y, X, fp64);
+  if (edt_check_args(fn, key_dtype, Z, Y, X, sampling)) return 1;
+  const int64_t need = bpx_edt_workspace(Z, Y, X, sampling ? 1 : 0);
   BPX_CHECK(ws_bytes >= need, "%s: workspace too small (%lld bytes, bpx_edt_workspace says %lld)", fn, (long long)ws_bytes, (long long)need);
   BPX_CHECK(((uintptr_t)out_d & 3) == 0 && ((uintptr_t)ws_d & 7) == 0 && (key_dtype != BPX_I32 || ((uintptr_t)key_d & 3) == 0),
             "%s: out and int32 keys must be 4-byte aligned, the workspace 8-byte aligned", fn);
-  hipStream_t s = (hipStream_t)stream;
-  const Keys keys{key_d, key_dtype == BPX_I32 ? 1 : 0, label_mode ? 0 : 1};
-  const int64_t rows = (int64_t)Z * Y, entries = edt_entries(Z, Y, X);
-  const unsigned row_blocks = (unsigned)std::min<int64_t>(cdiv64(rows, 4), 1 << 16);
-  if (fp64) {
-    double* val = reinterpret_cast<double*>(ws_d);
-    const StackF64 st{reinterpret_cast<uint64_t*>(val + n), val + n + entries, 0, 0, nullptr, nullptr};
-    edt_row_kernel<EdtF64><<<row_blocks, 256, 0, s>>>(keys, EdtF64{sampling[2]}, rows, X, val);
-    launch_columns<EdtF64, StackF64>(keys, sampling, st, Z, Y, X, val, reinterpret_cast<float*>(out_d), squared, s);
-  } else {
-    int32_t* val = reinterpret_cast<int32_t*>(out_d);
-    const StackInt st{reinterpret_cast<uint32_t*>(ws_d), reinterpret_cast<int32_t*>(ws_d) + entries, 0, 0, nullptr, nullptr};
-    edt_row_kernel<EdtInt><<<row_blocks, 256, 0, s>>>(keys, EdtInt{}, rows, X, val);
-    launch_columns<EdtInt, StackInt>(keys, nullptr, st, Z, Y, X, val, nullptr, squared, s);
-  }
+  const EdtKeys<false> keys{key_d, key_dtype == BPX_I32 ? 1 : 0, label_mode ? 0 : 1};
+  // integer path: the values in out_d, the workspace all stacks; fp64 path: the values in the workspace, the stacks behind them
+  void* val = sampling ? ws_d : out_d;
+  void* stacks = sampling ? reinterpret_cast<double*>(ws_d) + edt_voxels(Z, Y, X) : ws_d;
+  edt_launch<false>(keys, sampling, Z, Y, X, val, stacks, nullptr, reinterpret_cast<float*>(out_d), squared, 1, (hipStream_t)stream);
   BPX_LAUNCH_CHECK(fn);
   return 0;
 }

@@ -1,6 +1,7 @@
-// The one-dimensional pieces of the exact Euclidean distance transform (edt.hip): where a voxel's run of equal keys starts and ends in a
-// row, and the lower envelope of parabolas over one run of a column with its query.  Compiles for the device (edt.hip) and for the host
-// (scripts/edt_cpu_check.cpp runs the same code over whole small volumes against a brute-force minimum).
+// The one-dimensional pieces of the exact Euclidean distance transform, without (edt.hip) and with (edt_index.hip) the nearest source: where
+// a voxel's run of equal keys starts and ends in a row, and the lower envelope of parabolas over one run of a column with its query.  Compiles
+// for the device (edt_kernels.h) and for the host (scripts/edt_cpu_check.cpp runs the same code over whole small volumes against a brute-force
+// minimum).
 //
 // RULE (include/biapy_amd.h): out(v) = 0 where key(v) == 0, else the least |u - v|^2 over the voxels u with key(u) != key(v); EDT_INF where
 // there is none.  Separable: the row pass leaves g = the squared distance along the row to the nearest voxel of another key; a column pass
@@ -12,6 +13,14 @@
 // The envelope's stack lives behind a policy `S` with put(q, pos, t, h) / get(q, pos, t, h); entry q is the q-th surviving site: its position,
 // the first position t at which it is the best so far, and its height h.  A run of a column of n positions pushes at most n sites (the run
 // and, where the column goes on, one foreign voxel on each side), so n entries per stack suffice.
+//
+// THE NEAREST SOURCE.  Binary keys: 0 = a source, 1 = any other voxel.  Every voxel also gets the linear index of the source that realises its
+// value; among equally near sources the one with the smallest linear index, -1 where there is none.  The separable passes deliver exactly
+// that when each of them resolves ties to the smaller position: the row pass prefers the left source, a column pass the smaller y' among
+// equal costs - which the envelope does on the integer path, where push pops only a top that is strictly worse and first_better is the first
+// position at which the later site is strictly better.  On the fp64 path costs that differ by rounding only may go either way.  A policy with
+// `S::SITES` carries that index as a payload per site in two int members: `cur` - stored with the entry by the next put - and `top` - the
+// payload of the entry the last put or get handed over, i.e. of the envelope's top.  A policy without has neither.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -45,6 +54,13 @@ EDT_HD int64_t edt_run_end(uint64_t bnd, int lane, int64_t base, int64_t carry) 
 // steps from x to the foreign voxel left of a run starting at `start` / right of a run ending at `end`; 0 = there is none
 EDT_HD int64_t edt_left_steps(int64_t x, int64_t start) { return start > 0 ? x - start + 1 : 0; }
 EDT_HD int64_t edt_right_steps(int64_t x, int64_t end, int64_t X) { return end < X - 1 ? end - x + 1 : 0; }
+// dl / dr = those steps to the left / right (0 = none): the steps to the nearer of the two, the left one on a tie, and - the foreign voxel
+// being a source, `at` the voxel's own linear index - the linear index of that source, -1 where the row has none
+EDT_HD int64_t edt_row_steps(int64_t dl, int64_t dr) { return dl == 0 ? dr : (dr == 0 || dl <= dr ? dl : dr); }
+EDT_HD int32_t edt_row_site(int64_t at, int64_t dl, int64_t dr) {
+  if (dl != 0 && (dr == 0 || dl <= dr)) return (int32_t)(at - dl);
+  return dr != 0 ? (int32_t)(at + dr) : -1;
+}
 
 // ---- the metrics --------------------------------------------------------------------------------------------------------------------
 struct EdtInt {
@@ -111,86 +127,42 @@ template <class M, class S> struct EdtEnvelope {
     tp = u; tt = t; th = h;
     st.put(q, u, t, h);
   }
-  // the values of the run [s, e], written from e down to s.  Entries whose stretch begins beyond e never win inside the run; entry 0 begins at s.
+  // the values of the run [s, e], written from e down to s: write(x, value, tp) with tp the winning site's column position, -1 where there is
+  // none.  Entries whose stretch begins beyond e never win inside the run; entry 0 begins at s.  While write runs, the winning site is the top
+  // entry - what the last put or get of the policy handed over (edt_column reads a payload there).
   template <class W> EDT_HD void flush(int s, int e, W&& write) {
-    while (q >= 0 && tt > e) pop();
-    for (int x = e; x >= s; --x) {
-      if (q < 0) { write(x, M::inf()); continue; }
-      write(x, M::narrow(m.cost(x, tp, th)));
-      while (q >= 0 && tt >= x) pop();                                    // the stretches that begin at x (or, all of them beyond e gone, later)
-    }
-  }
-  // the same, telling which site wins: write(x, value, tp) with tp the winning site's column position, -1 where there is none.  While write
-  // runs, the winning site is the top entry - what the last put or get of the policy handed over (edt_column_sites reads its payload there).
-  template <class W> EDT_HD void flush_site(int s, int e, W&& write) {
     while (q >= 0 && tt > e) pop();
     for (int x = e; x >= s; --x) {
       if (q < 0) { write(x, M::inf(), -1); continue; }
       write(x, M::narrow(m.cost(x, tp, th)), tp);
-      while (q >= 0 && tt >= x) pop();
+      while (q >= 0 && tt >= x) pop();                                    // the stretches that begin at x (or, all of them beyond e gone, later)
     }
   }
 };
 
 // ---- one column ---------------------------------------------------------------------------------------------------------------------
-// key(i) / load(i): the key and the value so far at position i; store(i, v): the new value.  In place is fine: a position is loaded before
-// anything at or beyond it is stored.  write_bg: also store 0 at background positions (a pass whose output is not its input).
-template <class M, class S, class KeyF, class LoadF, class StoreF>
-EDT_HD void edt_column(const M& m, S& st, int n, KeyF&& key, LoadF&& load, StoreF&& store, bool write_bg) {
+// key(i) / load(i): the key and the value so far at position i; store(i, v, payload): the new value and, with S::SITES, the payload of the
+// site that realises it, -1 where the value is inf (and always without S::SITES, where no payload exists at run time).  site(i), asked with
+// S::SITES only: the payload the pass before left at position i (at a source: its own linear index, which is why the two foreign voxels
+// bounding a run need no lookup of their own).  In place is fine for the values and for the payloads alike: a position is loaded before
+// anything at or beyond it is stored, and the sites travel in the stack.  write_bg: also store 0 at background positions (a pass whose
+// output is not its input); otherwise they are never stored and keep value 0 and, as sources, their own index.  Keys may be labels (runs of
+// equal nonzero keys) in either form; a payload then says nothing at a foreign voxel that is no source, so no caller combines the two.
+struct EdtNoSite {
+  EDT_HD int operator()(int) const { return -1; }
+};
+
+template <class M, class S, class KeyF, class LoadF, class StoreF, class SiteF = EdtNoSite>
+EDT_HD void edt_column(const M& m, S& st, int n, KeyF&& key, LoadF&& load, StoreF&& store, bool write_bg, SiteF&& site = SiteF()) {
   typedef typename M::val val;
   EdtEnvelope<M, S> env(m, st, n);
-  int s = 0, kprev = 0;
-  for (int i0 = 0; i0 < n; i0 += EDT_BATCH) {
-    int kk[EDT_BATCH];
-    val ff[EDT_BATCH];
-    EDT_UNROLL
-    for (int j = 0; j < EDT_BATCH; ++j) {
-      kk[j] = 0; ff[j] = 0;
-      if (j < n - i0) { kk[j] = key(i0 + j); ff[j] = load(i0 + j); }
-    }
-    EDT_UNROLL
-    for (int j = 0; j < EDT_BATCH; ++j) {
-      if (j >= n - i0) break;
-      const int i = i0 + j, k = kk[j];
-      if (i > 0 && k != kprev) {                                          // a run ends at i - 1, another starts at i
-        if (kprev != 0) { env.push(s, i, 0); env.flush(s, i - 1, store); }   // the foreign voxel after the run
-        s = i;
-        env.reset();
-        if (k != 0) env.push(s, i - 1, 0);                                // the foreign voxel before the run
-      }
-      if (k != 0) env.push(s, i, ff[j]);
-      else if (write_bg) store(i, (val)0);
-      kprev = k;
-    }
-  }
-  if (kprev != 0) env.flush(s, n - 1, store);
-}
-
-// ---- the nearest source (edt_index.hip) ---------------------------------------------------------------------------------------------------
-// Binary keys: 0 = a source, 1 = any other voxel.  Every voxel also gets the linear index of the source that realises its value; among equally
-// near sources the one with the smallest linear index, -1 where there is none.  The separable passes deliver exactly that when each of them
-// resolves ties to the smaller position: the row pass prefers the left source, a column pass the smaller y' among equal costs - which the
-// envelope does on the integer path, where push pops only a top that is strictly worse and first_better is the first position at which the later
-// site is strictly better.  On the fp64 path costs that differ by rounding only may go either way.
-//
-// The row: dl / dr = steps to the source on the left / right (0 = none), `at` = the voxel's linear index.  The left one on a tie.
-EDT_HD int64_t edt_row_steps(int64_t dl, int64_t dr) { return dl == 0 ? dr : (dr == 0 || dl <= dr ? dl : dr); }
-EDT_HD int32_t edt_row_site(int64_t at, int64_t dl, int64_t dr) {
-  if (dl != 0 && (dr == 0 || dl <= dr)) return (int32_t)(at - dl);
-  return dr != 0 ? (int32_t)(at + dr) : -1;
-}
-
-// One column with a payload per site.  The stack policy carries it: S has two int members, `cur` - stored with the entry by the next put -
-// and `top` - the payload of the entry the last put or get handed over, i.e. of the envelope's top.  site(i): the payload the pass before left
-// at position i (at a source: its own linear index, which is why the two foreign voxels bounding a run need no lookup of their own);
-// store(i, v, payload): the new value and the payload of the site that realises it, -1 where the value is inf.  In place is fine for the
-// values and for the payloads alike: a position is loaded before anything at or beyond it is stored, and the sites travel in the stack.
-// Sources are never stored (they keep value 0 and their own index) unless write_bg.
-template <class M, class S, class KeyF, class LoadF, class SiteF, class StoreF>
-EDT_HD void edt_column_sites(const M& m, S& st, int n, KeyF&& key, LoadF&& load, SiteF&& site, StoreF&& store, bool write_bg) {
-  typedef typename M::val val;
-  EdtEnvelope<M, S> env(m, st, n);
-  auto write = [&](int x, val v, int tp) { store(x, v, tp < 0 ? -1 : st.top); };
+  auto carry = [&](int p) {                                               // the payload of the site pushed next
+    if constexpr (S::SITES) st.cur = p;
+  };
+  auto write = [&](int x, val v, int tp) {
+    if constexpr (S::SITES) store(x, v, tp < 0 ? -1 : st.top);
+    else store(x, v, -1);
+  };
   int s = 0, kprev = 0, pprev = -1;
   for (int i0 = 0; i0 < n; i0 += EDT_BATCH) {
     int kk[EDT_BATCH], pp[EDT_BATCH];
@@ -198,22 +170,25 @@ EDT_HD void edt_column_sites(const M& m, S& st, int n, KeyF&& key, LoadF&& load,
     EDT_UNROLL
     for (int j = 0; j < EDT_BATCH; ++j) {
       kk[j] = 0; ff[j] = 0; pp[j] = -1;
-      if (j < n - i0) { kk[j] = key(i0 + j); ff[j] = load(i0 + j); pp[j] = site(i0 + j); }
+      if (j < n - i0) {
+        kk[j] = key(i0 + j); ff[j] = load(i0 + j);
+        if constexpr (S::SITES) pp[j] = site(i0 + j);
+      }
     }
     EDT_UNROLL
     for (int j = 0; j < EDT_BATCH; ++j) {
       if (j >= n - i0) break;
       const int i = i0 + j, k = kk[j], p = pp[j];
-      if (i > 0 && k != kprev) {
-        if (kprev != 0) { st.cur = p; env.push(s, i, 0); env.flush_site(s, i - 1, write); }     // the source after the run
+      if (i > 0 && k != kprev) {                                          // a run ends at i - 1, another starts at i
+        if (kprev != 0) { carry(p); env.push(s, i, 0); env.flush(s, i - 1, write); }   // the foreign voxel after the run
         s = i;
         env.reset();
-        if (k != 0) { st.cur = pprev; env.push(s, i - 1, 0); }                                   // the source before the run
+        if (k != 0) { carry(pprev); env.push(s, i - 1, 0); }              // the foreign voxel before the run
       }
-      if (k != 0) { st.cur = p; env.push(s, i, ff[j]); }
+      if (k != 0) { carry(p); env.push(s, i, ff[j]); }
       else if (write_bg) store(i, (val)0, p);
       kprev = k; pprev = p;
     }
   }
-  if (kprev != 0) env.flush_site(s, n - 1, write);
+  if (kprev != 0) env.flush(s, n - 1, write);
 }

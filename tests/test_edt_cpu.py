@@ -34,6 +34,19 @@ def test_entry_points_are_declared_exported_and_bound():
     assert "edt" not in open(os.path.join(ROOT, "biapy_amd", "csrc", "label.hip")).read()
 
 
+def test_both_forms_share_one_kernel_set():
+    csrc = os.path.join(ROOT, "biapy_amd", "csrc")
+    for name in ("edt.hip", "edt_index.hip"):                         # entry points only: the shared kernels, not a copy
+        source = open(os.path.join(csrc, name)).read()
+        assert '#include "edt_kernels.h"' in source and "__global__" not in source, name
+    kernels = open(os.path.join(csrc, "edt_kernels.h")).read()
+    assert re.findall(r"^template <[^>]*>\n?\s*__global__ void __launch_bounds__\(\d+\) (\w+)\(", kernels, re.M) == ["edt_row_kernel", "edt_column_kernel"]
+    assert kernels.count("__global__") == 2
+    core = open(os.path.join(csrc, "edt_core.h")).read()
+    assert len(re.findall(r"\bEDT_HD void edt_column\(", core)) == 1 and "edt_column(" in kernels
+    assert "edt_column_sites" not in core and "flush_site" not in core
+
+
 def test_host_checks_answer_without_a_device():
     from biapy_amd import _lib as L
 

@@ -32,7 +32,7 @@ def test_entry_points_are_declared_exported_and_bound():
     make = open(os.path.join(ROOT, "biapy_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SRCS = .*\bedt_index\.hip\b", make, re.M) and re.search(r"^edt_index\.o: .*edt_core\.h", make, re.M)
     assert L.lib._raw.bpx_edt_index_workspace.restype is L.C.c_int64
-    assert "address_space(3)" in source                               # the LDS part of the stack stays typed as LDS
+    assert "address_space(3)" in open(os.path.join(ROOT, "biapy_amd", "csrc", "edt_kernels.h")).read()     # the LDS part of the stack stays typed as LDS
 
 
 def test_host_checks_answer_without_a_device():
