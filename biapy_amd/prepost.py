@@ -33,7 +33,10 @@ percentiles / histogram on the host.
 * ``peak_local_max`` / ``peak_mask`` find the local maxima of a probability or distance map (``csrc/peaks.hip``): the detection workflow's
   points as a sorted, compact list that is never read back, and the markers of the "distance map -> peaks -> ``label`` -> ``watershed``"
   recipe as a 0 / 1 volume.  The call shape of ``skimage.feature.peak_local_max`` with a box of per-axis radii and semantics of its own (among
-  equal values the raster-first voxel wins, so no two peaks lie in each other's box) - product-defined, checked against a host twin.
+  equal values the raster-first voxel wins, so no two peaks lie in each other's box) - product-defined, checked against a host twin;
+* ``median_filter`` / ``median_filter_axes`` smooth a probability map or a mask before any of that (``csrc/median.hip``): the first step of
+  the reference's post-processing, ``scipy.ndimage.median_filter`` with a per-axis size as values and a NumPy twin bit for bit - exact
+  selection on order-preserving keys in LDS and registers, ``float32`` / ``uint8`` / ``bool``, windows of up to 125 voxels.
 
 Any contiguous float32 tensor is taken as it is, 16-byte aligned or not (``stack[1]`` of a batch with an odd element count per item is not):
 the scans then read four 4-byte words where they would read one 16-byte word, and return the same bits.
@@ -764,7 +767,7 @@ def select_objects(labels: torch.Tensor, keep: torch.Tensor, relabel: bool = Fal
 # ``connectivity`` is always an int with label()'s meaning: the element is scipy.ndimage.generate_binary_structure(ndim, connectivity).
 # NOT offered: arbitrary ``structure`` / ``footprint`` arrays; ``mask=`` and ``origin=``; ``iterations < 1`` (SciPy's "until stable" needs a
 # read-back); grey ``mode="constant"`` (out-of-volume neighbours are ignored: SciPy's default "reflect" for these elements); ball footprints on
-# grey input; find_boundaries' "outer" / "subpixel"; clear_border's ``buffer_size`` and ``mask``; the median filter; volumes of 2^31 voxels or
+# grey input; find_boundaries' "outer" / "subpixel"; clear_border's ``buffer_size`` and ``mask``; volumes of 2^31 voxels or
 # more; multi-GPU slabs; the watershed_by_channels threshold logic itself, which is now a short sequence of these calls.
 
 _MORPH_ERODE, _MORPH_DILATE, _MORPH_BOUNDARY = 0, 1, 2            # include/biapy_amd.h: bpx_morph's op
@@ -1123,3 +1126,119 @@ def peak_local_max(image: torch.Tensor, min_distance=1, threshold_abs=None, excl
     else:
         values = (k - 2 ** 31).masked_fill(filler, 0).to(torch.int32)
     return coords, values, num
+
+
+# ---- median filter: the first step of the reference's post-processing of a prediction (csrc/median.hip) ---------------------------------------------
+# POST_PROCESSING.MEDIAN_FILTER with MEDIAN_FILTER_AXIS / MEDIAN_FILTER_SIZE in the reference's configuration (key names from memory, unverified)
+# runs scipy.ndimage.median_filter over the float probability volume on the host before any threshold, with a per-axis size that is 1 on the
+# axes not named.  Exact selection on order-preserving keys, so the call is held against SciPy as values and against a NumPy twin bit for bit.
+# NOT offered: even sizes (SciPy shifts the window's origin there), sizes above 15, windows of more than 125 voxels, ``footprint=``,
+# ``origin=``, ``output=``, the modes "mirror" and "wrap", rank and percentile filters; volumes of 2^31 voxels or more; multi-GPU slabs.
+
+_MEDIAN_MAX_SIZE = 15                                                 # csrc/median_core.h: MEDIAN_MAX_SIZE
+_MEDIAN_MAX_WINDOW = 125                                              # csrc/median_core.h: MEDIAN_MAX_WINDOW
+_MEDIAN_MODES = {"reflect": 0, "nearest": 1, "constant": 2}           # include/biapy_amd.h: bpx_median_filter's mode
+_MEDIAN_AXES = ("xy", "yx", "yz", "zy", "zx", "xz", "z", "y", "x", "xyz")
+
+
+def _median_sizes(size, ndim: int) -> Tuple[int, ...]:
+    sizes = _per_axis(size, ndim, "size")
+    if any(s < 1 for s in sizes):
+        raise ValueError(f"size must be at least 1 on every axis (got {size!r})")
+    if any(s % 2 == 0 for s in sizes):
+        raise NotImplementedError(f"biapy_amd.prepost.median_filter: size must be odd on every axis (got {size!r}); SciPy shifts the window's "
+                                  "origin for an even size and that is not offered")
+    if any(s > _MEDIAN_MAX_SIZE for s in sizes):
+        raise NotImplementedError(f"biapy_amd.prepost.median_filter: size must be at most {_MEDIAN_MAX_SIZE} on every axis (got {size!r})")
+    if math.prod(sizes) > _MEDIAN_MAX_WINDOW:
+        raise NotImplementedError(f"biapy_amd.prepost.median_filter: a window of {math.prod(sizes)} voxels (size {size!r}); at most "
+                                  f"{_MEDIAN_MAX_WINDOW} are supported")
+    return sizes
+
+
+def median_filter(x: torch.Tensor, size=3, mode: str = "reflect", cval: float = 0.0) -> torch.Tensor:
+    """``scipy.ndimage.median_filter(x, size=size, mode=mode, cval=cval)`` of a 2-D ``(Y, X)`` or 3-D ``(Z, Y, X)`` device tensor, as a tensor of
+    ``x``'s shape and dtype: ``float32`` (probabilities, distance maps), ``uint8`` (masks, class maps) or ``bool`` (viewed as ``uint8``, ``bool``
+    comes back: the median of a binary mask is the majority vote).  Channels are the caller's loop: ``x[..., c]``; a non-contiguous view is made
+    contiguous.
+
+    ``size`` is an int or one int per axis in ``(z, y, x)`` order, every entry odd and in ``1..15``, the window ``W = sz * sy * sx <= 125``
+    voxels; ``W = 1`` returns a copy.  ``mode`` is ``"reflect"`` (SciPy's default, ``d c b a | a b c d``, over as many periods as the window
+    needs), ``"nearest"`` or ``"constant"`` with ``cval`` (finite for ``float32``, an integer in ``0..255`` for ``uint8`` / ``bool``).
+
+    The result at a voxel is the element of rank ``W // 2`` among the ``W`` window values, ordered by their order-preserving ``uint32`` key -
+    ``float32``: ``bits | 0x80000000`` for a clear sign bit, ``~bits`` otherwise; ``uint8``: the value - and returned with its bits.  That is
+    SciPy's result as values, and the NumPy twin ``tests/median_ref.py`` bit for bit.  Two points SciPy leaves open are stated: ``-0.0`` sorts
+    below ``+0.0``, and NaNs sort by their bits (negative-sign NaNs below ``-inf``, positive-sign NaNs above ``+inf`` - product-defined).
+    Nothing is computed, so nothing is flushed: denormals come back as they went in.
+
+    One launch (``csrc/median.hip``): a block stages its tile and halo into LDS as keys and every thread selects in registers.  No workspace,
+    nothing read back, two runs give the same bits, the call can be captured in a graph.
+
+    Refused before anything is launched, in this order: other dtypes (``NotImplementedError``), other ranks (``ValueError``), an empty axis
+    (``NotImplementedError``); a ``size`` of another length or below 1 (``ValueError``), even, above 15 or with ``W > 125``
+    (``NotImplementedError``); ``"mirror"`` / ``"wrap"`` (``NotImplementedError``) and unknown modes (``ValueError``); a ``cval`` the dtype
+    cannot hold (``ValueError``); 2^31 voxels or more (``NotImplementedError``); last, a CPU tensor (``RuntimeError``).  ``footprint``,
+    ``origin`` and ``output`` are not offered."""
+    sizes, m, c = _median_check(x, size, mode, cval)
+    return _median_run(_on_device(x), sizes, m, c)
+
+
+def _median_check(x: torch.Tensor, size, mode, cval):
+    """Every refusal of ``median_filter`` but the last, in the house order; the sizes, the mode's code and ``cval`` as ``bpx_median_filter`` takes them."""
+    what = "median_filter"
+    if x.dtype not in (torch.float32, torch.uint8, torch.bool):
+        raise NotImplementedError(f"biapy_amd.prepost.{what} works on float32, uint8 or bool tensors (got {x.dtype})")
+    if x.dim() not in (2, 3):
+        raise ValueError(f"biapy_amd.prepost.{what} takes a 2-D (Y, X) or 3-D (Z, Y, X) tensor (got {x.dim()} dimensions)")
+    if x.numel() < 1:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: a {tuple(x.shape)} volume has an empty axis")
+    sizes = _median_sizes(size, x.dim())
+    if mode in ("mirror", "wrap"):
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: mode {mode!r} is not offered (reflect, nearest or constant)")
+    if mode not in _MEDIAN_MODES:
+        raise ValueError(f"mode must be 'reflect', 'nearest' or 'constant' (got {mode!r})")
+    c = float(cval)
+    if x.dtype == torch.float32:
+        if not (math.isfinite(c) and abs(c) <= 3.4028234663852886e38):
+            raise ValueError(f"cval must be finite as float32 (got {cval!r})")
+    elif not (math.isfinite(c) and c == math.floor(c) and 0.0 <= c <= 255.0):
+        raise ValueError(f"cval must be an integer in 0..255 for a {x.dtype} tensor (got {cval!r})")
+    if x.numel() >= 2 ** 31:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: {x.numel()} voxels - volumes of 2^31 voxels or more are not supported (int32 indices)")
+    return sizes, _MEDIAN_MODES[mode], c
+
+
+def _median_run(x: torch.Tensor, sizes, mode: int, cval: float) -> torch.Tensor:
+    """One launch of ``bpx_median_filter`` on the checked device tensor ``x``."""
+    src = x.contiguous()
+    if src.dtype == torch.bool:
+        src = src.view(torch.uint8)
+    out = torch.empty(x.shape, dtype=src.dtype, device=src.device)
+    Z, Y, X = (1,) * (3 - x.dim()) + tuple(x.shape)
+    sz, sy, sx = (1,) * (3 - x.dim()) + tuple(sizes)
+    L.check(lib.bpx_median_filter(src.data_ptr(), L.F32 if src.dtype == torch.float32 else L.U8, Z, Y, X, sz, sy, sx, mode, cval, out.data_ptr(),
+                                  L.stream_ptr()))
+    return out.view(torch.bool) if x.dtype == torch.bool else out
+
+
+def median_filter_axes(x: torch.Tensor, axes, size) -> torch.Tensor:
+    """The reference's call shape on one 3-D ``(Z, Y, X)`` channel: ``median_filter`` with ``size`` along the axes that ``axes`` names and 1
+    along the others, ``mode="reflect"``.  ``axes`` is one of ``'xy' 'yx' 'yz' 'zy' 'zx' 'xz' 'z' 'y' 'x' 'xyz'`` with an int ``size``, or a list
+    of them with a list of one size each, applied in sequence as the reference's loop does (each step filters the result of the one before).
+    ``median_filter_axes(p, 'xy', 5)`` is ``median_filter(p, (1, 5, 5))``.  No kernel of its own; the refusals are ``median_filter``'s, after a
+    ``ValueError`` for an ``axes`` that is none of the above, lists of different lengths, or a tensor that is not 3-D."""
+    if isinstance(axes, str):
+        axes, size = [axes], [size]
+    elif not isinstance(size, (tuple, list)) or len(size) != len(axes):
+        raise ValueError(f"a list of axes takes a list of one size each (got axes {axes!r}, size {size!r})")
+    for a in axes:
+        if a not in _MEDIAN_AXES:
+            raise ValueError(f"axes must be one of {', '.join(repr(v) for v in _MEDIAN_AXES)} (got {a!r})")
+    if x.dtype in (torch.float32, torch.uint8, torch.bool) and x.dim() != 3:
+        raise ValueError(f"biapy_amd.prepost.median_filter_axes takes a 3-D (Z, Y, X) tensor (got {x.dim()} dimensions)")
+    steps = [_median_check(x, tuple(int(s) if ax in a else 1 for ax in "zyx"), "reflect", 0.0) for a, s in zip(axes, size)]
+    x = _on_device(x)
+    for sizes, m, c in steps:                                          # every step is checked before the first one is launched
+        x = _median_run(x, sizes, m, c)
+    return x

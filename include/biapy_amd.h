@@ -950,6 +950,19 @@ int64_t bpx_peaks_workspace(int Z, int Y, int X);
 int bpx_peak_local_max(const void* img_d, int dtype, int Z, int Y, int X, int rz, int ry, int rx, double threshold, int bz, int by, int bx,
                        void* mask_d, void* keys_d, int max_peaks, int* num_d, void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
 
+/* ---- median filter (biapy_amd/prepost.py: median_filter, median_filter_axes; csrc/median.hip, csrc/median_core.h) ----
+ * in / out (Z,Y,X) contiguous, dtype BPX_F32 (4-byte aligned) or BPX_U8; Z * Y * X < 2^31; a 2-D image is Z = 1, sz = 1; out_d must not be
+ * in_d.  out[v] is the element of rank W / 2 among the W = sz * sy * sx values of the window centred on v (sizes odd, 1..15 each, W <= 125),
+ * ordered by their order-preserving uint32 key (float32: bits | 0x80000000 for a clear sign bit, ~bits otherwise, so -0.0 < +0.0 and NaNs sort
+ * by their bits beyond the infinities of their sign; uint8: the value) and returned with its bits: scipy.ndimage.median_filter(in, size=(sz,
+ * sy, sx), mode=, cval=) as values.  mode: 0 "reflect" (d c b a | a b c d, over as many periods as the window needs), 1 "nearest", 2
+ * "constant" with cval (finite as float32; an integer in 0..255 for uint8; ignored by the other modes but checked).
+ * One launch fixed by (Z, Y, X, dtype, sizes): a block stages its tile and halo into LDS as keys and every thread selects in registers with
+ * min / max only.  No workspace, no atomics, nothing read back; the same bits every run; capturable.  Argument checks run on the host before
+ * anything is launched and set bpx_last_error. */
+int bpx_median_filter(const void* in_d, int dtype, int Z, int Y, int X, int sz, int sy, int sx, int mode, double cval, void* out_d,
+                      bpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
