@@ -55,6 +55,14 @@ def _sums(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return _sums_and_loss(logits, target)[0]
 
 
+def _aligned16(x: torch.Tensor) -> torch.Tensor:
+    """x as a contiguous float32 tensor whose storage starts on a 16-byte boundary, which the 16-byte loads of bpx_seg_loss_sums / _bwd_fused
+    require.  A batch slice ``x[i:i + 1]`` is contiguous as it stands and starts 4 i V bytes into its base: it is copied when that is no multiple
+    of 16 (a fresh allocation is aligned)."""
+    x = x.contiguous().to(torch.float32)
+    return x.clone() if x.data_ptr() % 16 else x
+
+
 def _prep(logits: torch.Tensor, target: torch.Tensor):
     if not logits.is_cuda:
         raise RuntimeError("biapy_amd.losses run on the MI355X only (logits are on %s); there is no CPU path" % logits.device)
@@ -62,7 +70,7 @@ def _prep(logits: torch.Tensor, target: torch.Tensor):
         raise NotImplementedError("biapy_amd.losses implement the 1-channel (binary) head; use the reference losses for multi-class outputs")
     if target.shape != logits.shape:
         raise ValueError(f"target shape {tuple(target.shape)} != logits shape {tuple(logits.shape)}")
-    return logits.contiguous().to(torch.float32), target.contiguous().to(torch.float32)
+    return _aligned16(logits), _aligned16(target)
 
 
 class _SegLossFn(torch.autograd.Function):
