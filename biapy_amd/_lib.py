@@ -87,6 +87,8 @@ _SIGS = {
     "bpx_peaks_workspace": ([_i, _i, _i], _i64),
     "bpx_peak_local_max": ([_vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp], _i),
     "bpx_median_filter": ([_vp, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _vp], _i),
+    "bpx_sepfilter_workspace": ([_i, _i, _i, _i, _i, _i], _i64),
+    "bpx_sepfilter": ([_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, C.c_double, _vp, _vp, _i64, _vp], _i),
     "bpx_scan_blocks": ([_i64], _i),
     "bpx_select_workspace": ([], _i64),
     "bpx_select_kth_f32": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),

@@ -36,7 +36,10 @@ percentiles / histogram on the host.
   equal values the raster-first voxel wins, so no two peaks lie in each other's box) - product-defined, checked against a host twin;
 * ``median_filter`` / ``median_filter_axes`` smooth a probability map or a mask before any of that (``csrc/median.hip``): the first step of
   the reference's post-processing, ``scipy.ndimage.median_filter`` with a per-axis size as values and a NumPy twin bit for bit - exact
-  selection on order-preserving keys in LDS and registers, ``float32`` / ``uint8`` / ``bool``, windows of up to 125 voxels.
+  selection on order-preserving keys in LDS and registers, ``float32`` / ``uint8`` / ``bool``, windows of up to 125 voxels;
+* ``separable_filter`` / ``gaussian_filter`` / ``gaussian_laplace`` are the linear smoothing next to it (``csrc/sepfilter.hip``): one pass per
+  axis with run-time weights of up to 65 taps, ``scipy.ndimage.correlate1d`` / ``gaussian_filter`` / ``gaussian_laplace`` in a stated
+  ``float32`` arithmetic - a NumPy twin bit for bit, SciPy's ``float64`` result within a derived per-element bound.
 
 Any contiguous float32 tensor is taken as it is, 16-byte aligned or not (``stack[1]`` of a batch with an odd element count per item is not):
 the scans then read four 4-byte words where they would read one 16-byte word, and return the same bits.
@@ -1242,3 +1245,199 @@ def median_filter_axes(x: torch.Tensor, axes, size) -> torch.Tensor:
     for sizes, m, c in steps:                                          # every step is checked before the first one is launched
         x = _median_run(x, sizes, m, c)
     return x
+
+
+# ---- separable filter: linear smoothing of an image or a probability map (csrc/sepfilter.hip) --------------------------------------------------------
+# DATA.PREPROCESS.GAUSSIAN_BLUR in the reference's configuration (key name from memory, unverified) calls skimage.filters.gaussian, which is
+# scipy.ndimage.gaussian_filter per channel; the detection workflow smooths the probability map before peak_local_max, and blob_log starts from
+# gaussian_laplace.  One separable correlation with run-time per-axis weights serves all three; the Gaussian is one way to fill the weights.
+# NOT offered: uint8 / integer input, ``output=``, ``axes=``, mode "wrap", radii above 32, ``uniform_filter``, ``blob_log``; volumes of 2^31
+# voxels or more; multi-GPU slabs.
+
+_SEPFILTER_MAX_RADIUS = 32                                            # csrc/sepfilter_core.h: SEPFILTER_MAX_RADIUS
+_SEPFILTER_MODES = {"reflect": 0, "mirror": 1, "nearest": 2, "constant": 3}     # include/biapy_amd.h: bpx_sepfilter's mode
+
+
+def _sepfilter_input(x: torch.Tensor, what: str) -> None:
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f"biapy_amd.prepost.{what} works on float32 tensors (got {x.dtype}); call .float() first")
+    if x.dim() not in (2, 3):
+        raise ValueError(f"biapy_amd.prepost.{what} takes a 2-D (Y, X) or 3-D (Z, Y, X) tensor (got {x.dim()} dimensions)")
+    if x.numel() < 1:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: a {tuple(x.shape)} volume has an empty axis")
+
+
+def _sepfilter_border(x: torch.Tensor, what: str, mode, cval) -> Tuple[int, float]:
+    if mode == "wrap":
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: mode 'wrap' is not offered (reflect, mirror, nearest or constant)")
+    if mode not in _SEPFILTER_MODES:
+        raise ValueError(f"mode must be 'reflect', 'mirror', 'nearest' or 'constant' (got {mode!r})")
+    c = float(cval)
+    if not (math.isfinite(c) and abs(c) <= 3.4028234663852886e38):
+        raise ValueError(f"cval must be finite as float32 (got {cval!r})")
+    if x.numel() >= 2 ** 31:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: {x.numel()} voxels - volumes of 2^31 voxels or more are not supported (int32 indices)")
+    return _SEPFILTER_MODES[mode], c
+
+
+def _sepfilter_run(x: torch.Tensor, weights, mode: int, cval: float) -> torch.Tensor:
+    """``bpx_sepfilter`` on the checked device tensor ``x``: ``weights`` holds one contiguous ``float32`` array or ``None`` per axis of ``x``."""
+    src = x.contiguous()
+    out = torch.empty(x.shape, dtype=torch.float32, device=src.device)
+    Z, Y, X = (1,) * (3 - x.dim()) + tuple(x.shape)
+    ws3 = (None,) * (3 - x.dim()) + tuple(weights)
+    radii = [-1 if w is None else (len(w) - 1) // 2 for w in ws3]
+    need = int(lib.bpx_sepfilter_workspace(Z, Y, X, *radii))
+    ws = torch.empty(need // 4, dtype=torch.float32, device=src.device) if need > 0 else None
+    wp = [None if w is None else w.ctypes.data for w in ws3]         # host pointers: copied into the kernel arguments before the call returns
+    L.check(lib.bpx_sepfilter(src.data_ptr(), Z, Y, X, wp[0], radii[0], wp[1], radii[1], wp[2], radii[2], mode, cval, out.data_ptr(), L.ptr(ws),
+                              max(need, 0), L.stream_ptr()))
+    return out
+
+
+def separable_filter(x: torch.Tensor, weights, mode: str = "reflect", cval: float = 0.0) -> torch.Tensor:
+    """``scipy.ndimage.correlate1d`` along each given axis in turn, of a 2-D ``(Y, X)`` or 3-D ``(Z, Y, X)`` ``float32`` device tensor, as a new
+    ``float32`` tensor.  ``weights`` holds one entry per axis of ``x``, in ``(z, y, x)`` order: ``None`` (the axis is skipped) or a 1-D sequence of
+    ``2 r + 1`` floats, ``r`` in ``0..32``, rounded to ``float32``.  Channels are the caller's loop; a non-contiguous view is made contiguous.
+
+    The arithmetic is product-defined: along an axis, ``acc = w[0] * v[f(i - r)]``, then ``acc = acc + w[j] * v[f(i + j - r)]`` for ``j = 1 ..
+    2 r`` in that order, every ``*`` and ``+`` one IEEE ``float32`` operation (no FMA, no folded taps, denormals kept); the ``float32`` result of
+    one axis is the input of the next, z then y then x.  ``f`` is the border: ``"reflect"`` (``d c b a | a b c d``), ``"mirror"`` (``d c b | a b
+    c d``), ``"nearest"`` or ``"constant"`` with ``float32(cval)``, over as many periods as ``r`` needs.  The NumPy twin ``tests/gauss_ref.py``
+    gives the same bits; SciPy's ``float64`` result lies within the per-element bound derived there.
+
+    One launch per given axis (``csrc/sepfilter.hip``), the weights by value in the kernel arguments; a workspace of one volume when two or more
+    axes are given.  Nothing read back, two runs give the same bits, the call can be captured in a graph.  With no axis given the result is a
+    copy.
+
+    Refused before anything is launched, in this order: other dtypes (``NotImplementedError``), other ranks (``ValueError``), an empty axis
+    (``NotImplementedError``); ``weights`` of another length, an entry that is not 1-D, of even length or not finite as ``float32``
+    (``ValueError``), more than 65 taps (``NotImplementedError``); ``"wrap"`` (``NotImplementedError``) and unknown modes (``ValueError``); a
+    ``cval`` that is not finite as ``float32`` (``ValueError``); 2^31 voxels or more (``NotImplementedError``); last, a CPU tensor
+    (``RuntimeError``)."""
+    what = "separable_filter"
+    _sepfilter_input(x, what)
+    if not isinstance(weights, (tuple, list)) or len(weights) != x.dim():
+        raise ValueError(f"weights must hold one entry (None or a 1-D sequence) per axis of the {x.dim()}-D tensor (got {weights!r})")
+    ws = []
+    for w in weights:
+        if w is None:
+            ws.append(None)
+            continue
+        w64 = np.asarray(w, dtype=np.float64)
+        if w64.ndim != 1 or w64.size % 2 == 0:
+            raise ValueError(f"every entry of weights must be a 1-D sequence of odd length (got shape {w64.shape})")
+        with np.errstate(over="ignore"):
+            w32 = np.ascontiguousarray(w64.astype(np.float32))
+        if not np.isfinite(w32).all():
+            raise ValueError("every weight must be finite as float32")
+        ws.append(w32)
+    for w in ws:
+        if w is not None and w.size > 2 * _SEPFILTER_MAX_RADIUS + 1:
+            raise NotImplementedError(f"biapy_amd.prepost.{what}: {w.size} taps on an axis; at most {2 * _SEPFILTER_MAX_RADIUS + 1} "
+                                      f"(radius {_SEPFILTER_MAX_RADIUS}) are supported")
+    m, c = _sepfilter_border(x, what, mode, cval)
+    return _sepfilter_run(_on_device(x), ws, m, c)
+
+
+def _gaussian_weights(sigma: float, order: int, radius: int) -> np.ndarray:
+    """The ``float64`` weights ``scipy.ndimage.gaussian_filter1d`` hands to ``correlate1d``: the sampled Gaussian normalised to sum 1, times the
+    polynomial of its ``order``-th derivative, reversed (a correlation, not a convolution).  SciPy's arithmetic restated step by step, so the
+    ``float64`` values are the same bits."""
+    exponent_range = np.arange(order + 1)
+    sigma2 = sigma * sigma
+    x = np.arange(-radius, radius + 1)
+    phi_x = np.exp(-0.5 / sigma2 * x ** 2)
+    phi_x = phi_x / phi_x.sum()
+    if order == 0:
+        return phi_x[::-1]
+    q = np.zeros(order + 1)
+    q[0] = 1
+    D = np.diag(exponent_range[1:], 1)                                 # D @ q(x) = q'(x)
+    P = np.diag(np.ones(order) / -sigma2, -1)                          # P @ q(x) = q(x) * p'(x), p'(x) = -1 / sigma^2
+    Q_deriv = D + P
+    for _ in range(order):
+        q = Q_deriv.dot(q)
+    q = (x[:, None] ** exponent_range).dot(q)
+    return (q * phi_x)[::-1]
+
+
+def _per_axis_of(value, ndim: int, name: str) -> list:
+    if isinstance(value, (tuple, list)):
+        if len(value) != ndim:
+            raise ValueError(f"{name} must be a scalar or one value per axis of the {ndim}-D tensor (got {len(value)} values)")
+        return list(value)
+    return [value] * ndim
+
+
+def _gaussian_check(x: torch.Tensor, what: str, sigma, order, mode, cval, truncate, radius):
+    """Every refusal of ``gaussian_filter`` but the last, in the house order; the ``float32`` weights per axis (``None``: skipped), the mode's code
+    and ``cval`` as ``bpx_sepfilter`` takes them."""
+    _sepfilter_input(x, what)
+    nd = x.dim()
+    sigmas = [float(v) for v in _per_axis_of(sigma, nd, "sigma")]
+    orders = _per_axis_of(order, nd, "order")
+    radii = _per_axis_of(radius, nd, "radius")
+    if any(math.isnan(sd) or sd < 0 for sd in sigmas):
+        raise ValueError(f"sigma must not be negative (got {sigma!r})")
+    if any(isinstance(o, bool) or int(o) != o or not 0 <= int(o) <= 2 for o in orders):
+        raise ValueError(f"order must be 0, 1 or 2 on every axis (got {order!r})")
+    t = float(truncate)
+    if not (math.isfinite(t) and t >= 0):
+        raise ValueError(f"truncate must be finite and not negative (got {truncate!r})")
+    if any(r is not None and (isinstance(r, bool) or int(r) != r or int(r) < 0) for r in radii):
+        raise ValueError(f"radius must be None or a non-negative integer on every axis (got {radius!r})")
+    plan = []
+    for sd, o, r in zip(sigmas, orders, radii):
+        if sd <= 1e-15:                                                # SciPy skips the axis
+            plan.append(None)
+            continue
+        lw = int(t * sd + 0.5) if r is None else int(r)
+        if lw > _SEPFILTER_MAX_RADIUS:
+            cause = f"sigma {sd:g} with truncate {t:g}" if r is None else f"radius={lw} (sigma {sd:g})"
+            raise NotImplementedError(f"biapy_amd.prepost.{what}: {cause} needs a radius of {lw} voxels; at most {_SEPFILTER_MAX_RADIUS} are supported")
+        plan.append((sd, int(o), lw))
+    m, c = _sepfilter_border(x, what, mode, cval)
+    ws = [None if p is None else np.ascontiguousarray(_gaussian_weights(*p).astype(np.float32)) for p in plan]
+    return ws, m, c
+
+
+def gaussian_filter(x: torch.Tensor, sigma, order=0, mode: str = "reflect", cval: float = 0.0, truncate: float = 4.0, radius=None) -> torch.Tensor:
+    """``scipy.ndimage.gaussian_filter(x, sigma, order=order, mode=mode, cval=cval, truncate=truncate, radius=radius)`` of a 2-D ``(Y, X)`` or 3-D
+    ``(Z, Y, X)`` ``float32`` device tensor, as a new ``float32`` tensor.  ``sigma``, ``order`` (0, 1 or 2: the Gaussian, its first or second
+    derivative) and ``radius`` are a scalar or one value per axis in ``(z, y, x)`` order; an axis with ``sigma <= 1e-15`` is skipped, as SciPy
+    does; the radius of an axis is ``int(truncate * sigma + 0.5)`` unless given, at most 32.  Channels are the caller's loop; a non-contiguous view
+    is made contiguous.
+
+    The weights are SciPy's, computed in NumPy ``float64`` on the host with SciPy's own steps and then rounded to ``float32``; the filtering is
+    ``separable_filter``'s stated ``float32`` arithmetic (product-defined: one multiply and one add per tap in tap order, no FMA, denormals
+    kept, z then y then x).  The NumPy twin ``tests/gauss_ref.py`` gives the same bits; ``scipy.ndimage.gaussian_filter`` of the ``float64``
+    image lies within the per-element bound derived there.
+
+    One launch per filtered axis (``csrc/sepfilter.hip``), nothing read back, two runs give the same bits, the call can be captured in a graph.
+
+    Refused before anything is launched, in this order: other dtypes (``NotImplementedError``, call ``.float()``), other ranks
+    (``ValueError``), an empty axis (``NotImplementedError``); ``sigma`` / ``order`` / ``radius`` of another length, a negative sigma, an order
+    outside 0..2, a negative truncate or radius (``ValueError``); a radius above 32 (``NotImplementedError``, naming the sigma); ``"wrap"``
+    (``NotImplementedError``) and unknown modes (``ValueError``); a ``cval`` that is not finite as ``float32`` (``ValueError``); 2^31 voxels or
+    more (``NotImplementedError``); last, a CPU tensor (``RuntimeError``).  ``output`` and ``axes`` are not offered."""
+    ws, m, c = _gaussian_check(x, "gaussian_filter", sigma, order, mode, cval, truncate, radius)
+    return _sepfilter_run(_on_device(x), ws, m, c)
+
+
+def gaussian_laplace(x: torch.Tensor, sigma, mode: str = "reflect", cval: float = 0.0, truncate: float = 4.0) -> torch.Tensor:
+    """``scipy.ndimage.gaussian_laplace(x, sigma, mode=mode, cval=cval, truncate=truncate)``: the sum over the axes of ``gaussian_filter`` with
+    ``order = 2`` on that axis and 0 on the others - the scale-space operator of ``blob_log`` (``blob_log`` itself is not offered).  The
+    ``float32`` adds run in axis order z, y, x as torch adds on the device; each term is ``gaussian_filter``'s stated arithmetic, so the twin of
+    ``tests/gauss_ref.py`` gives the same bits.  Two (2-D) or three (3-D) ``gaussian_filter`` calls and one add each after the first; the
+    refusals are ``gaussian_filter``'s, every term checked before the first is launched."""
+    what = "gaussian_laplace"
+    _sepfilter_input(x, what)
+    nd = x.dim()
+    terms = [_gaussian_check(x, what, sigma, [2 if a == axis else 0 for a in range(nd)], mode, cval, truncate, None) for axis in range(nd)]
+    x = _on_device(x)
+    out = None
+    for ws, m, c in terms:
+        g = _sepfilter_run(x, ws, m, c)
+        out = g if out is None else out.add_(g)
+    return out

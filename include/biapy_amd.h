@@ -963,6 +963,26 @@ int bpx_peak_local_max(const void* img_d, int dtype, int Z, int Y, int X, int rz
 int bpx_median_filter(const void* in_d, int dtype, int Z, int Y, int X, int sz, int sy, int sx, int mode, double cval, void* out_d,
                       bpx_stream_t stream);
 
+/* ---- separable filter (biapy_amd/prepost.py: separable_filter, gaussian_filter, gaussian_laplace; csrc/sepfilter.hip, csrc/sepfilter_core.h) ----
+ * in / out / ws (Z,Y,X) contiguous float32 (4-byte aligned; 16-byte stores are used only where an address allows them); Z * Y * X < 2^31; a
+ * 2-D image is Z = 1 with wz = NULL.  Correlation with one 1-D kernel per axis, z then y then x (scipy.ndimage.correlate1d chained): wz / wy /
+ * wx are HOST pointers to 2 r + 1 float32 weights, r in 0..32; NULL with a negative radius skips the axis.  Along an axis of n voxels
+ *   acc = w[0] * v[f(i - r)];  acc = acc + w[j] * v[f(i + j - r)] for j = 1 .. 2r in that order;  out[i] = acc
+ * every * and + one IEEE float32 operation, round to nearest, no FMA, no folded taps, denormals kept; the float32 result of one axis is the
+ * input of the next.  mode f: 0 "reflect" (d c b a | a b c d), 1 "mirror" (d c b | a b c d; n = 1 maps to 0), 2 "nearest", 3 "constant" with
+ * float32(cval) outside the axis at every pass (cval finite as float32; ignored by the other modes but checked); all fold over as many
+ * periods as r needs.
+ *   bpx_sepfilter_workspace : 4 * Z * Y * X bytes when two or more radii are not negative, else 0; -1 when an extent is < 1, the volume has
+ *                             2^31 voxels or more, or a radius is above 32.
+ * One launch per active axis; the passes alternate between out_d and ws_d so that the last writes out_d; in_d is never written and must
+ * overlap neither; with no active axis out is a copy of in's bits.  The weights travel by value in the kernel arguments: no atomics, nothing
+ * allocated, copied or read back; the same bits every run; capturable.  Argument checks run on the host before anything is launched, in
+ * this order, and set bpx_last_error: null pointers (in_d, out_d, weights of a radius that is not negative); extents; 2^31 voxels; a radius
+ * outside 0..32; a weight that is not finite; the mode; cval; the workspace; aliasing; alignment. */
+int64_t bpx_sepfilter_workspace(int Z, int Y, int X, int rz, int ry, int rx);
+int bpx_sepfilter(const void* in_d, int Z, int Y, int X, const float* wz, int rz, const float* wy, int ry, const float* wx, int rx, int mode,
+                  double cval, void* out_d, void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
