@@ -65,6 +65,9 @@ _SIGS = {
     "bpx_aug_apply": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_uint64, _f, _i, _vp, _vp, _vp], _i),
     "bpx_warp_draw": ([_vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "bpx_warp_apply": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp], _i),
+    "bpx_elastic_draw": ([C.c_uint64, C.c_uint64, _f, _f, _i, _vp, _vp, _vp], _i),
+    "bpx_elastic_noise": ([C.c_uint64, _i, _i, _i, _vp, _vp, _vp], _i),
+    "bpx_elastic_apply": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp], _i),
     "bpx_patch_draw": ([_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp], _i),
     "bpx_patch_gather": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp], _i),
     "bpx_label_workspace": ([_i, _i, _i], _i64),

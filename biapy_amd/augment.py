@@ -9,6 +9,8 @@ Per sample every enabled transform fires independently with probability ``da_pro
 
 0. affine warp in the (Y, X) plane, identically for every z and channel, when ``rotation`` / ``zoom`` / ``shear`` / ``shift`` are given (the
    section "The affine warp" below); image bilinear, target nearest;
+0b. elastic deformation in the (Y, X) plane, identically for every z and channel, when ``elastic`` is given (the section "The elastic
+   deformation" below); image bilinear, target nearest;
 1. geometry, image and target alike: ``v = torch.rot90(src, k, dims=(Y, X))`` with ``k`` uniform in {0, 1, 2, 3} when ``rot90`` fires (else 0),
    then ``torch.flip`` over Z (``zflip``), Y (``vflip``) and X (``hflip``) for the flips that fired - bit for bit a permutation;
 2. contrast, image only: ``v = (v - m) * a + m``, ``a = 1 + c`` with ``c`` uniform in ``contrast``, ``m`` the fp32 rounding of the sample's
@@ -49,12 +51,43 @@ of the other draws (the call's counter value is read from words 5-6 of the sampl
 ``bpx_warp_draw``, ``bpx_aug_mean`` (contrast only), ``bpx_warp_apply`` into scratch tensors the augmenter owns and ``bpx_aug_apply`` from those
 into the output - a second pass over the batch that leaves the gather pass as it is; with none on, exactly the launches listed above.
 ``last_warp_records`` / ``warp_records=`` are the inspection hooks.
+
+The elastic deformation (step 0b; product-defined and parity-unpinned like the rest)
+------------------------------------------------------------------------------------
+``elastic=dict(alpha=(12, 16), sigma=4.0, mode="constant", cval=0.0)`` (every key optional): a smooth random displacement field per sample,
+scaled by ``alpha`` voxels, ``0 <= lo <= hi <= 1024``; ``sigma`` in ``(0, 8]`` is the Gaussian's (the tap radius ``int(4 sigma + 0.5)`` must not
+exceed the 32 ``bpx_sepfilter`` takes); ``mode`` is one of ``AFFINE_MODES`` and ``cval`` the image's value outside in ``"constant"`` mode.  The
+step runs after the affine warp, if any, and before the gather pass; a sample fires with ``da_prob``, independently of every other transform.  A
+sample's draw is an ELASTIC RECORD of 8 words (layout: ``include/biapy_amd.h``): word 0 the flags (bit 0 fired), word 1 ``alpha`` (fp32, 0 when
+the sample did not fire), words 2-3 the call's counter value, the other words 0.  Draws: the key and counter words of the other draws (the
+counter value is read from words 5-6 of the sample's record), stream 24: ``r0`` fires, ``r1`` is ``alpha``'s uniform.
+
+The field of a call is a float32 tensor ``(B, 2, Y, X)``, plane 0 ``dy`` and plane 1 ``dx``, fewer than 2^31 elements (``ValueError`` otherwise,
+before anything is launched).  Noise: element ``e`` (the linear ``(plane, y, x)`` index within the sample's field) is ``n = u * 2 - 1`` with
+``u = (r >> 8) * 2^-24``, ``r`` word ``e mod 4`` of the Philox block with the key ``(seed low ^ 0x454C4153, seed high)`` and the counter words
+``(q low, q high ^ (sample << 8), c low, c high)``, ``q = e // 4``: a function of (seed, counter value, sample, element) only.  Smoothing:
+``bpx_sepfilter`` on the field seen as a ``(2B, Y, X)`` volume, the z axis skipped, y and x with ``prepost._gaussian_weights(sigma, 0, radius)``
+rounded to fp32, mode ``"reflect"`` - the arithmetic ``prepost.separable_filter`` states.  The smoothed field ``s`` is NOT rescaled.
+
+Output voxel (y, x) reads the source at ``fy = y + alpha s[0][y][x]``, ``fx = x + alpha s[1][y][x]`` - fp32, one multiply and one add each, no
+FMA - each clamped to ``[-2^30, 2^30]`` (a NaN becomes the lower bound).  From there exactly the warp's rules above: the four bilinear taps and
+their association for the image, the voxel ``(floor(fy + 0.5), floor(fx + 0.5))`` for the target, the border rule per integer tap index,
+``cval`` for the image and 0 for the target in ``"constant"`` mode.  A sample whose flags are 0 is copied bit for bit; whatever the field holds,
+every load stays inside the sample's plane.
+
+With ``elastic`` given the call launches, everything on: ``bpx_aug_draw``, ``bpx_warp_draw``, ``bpx_elastic_draw``, ``bpx_aug_mean``,
+``bpx_warp_apply``, ``bpx_elastic_noise``, ``bpx_sepfilter``, ``bpx_elastic_apply``, ``bpx_aug_apply``; the field, its smoothing workspace and
+the deformed pair are scratch the augmenter owns and keeps until the shape changes.  The contrast mean ``m`` stays the mean of the INPUT sample.
+``last_elastic_records`` / ``last_elastic_field`` (the smoothed, unscaled field of the last call) inspect; ``elastic_records=`` (skips the
+draw) and ``elastic_field=`` (skips noise and smoothing) inject.  With ``elastic=None`` nothing of this exists and a call launches what it
+launched before.
 """
 from __future__ import annotations
 
 import math
 from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -74,6 +107,14 @@ WF_ROT, WF_ZOOM, WF_SHEAR, WF_SHIFT = 1, 2, 4, 8                 # warp record w
 WW_FLAGS, WW_M, WW_P = 0, 1, 8
 AFFINE_MODES = {"constant": 0, "reflect": 1, "edge": 2}          # BPX_WARP_CONSTANT / _REFLECT / _EDGE
 WARP_M_MAX = 2.0 ** 20                                            # |matrix word| accepted through warp_records=
+
+ELASTIC_REC_WORDS = 8
+EF_FIRED = 1                                                      # elastic record word 0
+EW_FLAGS, EW_ALPHA, EW_CTR = 0, 1, 2
+ELASTIC_STREAM, ELASTIC_KEY_XOR = 24, 0x454C4153                  # BPX_ELASTIC_STREAM / _KEY_XOR
+ELASTIC_ALPHA_MAX, ELASTIC_SIGMA_MAX, ELASTIC_RADIUS_MAX = 1024.0, 8.0, 32      # the radius limit is bpx_sepfilter's
+ELASTIC_FIELD_MAX = 2 ** 31                                       # elements of a call's field: bpx_sepfilter's int32 indices
+_ELASTIC_DEFAULTS = dict(alpha=(12.0, 16.0), sigma=4.0, mode="constant", cval=0.0)
 
 _CUTOUT_DEFAULTS = dict(n=(1, 3), size=(0.05, 0.3), cval=0.0, apply_to_mask=False)
 
@@ -138,11 +179,12 @@ def _span(t: torch.Tensor):
 
 
 class DeviceAugmenter:
-    """See the module docstring.  ``aug(x, t, out=None, records=None, warp_records=None) -> (x_out, t_out)``."""
+    """See the module docstring.  ``aug(x, t, out=None, records=None, warp_records=None, elastic_records=None, elastic_field=None) ->
+    (x_out, t_out)``."""
 
     def __init__(self, *, da_prob: float = 0.5, rot90: bool = False, zflip: bool = False, vflip: bool = False, hflip: bool = False,
                  brightness=None, contrast=None, gaussian_noise=None, cutout=None, seed: Optional[int] = None, rotation=None, zoom=None,
-                 shear=None, shift=None, affine_mode: str = "constant", affine_cval: float = 0.0):
+                 shear=None, shift=None, affine_mode: str = "constant", affine_cval: float = 0.0, elastic=None):
         da_prob = float(da_prob)
         if not (0.0 <= da_prob <= 1.0):
             raise ValueError(f"da_prob must lie in [0, 1], got {da_prob}")
@@ -187,6 +229,37 @@ class DeviceAugmenter:
             raise ValueError(f"affine_cval must be a number, got {affine_cval!r}") from None
         if not math.isfinite(self.affine_cval):
             raise ValueError(f"affine_cval must be finite, got {affine_cval!r}")
+        self.elastic = None
+        if elastic is not None:
+            if not isinstance(elastic, dict):
+                raise ValueError(f"elastic must be a dict with the keys {sorted(_ELASTIC_DEFAULTS)}, got {elastic!r}")
+            unknown = set(elastic) - set(_ELASTIC_DEFAULTS)
+            if unknown:
+                raise ValueError(f"elastic has unknown keys {sorted(unknown)}")
+            e = {**_ELASTIC_DEFAULTS, **elastic}
+            alpha = _bounded("elastic['alpha']", e["alpha"], 0.0, ELASTIC_ALPHA_MAX)
+            if alpha is None:
+                raise ValueError("elastic['alpha'] must be a (lo, hi) pair of numbers, got None")
+            try:
+                sigma = float(e["sigma"])
+            except (TypeError, ValueError):
+                raise ValueError(f"elastic['sigma'] must be a number, got {e['sigma']!r}") from None
+            if not (math.isfinite(sigma) and 0.0 < sigma <= ELASTIC_SIGMA_MAX):
+                raise ValueError(f"elastic['sigma'] must satisfy 0 < sigma <= {ELASTIC_SIGMA_MAX:g}: the tap radius int(4 sigma + 0.5) must not exceed the "
+                                 f"{ELASTIC_RADIUS_MAX} voxels bpx_sepfilter takes, got {e['sigma']!r}")
+            if e["mode"] not in AFFINE_MODES:
+                raise ValueError(f"elastic['mode'] must be one of {sorted(AFFINE_MODES)}, got {e['mode']!r}")
+            try:
+                ecval = float(e["cval"])
+            except (TypeError, ValueError):
+                raise ValueError(f"elastic['cval'] must be a number, got {e['cval']!r}") from None
+            if not math.isfinite(ecval):
+                raise ValueError(f"elastic['cval'] must be finite, got {e['cval']!r}")
+            self.elastic = dict(alpha=alpha, sigma=sigma, mode=e["mode"], cval=ecval)
+            radius = int(4.0 * sigma + 0.5)
+            from .prepost import _gaussian_weights
+
+            self._ew = np.ascontiguousarray(_gaussian_weights(sigma, 0, radius).astype(np.float32))   # y and x alike, computed once
         if seed is None:
             rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
             seed = torch.initial_seed() + rank                        # ranks draw differently
@@ -199,6 +272,10 @@ class DeviceAugmenter:
         self._ws = None
         self._warp = None             # int32 (B, 16): the warp records
         self._wx = self._wt = None    # the warped pair, input of the gather pass
+        self._erec = None             # int32 (B, 8): the elastic records
+        self._efield = None           # float32 (B, 2, Y, X): the smoothed field
+        self._ews = None              # float32 (2, B, 2, Y, X): the noise, then bpx_sepfilter's workspace
+        self._ex = self._et = None    # the deformed pair, input of the gather pass
 
     # ---- configuration --------------------------------------------------------------------------------------------------------
     @property
@@ -231,12 +308,19 @@ class DeviceAugmenter:
         c = self.warp_config()
         return L.WarpCfg(c["seed"], c["thr"], c["enable"], 0, *c["rotation"], *c["zoom"], *c["shear"], *c["shift"])
 
+    def elastic_config(self) -> Optional[dict]:
+        """The elastic step's parameters as plain numbers (``tests/elastic_ref.draw`` takes the same dict); ``None`` without ``elastic=``."""
+        if self.elastic is None:
+            return None
+        return dict(seed=self.seed, thr=int(math.floor(self.da_prob * 2.0 ** 32)), alpha=self.elastic["alpha"], sigma=self.elastic["sigma"],
+                    radius=(len(self._ew) - 1) // 2, mode=self.elastic["mode"], cval=self.elastic["cval"])
+
     def _cfg_struct(self) -> "L.AugCfg":
         c = self.config()
         return L.AugCfg(c["seed"], c["thr"], c["enable"], c["box"][0], c["box"][1], *c["contrast"], *c["brightness"], *c["noise"], *c["size"])
 
     @classmethod
-    def from_cfg(cls, cfg, seed: Optional[int] = None, *, affine: bool = False) -> Optional["DeviceAugmenter"]:
+    def from_cfg(cls, cfg, seed: Optional[int] = None, *, affine: bool = False, elastic: bool = False) -> Optional["DeviceAugmenter"]:
         """The augmenter a reference configuration asks for, ``None`` when ``AUGMENTOR.ENABLE`` is false.
 
         Mapped ``AUGMENTOR`` keys: ``DA_PROB``; ``ROT90``, ``ZFLIP``, ``VFLIP``, ``HFLIP``; ``BRIGHTNESS`` + ``BRIGHTNESS_FACTOR``; ``CONTRAST`` +
@@ -249,6 +333,10 @@ class DeviceAugmenter:
         (``ZOOM_IN_Z`` is refused: the warp acts in the (Y, X) plane), ``SHEAR`` + ``SHEAR_RANGE`` (degrees), ``SHIFT`` + ``SHIFT_RANGE`` (fractions)
         and ``AFFINE_MODE`` (``constant`` / ``reflect`` / ``edge``; ``wrap`` and ``symmetric`` are refused by name; ``reflect`` when the key is
         absent, as the reference's tree is remembered).  It is opt-in because these semantics are this package's own: the default keeps refusing them.
+
+        ``elastic=True`` also maps ``ELASTIC`` onto step 0b: ``E_ALPHA`` (a range), ``E_SIGMA`` (a scalar, used as it is; a range is refused by
+        name) and ``E_MODE`` (``constant`` / ``reflect`` / ``edge``; any other is refused by name).  Opt-in for the same reason: the default, and
+        ``affine=True`` alone, keep refusing ``ELASTIC``.
 
         The key names are written from memory of the reference's configuration tree and could not be verified against it on the build machine;
         the semantics of every transform are this package's own (parity-unpinned, see the module docstring)."""
@@ -268,7 +356,7 @@ class DeviceAugmenter:
             if k not in items and get(k, False) is True:
                 items[k] = True
         for k in sorted(items):
-            if items[k] is True and k not in _MAPPED_SWITCHES and k not in _NEUTRAL_SWITCHES and not (affine and k in _AFFINE_SWITCHES):
+            if items[k] is True and k not in _MAPPED_SWITCHES and k not in _NEUTRAL_SWITCHES and not (affine and k in _AFFINE_SWITCHES) and not (elastic and k == "ELASTIC"):
                 raise NotImplementedError(f"AUGMENTOR.{k} is enabled but biapy_amd.augment.DeviceAugmenter does not implement it (supported: "
                                           f"{', '.join(sorted(_MAPPED_SWITCHES - {'ENABLE'}))}); keep this transform in the loader or switch it off")
         kw = dict(da_prob=get("DA_PROB", 0.5), rot90=bool(get("ROT90", False)), zflip=bool(get("ZFLIP", False)),
@@ -298,6 +386,16 @@ class DeviceAugmenter:
                 raise NotImplementedError(f"AUGMENTOR.AFFINE_MODE = {mode!r} is not implemented by biapy_amd.augment.DeviceAugmenter (supported: "
                                           f"{', '.join(sorted(AFFINE_MODES))})")
             kw["affine_mode"] = mode
+        if elastic and get("ELASTIC", False):
+            sigma = get("E_SIGMA", _ELASTIC_DEFAULTS["sigma"])
+            if isinstance(sigma, (tuple, list)) or hasattr(sigma, "__len__"):
+                raise NotImplementedError(f"AUGMENTOR.E_SIGMA = {sigma!r} is a range; biapy_amd.augment.DeviceAugmenter takes one sigma per augmenter "
+                                          f"(its weights are computed once): give a scalar")
+            emode = str(get("E_MODE", _ELASTIC_DEFAULTS["mode"]))
+            if emode not in AFFINE_MODES:
+                raise NotImplementedError(f"AUGMENTOR.E_MODE = {emode!r} is not implemented by biapy_amd.augment.DeviceAugmenter (supported: "
+                                          f"{', '.join(sorted(AFFINE_MODES))})")
+            kw["elastic"] = dict(alpha=tuple(get("E_ALPHA", _ELASTIC_DEFAULTS["alpha"])), sigma=sigma, mode=emode)
         return cls(**kw)
 
     # ---- state ----------------------------------------------------------------------------------------------------------------
@@ -322,13 +420,24 @@ class DeviceAugmenter:
         return self._warp
 
     @property
+    def last_elastic_records(self) -> Optional[torch.Tensor]:
+        """The ``(B, 8)`` int32 device tensor of the last call's elastic records (``None`` before the first call that deforms)."""
+        return self._erec
+
+    @property
+    def last_elastic_field(self) -> Optional[torch.Tensor]:
+        """The ``(B, 2, Y, X)`` float32 device tensor of the last call's smoothed, unscaled field (``None`` before the first call that deforms)."""
+        return self._efield
+
+    @property
     def last_records(self) -> Optional[torch.Tensor]:
         """The ``(B, 32)`` int32 device tensor of the last call's records (the augmenter's own buffer, overwritten by the next call)."""
         return self._records
 
     # ---- the call -------------------------------------------------------------------------------------------------------------
     def __call__(self, x: torch.Tensor, t: torch.Tensor, out=None, *, records: Optional[torch.Tensor] = None,
-                 warp_records: Optional[torch.Tensor] = None):
+                 warp_records: Optional[torch.Tensor] = None, elastic_records: Optional[torch.Tensor] = None,
+                 elastic_field: Optional[torch.Tensor] = None):
         for name, v in (("x", x), ("t", t)):
             if not torch.is_tensor(v) or not v.is_cuda:
                 raise ValueError(f"{name} must be a CUDA/HIP tensor: biapy_amd.augment runs on the device only, there is no CPU path")
@@ -386,7 +495,32 @@ class DeviceAugmenter:
             if not bool((torch.isfinite(m) & (m.abs() <= WARP_M_MAX)).all()):
                 raise ValueError(f"warp_records words 1-6 (the matrix) must be finite with |m| <= 2^20, got {m.cpu().tolist()}")
 
+        elastic = self.elastic is not None
+        if (elastic_records is not None or elastic_field is not None) and not elastic:
+            raise ValueError("elastic_records= and elastic_field= need an augmenter built with elastic=: mode and cval are its")
+        if elastic:                                                    # checked on the host, before anything is launched or allocated
+            if 2 * B * Y * X >= ELASTIC_FIELD_MAX:
+                raise ValueError(f"the elastic field of this batch has 2 * {B} * {Y} * {X} = {2 * B * Y * X} elements; 2^31 or more are not supported")
+            if elastic_records is not None and (not torch.is_tensor(elastic_records) or elastic_records.device != x.device
+                                                or elastic_records.dtype != torch.int32 or tuple(elastic_records.shape) != (B, ELASTIC_REC_WORDS)
+                                                or not elastic_records.is_contiguous()):
+                raise ValueError(f"elastic_records must be a contiguous ({B}, {ELASTIC_REC_WORDS}) int32 tensor on the device of x")
+            if elastic_field is not None and (not torch.is_tensor(elastic_field) or elastic_field.device != x.device
+                                              or elastic_field.dtype != torch.float32 or tuple(elastic_field.shape) != (B, 2, Y, X)
+                                              or not elastic_field.is_contiguous()):
+                raise ValueError(f"elastic_field must be a contiguous ({B}, 2, {Y}, {X}) float32 tensor on the device of x")
+
         self._ensure(x.device, B)
+        if elastic:
+            if self._erec is None or self._erec.shape[0] != B or self._erec.device != x.device:
+                self._erec = torch.zeros((B, ELASTIC_REC_WORDS), dtype=torch.int32, device=x.device)
+            if self._efield is None or tuple(self._efield.shape) != (B, 2, Y, X) or self._efield.device != x.device:
+                self._efield = torch.empty((B, 2, Y, X), dtype=torch.float32, device=x.device)
+                self._ews = torch.empty((2, B, 2, Y, X), dtype=torch.float32, device=x.device)
+            for name, like in (("_ex", xm), ("_et", tm)):
+                buf = getattr(self, name)
+                if buf is None or buf.shape != like.shape or buf.dtype != like.dtype or buf.device != like.device:
+                    setattr(self, name, torch.empty(like.shape, dtype=like.dtype, device=like.device))
         if warp:
             if self._warp is None or self._warp.shape[0] != B or self._warp.device != x.device:
                 self._warp = torch.zeros((B, WARP_REC_WORDS), dtype=torch.int32, device=x.device)
@@ -410,6 +544,11 @@ class DeviceAugmenter:
 
             wcfg = self._warp_cfg_struct()
             L.check(lib.bpx_warp_draw(ctypes.addressof(wcfg), B, Y, X, rec.data_ptr(), self._warp.data_ptr(), s))
+        if elastic_records is not None:
+            self._erec.copy_(elastic_records)
+        elif elastic:
+            ec = self.elastic_config()
+            L.check(lib.bpx_elastic_draw(ec["seed"], ec["thr"], ec["alpha"][0], ec["alpha"][1], B, rec.data_ptr(), self._erec.data_ptr(), s))
         if records is not None or self.contrast is not None:           # m is only ever used by the contrast step
             n = Z * Y * X * C
             need = B * int(lib.bpx_aug_mean_blocks(n))
@@ -420,6 +559,17 @@ class DeviceAugmenter:
             L.check(lib.bpx_warp_apply(xm.data_ptr(), tm.data_ptr(), L.dt_of(t), B, Z, Y, X, C, Ct, self._warp.data_ptr(), AFFINE_MODES[self.affine_mode],
                                        self.affine_cval, self._wx.data_ptr(), self._wt.data_ptr(), s))
             xm, tm = self._wx, self._wt
+        if elastic:                                                    # step 0b into its own scratch pair
+            if elastic_field is not None:
+                self._efield.copy_(elastic_field)
+            else:
+                r = (len(self._ew) - 1) // 2
+                L.check(lib.bpx_elastic_noise(self.seed, B, Y, X, self._erec.data_ptr(), self._ews[0].data_ptr(), s))
+                L.check(lib.bpx_sepfilter(self._ews[0].data_ptr(), 2 * B, Y, X, None, -1, self._ew.ctypes.data, r, self._ew.ctypes.data, r, 0, 0.0,
+                                          self._efield.data_ptr(), self._ews[1].data_ptr(), self._efield.numel() * 4, s))
+            L.check(lib.bpx_elastic_apply(xm.data_ptr(), tm.data_ptr(), L.dt_of(t), B, Z, Y, X, C, Ct, self._erec.data_ptr(), self._efield.data_ptr(),
+                                          AFFINE_MODES[self.elastic["mode"]], self.elastic["cval"], self._ex.data_ptr(), self._et.data_ptr(), s))
+            xm, tm = self._ex, self._et
         cut = self.cutout or _CUTOUT_DEFAULTS
         L.check(lib.bpx_aug_apply(xm.data_ptr(), tm.data_ptr(), L.dt_of(t), B, Z, Y, X, C, Ct, rec.data_ptr(), self.seed, float(cut["cval"]),
                                   int(bool(cut["apply_to_mask"])), xo.data_ptr(), to.data_ptr(), s))

@@ -1,6 +1,7 @@
 // Training-time augmentation on the device (biapy_amd/augment.py states the semantics, include/biapy_amd.h the record layout): flips, rot90 over
 // (Y, X), contrast, brightness, Gaussian noise and cutout of a float32 (B,Z,Y,X,C) batch and its float32 / uint8 target in ONE gather pass.
-// The affine warp (rotation, zoom, shear, shift: step 0, a pass of its own in front of that one) is the last section of the file.
+// The affine warp (rotation, zoom, shear, shift: step 0, a pass of its own in front of that one) is the last section of the file; the elastic
+// deformation (step 0b) is elastic.hip, which shares augment_core.h with the warp.
 //
 // Random numbers: Philox4x32-10 (philox.h), key = the augmenter's 64-bit seed, counter words = (sample, stream, counter low, counter high) with the
 // augmenter's own device counter, one value per call.  Streams of the draw kernel, r = the four output words:
@@ -17,15 +18,12 @@
 // consecutive elements 4q .. 4q+3 as two Box-Muller pairs (noise4).
 #include "bpx_common.h"
 #include "philox.h"
+#include "augment_core.h"   // aug_uniform, warp_clamp, warp_tap, warp_lerp: shared with elastic.hip
 
 namespace {
 
 constexpr int REC = BPX_AUG_REC_WORDS;
 
-__device__ __forceinline__ float aug_uniform(uint32_t r, float lo, float hi) {
-  const float u = (float)(r >> 8) * 5.9604644775390625e-8f;   // 2^-24, exact
-  return fminf(__fadd_rn(lo, __fmul_rn(u, __fsub_rn(hi, lo))), hi);
-}
 __device__ __forceinline__ int aug_extent(uint32_t r, float lo, float hi, int dim) {
   const int e = (int)floorf(__fmul_rn(aug_uniform(r, lo, hi), (float)dim));
   return min(max(e, 1), dim);
@@ -186,9 +184,6 @@ template <> struct Vec<uint8_t, 4> {
     *reinterpret_cast<uint32_t*>(p) = (w[0] & 255u) | ((w[1] & 255u) << 8) | ((w[2] & 255u) << 16) | (w[3] << 24);
   }
 };
-
-// i / n for 0 <= i < 2^15 and 1 <= n <= 2^10 by one multiplication (exact: (i + 0.5) / n is at least 0.5 / n away from every integer)
-__device__ __forceinline__ int small_div(int i, float rcp_n) { return (int)(((float)i + 0.5f) * rcp_n); }
 
 // rows of the source rectangle -> LDS (row r at r * pitch): the workgroup's threads walk the rectangle's V-element items row after row, so a
 // wave covers several short rows at once and every lane is busy
@@ -412,28 +407,15 @@ __global__ void __launch_bounds__(256) warp_draw_kernel(const bpx_warp_cfg cfg, 
 constexpr int WT = 32;
 struct WarpGeom { int Z, Y, X, tiles_x, tiles_y; };
 
-// the source index of tap i on an axis of n voxels (p = max(2n - 2, 1), the reflect period); `in`: whether a constant-mode tap reads the plane
-template <int MODE>
-__device__ __forceinline__ int warp_tap(int i, int n, int p, bool& in) {
-  if constexpr (MODE == BPX_WARP_REFLECT) {
-    int r = i % p;
-    r += r < 0 ? p : 0;
-    in = true;
-    return r < n ? r : p - r;
-  } else {
-    in = MODE == BPX_WARP_EDGE || (unsigned)i < (unsigned)n;
-    return min(max(i, 0), n - 1);
-  }
-}
-
+// warp_tap<MODE>, the border rule of an integer tap index, warp_clamp and warp_lerp: augment_core.h
 struct WarpMap {
   float m00, m01, m02, m10, m11, m12, cy, cx;
   __device__ __forceinline__ void src(int y, int x, float& fy, float& fx) const {
     const float dy = __fsub_rn((float)y, cy), dx = __fsub_rn((float)x, cx);
     fy = __fadd_rn(__fadd_rn(__fmul_rn(m00, dy), __fmul_rn(m01, dx)), m02);
     fx = __fadd_rn(__fadd_rn(__fmul_rn(m10, dy), __fmul_rn(m11, dx)), m12);
-    fy = fminf(fmaxf(fy, -1073741824.f), 1073741824.f);          // a NaN becomes the lower bound: every index below is finite
-    fx = fminf(fmaxf(fx, -1073741824.f), 1073741824.f);
+    fy = warp_clamp(fy);
+    fx = warp_clamp(fx);
   }
 };
 
@@ -488,10 +470,7 @@ __global__ void __launch_bounds__(256) warp_apply_kernel(const float* __restrict
           v00 = iy0 && ix0 ? v00 : cval; v01 = iy0 && ix1 ? v01 : cval;
           v10 = iy1 && ix0 ? v10 : cval; v11 = iy1 && ix1 ? v11 : cval;
         }
-        const float ux = __fsub_rn(1.f, wx), uy = __fsub_rn(1.f, wy);
-        const float top = __fadd_rn(__fmul_rn(v00, ux), __fmul_rn(v01, wx));
-        const float bot = __fadd_rn(__fmul_rn(v10, ux), __fmul_rn(v11, wx));
-        out = __fadd_rn(__fmul_rn(top, uy), __fmul_rn(bot, wy));
+        out = warp_lerp(v00, v01, v10, v11, wx, wy);
       }
       xo[plane * C + dst] = out;
     }

@@ -759,6 +759,46 @@ int bpx_warp_draw(const bpx_warp_cfg* cfg, int B, int Y, int X, const uint32_t* 
 int bpx_warp_apply(const float* x_d, const void* t_d, int t_dtype, int B, int Z, int Y, int X, int C, int Ct, const uint32_t* warp_d, int mode,
                    float cval, float* x_out_d, void* t_out_d, bpx_stream_t stream);
 
+/* ---- elastic deformation in the (Y, X) plane (step 0b of biapy_amd/augment.py, after the affine warp; csrc/elastic.hip, csrc/augment_core.h) ----
+ * One displacement field per sample, identical for every z and channel; the image is interpolated bilinearly, the target takes the nearest
+ * voxel.  A sample's draw is an ELASTIC RECORD of 8 four-byte words:
+ *   word 0       flags: bit 0 fired; 0 = the sample is copied bit for bit
+ *   word 1       alpha (float), the scale of the displacement in voxels; 0 when the sample did not fire
+ *   words 2-3    the counter value the call drew with, low and high
+ *   words 4-7    0
+ * THE FIELD of a call is float32 (B, 2, Y, X), plane 0 dy and plane 1 dx, fewer than 2^31 elements.
+ *   noise      field[b] element e (the linear (plane, y, x) index within the sample) = u * 2 - 1, u = (r >> 8) * 2^-24, r = word e % 4 of
+ *              Philox4x32-10(key = (seed low ^ 0x454C4153, seed high), counter = (q low, q high ^ (b << 8), c low, c high)), q = e / 4, c the
+ *              call's counter value: a function of (seed, c, b, e) only, the tail of a field of 4 q + 1..3 elements included
+ *   smoothing  bpx_sepfilter on the field seen as a (2 B, Y, X) volume: wz = NULL, the Gaussian weights along y and x, mode "reflect"
+ *   gather     output voxel (y, x) reads the source at fy = y + alpha s[0][y][x], fx = x + alpha s[1][y][x] of the smoothed field s, each one
+ *              float32 multiply and one add, clamped to +-2^30 (a NaN becomes the lower bound); from there bpx_warp_apply's rules: the four
+ *              bilinear taps and their association for the image, the voxel (floor(fy + 0.5), floor(fx + 0.5)) for the target, the border
+ *              mode per integer tap index (BPX_WARP_CONSTANT / _REFLECT / _EDGE), cval for the image and 0 for the target outside. */
+#define BPX_ELASTIC_REC_WORDS 8
+#define BPX_ELASTIC_F_FIRED 0x1u
+#define BPX_ELASTIC_W_FLAGS 0
+#define BPX_ELASTIC_W_ALPHA 1
+#define BPX_ELASTIC_W_CTR 2
+#define BPX_ELASTIC_STREAM 24          /* the draw's Philox stream (counter word 1) */
+#define BPX_ELASTIC_KEY_XOR 0x454C4153u /* the noise's key: seed low ^ this */
+#define BPX_ELASTIC_ALPHA_MAX 1024.0f
+/*   bpx_elastic_draw  : fills elastic_d[B][8] from Philox4x32-10(key = seed, counter = (sample, 24, c low, c high)), c = words 5-6 of the
+ *                       sample's augmentation record records_d[b] (what bpx_aug_draw drew with: no second ticket): r0 fires ((uint64) r0 <
+ *                       thr), r1 is the uniform of alpha, min(lo + u (hi - lo), hi), 0 <= lo <= hi <= 1024.  One launch, nothing read back.
+ *   bpx_elastic_noise : fills field_d[B][2][Y][X] as stated above, c = words 2-3 of elastic_d[b].  One launch: one Philox call per four
+ *                       elements, 16-byte stores where an address allows them.
+ *   bpx_elastic_apply : out = the deformed pair, ONE out-of-place pass over image (1..16 channels) and target (1..8, BPX_F32 or BPX_U8) through
+ *                       the smoothed field_d.  Whatever the field and alpha hold, the clamp and the border rule keep every load inside the
+ *                       sample's plane.  No atomics, no workspace, nothing read back; capturable.
+ * Argument checks run on the host before anything is launched and set bpx_last_error: null pointers, extents, the 2^31-element field,
+ * channel counts, the target dtype, the mode, cval, out overlapping an input. */
+int bpx_elastic_draw(uint64_t seed, uint64_t thr, float alpha_lo, float alpha_hi, int B, const uint32_t* records_d, uint32_t* elastic_d,
+                     bpx_stream_t stream);
+int bpx_elastic_noise(uint64_t seed, int B, int Y, int X, const uint32_t* elastic_d, float* field_d, bpx_stream_t stream);
+int bpx_elastic_apply(const float* x_d, const void* t_d, int t_dtype, int B, int Z, int Y, int X, int C, int Ct, const uint32_t* elastic_d,
+                      const float* field_d, int mode, float cval, float* x_out_d, void* t_out_d, bpx_stream_t stream);
+
 /* ---- random training patches from device-resident volumes (biapy_amd/sampler.py states the semantics; csrc/sampler.hip) ---------
  * V volumes stay on the device: image (Z,Y,X,C), 1 <= C <= 16, float32 / uint8 / uint16; target (Z,Y,X,Ct), 1 <= Ct <= 8, uint8 / float32;
  * 2-D data is Z = 1.  A call draws B patch origins and copies the B windows of Pz x Py x Px voxels into a (B,Pz,Py,Px,C) float32 batch
