@@ -86,6 +86,9 @@ _SIGS = {
     "bpx_debug_set_overlap_per_voxel": ([_i], _i),
     "bpx_region_props": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "bpx_debug_set_regionprops_local": ([_i], _i),
+    "bpx_region_moments": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "bpx_region_faces": ([_vp, _i, _i, _i, _i, _vp, _vp], _i),
+    "bpx_region_perimeter2d": ([_vp, _i, _i, _i, _vp, _vp], _i),
     "bpx_morph": ([_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "bpx_peaks_workspace": ([_i, _i, _i], _i64),
     "bpx_peak_local_max": ([_vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp], _i),

@@ -25,6 +25,9 @@ percentiles / histogram on the host.
   label (``csrc/regionprops.hip``; scikit-image's ``regionprops``, SciPy's ``find_objects`` / ``center_of_mass``, the integers bit for bit), and
   the filter that keeps the labels a torch expression over those tensors selects - the detection workflow's centroids and the instance
   workflow's property filter without a device-to-host copy of the label volume;
+* ``shape_props`` and ``elongation`` / ``axis_lengths`` / ``surface_area`` / ``sphericity`` / ``perimeter`` / ``circularity`` finish that
+  filter (``csrc/shapeprops.hip``): exact second-order coordinate sums, the covariance from their exact 128-bit numerator, voxel faces per axis
+  and the weight classes of scikit-image's 2-D perimeter - integer sums, bit for bit a NumPy twin - and the measures as torch expressions;
 * ``binary_erosion`` / ``binary_dilation`` / ``binary_opening`` / ``binary_closing``, ``erosion`` / ``dilation``, ``find_boundaries``,
   ``binary_fill_holes`` and ``clear_border`` are the steps between those calls (``csrc/morph.hip``: one 3 x 3 x 3 stencil pass over ``uint8``,
   ``int32`` or ``float32``; the structuring element is ``generate_binary_structure(ndim, connectivity)``): ``scipy.ndimage``'s ``binary_*``,
@@ -690,10 +693,10 @@ def matching(y_true: torch.Tensor, y_pred: torch.Tensor, thresh=0.5, criterion: 
 # ---- region properties of a label volume and the property filter on top of them (csrc/regionprops.hip) -------------------------------------------
 # What every consumer of label() / watershed() does next: the detection workflow takes the centroids of its labelled blobs, the instance workflow
 # measures every instance and drops those that fail a property test, and a crop of an instance needs its box (skimage.measure.regionprops,
-# scipy.ndimage.find_objects / center_of_mass on the host there).  Offered: area, bbox, the exact coordinate sums and the centroid.  NOT offered:
-# intensity properties (a float sum by atomics depends on the order and would break "the same bits every run"; min / max need a segmented scan
-# that the closed-form runs avoid); second moments, inertia axes, eccentricity; perimeter, surface, sphericity (the reference meshes the object);
-# coords, image, convex_*; volumes of 2^31 voxels or more; multi-GPU slabs.
+# scipy.ndimage.find_objects / center_of_mass on the host there).  Offered: area, bbox, the exact coordinate sums and the centroid; second
+# moments, voxel faces, the 2-D perimeter and the measures derived from them are shape_props, below.  NOT offered: intensity properties (a
+# float sum by atomics depends on the order and would break "the same bits every run"; min / max need a segmented scan that the closed-form
+# runs avoid); a meshed surface; coords, image, convex_*; volumes of 2^31 voxels or more; multi-GPU slabs.
 
 class RegionProps(NamedTuple):
     """``region_props``' result, every field a device tensor with one row per label ``0..N``; row 0 is the background's and holds zeros (NaN in
@@ -716,8 +719,8 @@ def region_props(labels: torch.Tensor, num=None) -> RegionProps:
     does.  Views are taken via ``.contiguous()``.  Three launches fixed by the shape and ``N``, nothing else read back: capturable.
 
     Refused before anything is launched: a negative ``num`` and a rank other than 2 / 3 (``ValueError``); a CPU tensor (``RuntimeError``); a dtype
-    other than ``int32``, an empty volume and 2^31 voxels or more (``NotImplementedError``).  Not offered: intensity properties, second moments
-    (inertia axes, eccentricity), perimeter / surface / sphericity, ``coords`` / ``image`` / ``convex_*``, multi-GPU slabs (see the comment above)."""
+    other than ``int32``, an empty volume and 2^31 voxels or more (``NotImplementedError``).  Second moments, faces and the 2-D perimeter:
+    ``shape_props``.  Not offered: intensity properties, ``coords`` / ``image`` / ``convex_*``, multi-GPU slabs (see the comment above)."""
     n_max = None if num is None else int(num)
     if n_max is not None and n_max < 0:
         raise ValueError(f"num must not be negative (got {n_max})")
@@ -761,6 +764,188 @@ def select_objects(labels: torch.Tensor, keep: torch.Tensor, relabel: bool = Fal
     left = torch.empty((), dtype=torch.int32, device=lab.device)
     L.check(lib.bpx_label_filter(out.data_ptr(), out.numel(), n_max, sizes.data_ptr(), 1, 1 if relabel else 0, left.data_ptr(), L.stream_ptr()))
     return (out, left) if return_num else out
+
+
+# ---- shape properties: second moments, voxel faces, the 2-D perimeter, and the measures derived from them (csrc/shapeprops.hip) --------------------
+# The rest of the reference's property filter (circularity, elongation, perimeter, sphericity beside npixels / area / diameter).  All of it is
+# integer sums reached by commutative atomics, so "the same bits every run" holds; the derived measures are plain torch expressions over the
+# fields - no solver library, nothing read back - and each of them, or any other expression, feeds ``select_objects``.
+
+class ShapeProps(NamedTuple):
+    """``shape_props``' result, every field a device tensor with one row per label ``0..N``; row 0 and the row of a label that no voxel carries
+    hold zeros (NaN in ``centroid``).  The first four fields are ``RegionProps``'."""
+    area: torch.Tensor                          # int32 (N + 1,)
+    bbox: torch.Tensor                          # int32 (N + 1, 2 * ndim)
+    coord_sum: torch.Tensor                     # int64 (N + 1, ndim)
+    centroid: torch.Tensor                      # float64 (N + 1, ndim)
+    moments: torch.Tensor                       # int64 (N + 1, 6): the sums of zz, yy, xx, zy, zx, yx, exact; (N + 1, 3) in 2-D: yy, xx, yx
+    covariance: torch.Tensor                    # float64 (N + 1, ndim, ndim): moments / area - centroid centroid^T, from the exact numerator
+    faces: torch.Tensor                         # int64 (N + 1, ndim): voxel faces towards another label or the outside, per axis
+    perimeter_classes: Optional[torch.Tensor]   # int32 (N + 1, 3) in 2-D: pixels of weight 1, sqrt 2, (1 + sqrt 2) / 2; None in 3-D
+
+
+_COV_3D = ((0, 3, 4), (3, 1, 5), (4, 5, 2))     # covariance[i][j] = column of bpx_region_moments' cov_d
+_COV_2D = ((1, 5), (5, 2))
+
+
+def _columns(t: torch.Tensor, which) -> torch.Tensor:
+    """``t[:, which]`` without an index tensor, which would be copied from the host and cannot be captured."""
+    return torch.stack([t[:, c] for c in which], 1)
+
+
+def moments_fit(shape) -> bool:
+    """Whether ``shape_props`` accepts a volume of this shape: ``n * (Emax - 1)**2 < 2**63`` (``n`` the voxel count, ``Emax`` the largest
+    extent), under which every second-order coordinate sum fits ``int64``.  Every volume below 2^31 voxels with no extent above 65 536 passes, a single row up to 2^21 voxels (2^15 rows of 2^16 do, of 2^17 do not)."""
+    n, emax = math.prod(shape), max(shape)
+    return n * (emax - 1) ** 2 < 2 ** 63
+
+
+def shape_props(labels: torch.Tensor, num=None) -> ShapeProps:
+    """``region_props`` plus the exact second-order coordinate sums, the covariance matrix, the voxel faces per axis and (2-D) the weight classes
+    of scikit-image's perimeter estimator of every label ``1..N`` of a 2-D ``(Y, X)`` or 3-D ``(Z, Y, X)`` ``int32`` label tensor, as a
+    ``ShapeProps`` named tuple of DEVICE tensors.  Every integer field is bit for bit the same on every run; ``covariance`` follows from the
+    integers by a fixed sequence of float64 operations (the exact 128-bit numerator ``A * S_ab - S_a * S_b``, converted, divided by ``A``
+    twice).  ``faces[l][k]`` counts the (voxel of ``l``, direction along axis ``k``) pairs whose neighbour carries another label or lies outside.
+
+    ``num`` as for ``region_props``.  Launches fixed by the shape and ``N`` (``bpx_region_props``, ``bpx_region_moments``, ``bpx_region_faces``
+    and, in 2-D, ``bpx_region_perimeter2d``), nothing else read back: capturable.  Refused before anything is launched, in this order: what
+    ``region_props`` refuses up to the voxel count; a shape with ``n * (Emax - 1)**2 >= 2**63`` (``NotImplementedError``, ``moments_fit``);
+    then its dtype, device and empty-volume refusals.  Not offered: intensity properties, ``coords`` / ``image`` / ``convex_*``, multi-GPU slabs.
+
+    The measures on top - ``principal_moments``, ``axis_lengths``, ``elongation``, ``surface_area``, ``perimeter``, ``circularity``,
+    ``sphericity`` - are torch expressions of one row per label; ``select_objects(labels, elongation(p) < 3)`` filters by them."""
+    n_max = None if num is None else int(num)
+    if n_max is not None and n_max < 0:
+        raise ValueError(f"num must not be negative (got {n_max})")
+    Z, Y, X = _label_volume(labels, "shape_props")
+    if not moments_fit((Z, Y, X)):
+        raise NotImplementedError(f"biapy_amd.prepost.shape_props: a {Z} x {Y} x {X} volume has n * (Emax - 1)^2 >= 2^63 - its second-order "
+                                  "coordinate sums may not fit int64")
+    lab = _labels(labels, "shape_props").contiguous()
+    if n_max is None:
+        n_max = max(int(lab.max()), 0)
+    dev, rows, two_d = lab.device, n_max + 1, labels.dim() == 2
+    area = torch.empty(rows, dtype=torch.int32, device=dev)
+    sums = torch.empty((rows, 3), dtype=torch.int64, device=dev)
+    bbox = torch.empty((rows, 6), dtype=torch.int32, device=dev)
+    mom = torch.empty((rows, 6), dtype=torch.int64, device=dev)
+    cov = torch.empty((rows, 6), dtype=torch.float64, device=dev)
+    faces = torch.empty((rows, 3), dtype=torch.int64, device=dev)
+    s = L.stream_ptr()
+    L.check(lib.bpx_region_props(lab.data_ptr(), Z, Y, X, n_max, area.data_ptr(), sums.data_ptr(), bbox.data_ptr(), s))
+    L.check(lib.bpx_region_moments(lab.data_ptr(), Z, Y, X, n_max, area.data_ptr(), sums.data_ptr(), mom.data_ptr(), cov.data_ptr(), s))
+    L.check(lib.bpx_region_faces(lab.data_ptr(), Z, Y, X, n_max, faces.data_ptr(), s))
+    classes = None
+    if two_d:
+        classes = torch.empty((rows, 3), dtype=torch.int32, device=dev)
+        L.check(lib.bpx_region_perimeter2d(lab.data_ptr(), Y, X, n_max, classes.data_ptr(), s))
+        sums, bbox, mom, faces = sums[:, 1:], _columns(bbox, (1, 2, 4, 5)), _columns(mom, (1, 2, 5)), faces[:, 1:]
+    cov = _columns(cov, [c for row in (_COV_2D if two_d else _COV_3D) for c in row]).reshape(rows, labels.dim(), labels.dim())
+    return ShapeProps(area, bbox, sums, sums.double() / area.double()[:, None], mom, cov, faces, classes)
+
+
+def _shape_props(p, what: str) -> int:
+    if not isinstance(p, ShapeProps):
+        raise TypeError(f"biapy_amd.prepost.{what} takes the ShapeProps of shape_props (got {type(p).__name__})")
+    return p.faces.shape[1]
+
+
+def _sampling(sampling, ndim: int, what: str):
+    if sampling is None:
+        return (1.0,) * ndim
+    s = tuple(float(v) for v in sampling)
+    if len(s) != ndim or not all(math.isfinite(v) and v > 0 for v in s):
+        raise ValueError(f"biapy_amd.prepost.{what}: sampling must be {ndim} finite positive numbers (got {sampling!r})")
+    return s
+
+
+def _eig2(a: torch.Tensor, d: torch.Tensor, b: torch.Tensor):
+    """The eigenvalues of [[a, b], [b, d]], the larger first."""
+    mid, half = (a + d) / 2, torch.sqrt(((a - d) / 2) ** 2 + b * b)
+    return mid + half, mid - half
+
+
+def principal_moments(p: ShapeProps) -> torch.Tensor:
+    """The eigenvalues of ``p.covariance`` in descending order, ``float64 (N + 1, ndim)``, never negative - scikit-image's ``inertia_tensor_eigvals``.
+    Closed forms, elementwise torch: no solver, nothing read back.  2-D: ``(a + d) / 2 +- sqrt(((a - d) / 2)^2 + b^2)``, a few units of
+    ``2^-52 * trace``.  3-D: the trigonometric form ``q + 2 s cos(phi + 2 pi k / 3)`` with ``phi = acos(det(C - q I) / (2 s^3)) / 3``; where two
+    eigenvalues nearly coincide while the third lies far off (a long thin object) the arc cosine is taken near 1 and the two close ones are only
+    good to about ``1e-8 * trace`` (measured: tests/shapeprops_ref.py, profiles/shapeprops_values.txt).  An object that is flat along an axis (a
+    rod, a plane one voxel thick) has an exactly zero variance there - the covariance's numerator is an exact integer - and is reduced to the 2-D
+    form, so its zero eigenvalue is exact."""
+    nd = _shape_props(p, "principal_moments")
+    c = p.covariance
+    if nd == 2:
+        return torch.stack(_eig2(c[:, 0, 0], c[:, 1, 1], c[:, 0, 1]), 1).clamp_min(0)
+    a, d, f = c[:, 0, 0], c[:, 1, 1], c[:, 2, 2]
+    b, e, g = c[:, 0, 1], c[:, 0, 2], c[:, 1, 2]
+    q = (a + d + f) / 3
+    p1 = b * b + e * e + g * g
+    a0, d0, f0 = a - q, d - q, f - q
+    s = torch.sqrt((a0 * a0 + d0 * d0 + f0 * f0 + 2 * p1) / 6)
+    det = a0 * (d0 * f0 - g * g) - b * (b * f0 - g * e) + e * (b * g - d0 * e)
+    r = torch.where(s > 0, det / (2 * s * s * s), torch.zeros_like(s)).clamp(-1, 1)
+    phi = torch.acos(r) / 3
+    hi = q + 2 * s * torch.cos(phi)
+    lo = q + 2 * s * torch.cos(phi + 2 * math.pi / 3)
+    lam = torch.stack((hi, 3 * q - hi - lo, lo), 1)
+    zero = torch.zeros_like(q)
+    for flat, (u, v, w) in ((a == 0, (d, f, g)), (d == 0, (a, f, e)), (f == 0, (a, d, b))):        # no variance along z, y, x: the other two axes' 2 x 2
+        lam = torch.where(flat[:, None], torch.stack(_eig2(u, v, w) + (zero,), 1), lam)
+    return torch.sort(lam.clamp_min(0), dim=1, descending=True).values          # equal eigenvalues may come out an ulp out of order
+
+
+def axis_lengths(p: ShapeProps) -> torch.Tensor:
+    """The lengths of the axes of the ellipse / ellipsoid with the object's second moments, longest first: ``4 sqrt(lambda)`` in 2-D
+    (scikit-image's ``axis_major_length`` / ``axis_minor_length``), ``sqrt(20 lambda)`` in 3-D."""
+    lam = principal_moments(p)
+    return 4 * torch.sqrt(lam) if lam.shape[1] == 2 else torch.sqrt(20 * lam)
+
+
+def elongation(p: ShapeProps) -> torch.Tensor:
+    """``sqrt(lambda_max / lambda_min)`` of the principal moments: 1 for a disk, ball, square or cube, ``inf`` for a flat object (a rod, a plane
+    one voxel thick; in 3-D an object flat along a direction that is no axis, a diagonal line, gets a large finite value instead), NaN for a
+    single voxel and for an absent label."""
+    lam = principal_moments(p)
+    return torch.sqrt(lam[:, 0] / lam[:, -1])
+
+
+def surface_area(p: ShapeProps, sampling=None) -> torch.Tensor:
+    """``sum_k faces_k * prod_{j != k} sampling_j``: the area of the object's voxel faces (in 2-D the length of its pixel edges), ``float64
+    (N + 1,)``.  The face count of a digitised ball tends to 1.5 x its true surface and that of a disk to 4 / pi x its circumference (ratios
+    1.4995 at r = 40 and 1.281 at r = 80): a staircase does not shorten as the grid is refined."""
+    nd = _shape_props(p, "surface_area")
+    s = _sampling(sampling, nd, "surface_area")
+    w = [math.prod(s[j] for j in range(nd) if j != k) for k in range(nd)]          # Python floats: no copy to the device, capturable
+    return sum(p.faces[:, k].double() * w[k] for k in range(nd))
+
+
+_PERIMETER_WEIGHTS = (1.0, math.sqrt(2.0), (1.0 + math.sqrt(2.0)) / 2.0)
+
+
+def perimeter(p: ShapeProps) -> torch.Tensor:
+    """scikit-image's ``perimeter(label == l, neighborhood=4)`` of every label of a 2-D image, ``float64 (N + 1,)``: the border pixels in three
+    classes by the border pixels around them, weighted 1, sqrt 2 and (1 + sqrt 2) / 2.  It follows scikit-image's estimator, not the pixel-edge
+    length (``surface_area``).  3-D raises ``ValueError``."""
+    if _shape_props(p, "perimeter") != 2:
+        raise ValueError("biapy_amd.prepost.perimeter is defined for 2-D labels only; surface_area and sphericity serve in 3-D")
+    c = p.perimeter_classes.double()
+    return c[:, 0] * _PERIMETER_WEIGHTS[0] + c[:, 1] * _PERIMETER_WEIGHTS[1] + c[:, 2] * _PERIMETER_WEIGHTS[2]
+
+
+def circularity(p: ShapeProps) -> torch.Tensor:
+    """``4 pi area / perimeter^2`` with scikit-image's perimeter estimator (2-D only): near 1 for a disk, ``inf`` / NaN where the perimeter is 0."""
+    _shape_props(p, "circularity")
+    return 4 * math.pi * p.area.double() / perimeter(p) ** 2
+
+
+def sphericity(p: ShapeProps, sampling=None) -> torch.Tensor:
+    """``pi^(1/3) (6 V)^(2/3) / surface_area`` with ``V = area * prod(sampling)``.  Product-defined, NOT the reference's number from a meshed
+    surface: as the voxel-face count of a ball tends to 1.5 x its true surface, this tends to 2 / 3 for a ball (and is 0.806 for a cube)."""
+    if _shape_props(p, "sphericity") != 3:
+        raise ValueError("biapy_amd.prepost.sphericity is defined for 3-D labels only; circularity serves in 2-D")
+    v = p.area.double() * math.prod(_sampling(sampling, 3, "sphericity"))
+    return math.pi ** (1.0 / 3.0) * (6 * v) ** (2.0 / 3.0) / surface_area(p, sampling)
 
 
 # ---- morphology: erosion, dilation, boundaries, hole filling and border clearing (csrc/morph.hip) -------------------------------------------------

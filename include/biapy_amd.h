@@ -952,6 +952,30 @@ int bpx_debug_set_overlap_per_voxel(int on); /* timing hook of bpx_label_overlap
 int bpx_region_props(const int32_t* labels_d, int Z, int Y, int X, int n_max, int32_t* area_d, int64_t* sums_d, int32_t* bbox_d, bpx_stream_t stream);
 int bpx_debug_set_regionprops_local(int on); /* test / A-B hook of bpx_region_props' accumulate pass: 1 (default) = the runs of a block meet in a 256-slot table in LDS that is merged into the outputs once per block; 0 = every run straight to the outputs, faster on a volume without labels and far slower on any other; negative = back to the default; same bits (environment: BPX_REGIONPROPS_LOCAL) */
 
+/* ---- shape properties of a label volume (biapy_amd/prepost.py: shape_props and the derived measures; csrc/shapeprops.hip, csrc/shapeprops_core.h) ----
+ * labels (Z,Y,X) int32, contiguous, 4-byte aligned; 2-D is Z = 1; Z * Y * X < 2^31; 0 <= n_max < 2^31 - 1; a label <= 0 or > n_max is background 0
+ * (as for bpx_region_props).  Row 0 and the row of a label that no voxel carries are all zeros in every output.
+ *   bpx_region_moments: mom_d[l][6] = the sums of zz, yy, xx, zy, zx, yx over the voxels of l (int64, exact).  Refused when
+ *     n * (Emax - 1)^2 >= 2^63 (n = Z * Y * X, Emax the largest extent): below that every sum fits.  The accumulate pass of bpx_region_props with
+ *     another closed form per run: sum xx = L x0^2 + x0 L (L - 1) + (L - 1) L (2 L - 1) / 6, sum zx = z sum x, sum yx = y sum x, sum zz = L z^2,
+ *     sum yy = L y^2, sum zy = L z y.  With cov_d != NULL a finish pass forms cov_d[l][6] (float64, the same order) from area_d and sums_d, THE
+ *     OUTPUTS OF bpx_region_props for the same volume and n_max: the numerator A * S_ab - S_a * S_b exactly in 128 bits, converted to double
+ *     (high word * 2^64 + low word), divided by A twice; 0 where the area is 0.  cov_d == NULL: the sums only; area_d and sums_d are not read.
+ *     Launches: zero, accumulate, finish (with cov_d).
+ *   bpx_region_faces: faces_d[l][3] (int64) = per axis z, y, x the number of pairs (voxel of l, one of the two directions along the axis) whose
+ *     neighbour lies outside the volume or carries another label: the surface of l in voxel faces.  Z = 1 gives 2 * area on the z axis.
+ *     Launches: zero, count.
+ *   bpx_region_perimeter2d: classes_d[l][3] (int32) = the number of pixels of l in the three weight classes (1, sqrt 2, (1 + sqrt 2) / 2) of
+ *     scikit-image's perimeter(labels == l, neighborhood=4): a border pixel carries a label > 0 and has a 4-neighbour that differs (outside the
+ *     image differs); k4 / kd count its 4- / diagonal neighbours that are border pixels of the same label; code = 1 + 2 k4 + 10 kd is of class 0
+ *     for 5, 7, 15, 17, 25, 27, class 1 for 21, 33, class 2 for 13, 23, of none otherwise.  Launches: zero, classify.
+ * Integer atomics only (uint32 / uint64 add): the same bits every run; no workspace; nothing read back; capturable.
+ * Argument checks run on the host before anything is launched, those of bpx_region_props in its order first, and set bpx_last_error. */
+int bpx_region_moments(const int32_t* labels_d, int Z, int Y, int X, int n_max, const int32_t* area_d, const int64_t* sums_d, int64_t* mom_d,
+                       double* cov_d, bpx_stream_t stream);
+int bpx_region_faces(const int32_t* labels_d, int Z, int Y, int X, int n_max, int64_t* faces_d, bpx_stream_t stream);
+int bpx_region_perimeter2d(const int32_t* labels_d, int Y, int X, int n_max, int32_t* classes_d, bpx_stream_t stream);
+
 /* ---- morphology: erosion, dilation and the boundary map (biapy_amd/prepost.py: binary_erosion, binary_dilation, binary_opening, binary_closing,
  * erosion, dilation, find_boundaries; csrc/morph.hip, csrc/morph_core.h) ----
  * in (Z,Y,X) contiguous, dtype BPX_U8, BPX_I32 or BPX_F32 (the 4-byte types 4-byte aligned; uint8 at any address); ndim 3, or 2 with Z = 1;
