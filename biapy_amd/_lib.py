@@ -144,6 +144,8 @@ _SIGS = {
     "bpx_debug_set_bwd_fused": ([_i], _i),
     "bpx_debug_set_bwd_rs": ([_i], _i),
     "bpx_debug_set_conv_kg": ([_i], _i),
+    "bpx_debug_set_conv_wn": ([_i], _i),
+    "bpx_conv3d_wn_supported": ([_i] * 6, _i),
     "bpx_debug_set_tile_order": ([_i], _i),
     "bpx_debug_set_wgrad_cap": ([_i], _i),
     "bpx_debug_set_wgrad_k1": ([_i], _i),

@@ -26,6 +26,10 @@ extern "C" int bpx_debug_set_conv_stamps(void* p) { g_stamps = (long long*)p; re
 static int g_use_ws = 0;  // bf16 kernel selection, see bpx_debug_set_conv_ws below
 static int g_conv_kg = -1; // two K groups in the small-tile kernel: -1 = environment (BPX_CONV_KG, default on), 0 / 1 (bpx_debug_set_conv_kg)
 extern "C" int bpx_debug_set_conv_kg(int on) { g_conv_kg = on; return 0; }
+// waves across the output channels in the small-tile 16-bit kernel (conv3_kernel's WN): -1 = environment (BPX_CONV_WN, default 0), 0 = the launcher's
+// choice per instance class, 1 / 2 / 4 = that value wherever an instance exists (WN <= NS), else 1
+static int g_conv_wn = -1;
+extern "C" int bpx_debug_set_conv_wn(int wn) { g_conv_wn = wn; return 0; }
 static int64_t g_lean_min_vps = 32768;   // voxels per sample from which the lean kernel is used (test hook: bpx_debug_set_conv_ws 10 = 64^3 as in round 2, 11 = 32^3)
 
 namespace {
@@ -104,14 +108,21 @@ __host__ __device__ constexpr int wreg_next(int s, int np, int per) {
 // splitting K across WORKGROUPS costs a device-scope fence per workgroup (round 4: 2.5-5x slower).  Inside a workgroup it costs one LDS exchange:
 // group kg takes the chunks kg, kg + 2, ... through its own pair of halo buffers (the chunk barriers are shared), group 1 hands its accumulators
 // to group 0 through LDS at the end, group 0 runs the shortcut steps and the epilogue.  The chain is half as long and every SIMD holds two waves.
-template <typename T, int TZ, int TY, int TX, int NS, int EPI, int ACTK, typename TT = T, int KG = 1>
+// WN (the 4x4x8 16-bit instances): how many of a K group's four waves lie across the OUTPUT CHANNELS.  With WN = 1 the waves split the tile's voxels
+// only and every wave pulls all NS weight fragments of a step through the L1 - the same bytes four times per group.  Wave (wm, wn) of WM x WN
+// owns the m-subtiles [wm MT / WM, (wm + 1) MT / WM) - WN z-slices of the tile - and the n-subtiles [wn NS / WN, (wn + 1) NS / WN): as many
+// accumulators as before, WN-fold fewer weight bytes per wave, WN-fold more LDS fragment reads (the wide pipe).  Every accumulator sees the same
+// MFMAs in the same order, and the statistics keep one partial per z-slice (the WN = 1 wave), so y, g and the partial rows are the same bits.
+template <typename T, int TZ, int TY, int TX, int NS, int EPI, int ACTK, typename TT = T, int KG = 1, int WN = 1>
 __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p) {
   using Tr = ElemTraits<T>;
   constexpr int KPL = Tr::KPL, GPT = 16 / KPL, VB = 16 * (int)sizeof(T);
   constexpr int HZ = TZ + 2, HY = TY + 2, HX = TX + 2, HV = HZ * HY * HX;
   constexpr int QTOT = 27 * GPT, STEPS = (QTOT + 3) / 4, QPAD = STEPS * 4;
-  constexpr int MT = TZ * TY * TX / 16, MS = MT / 4;
+  constexpr int WM = 4 / WN, NW = NS / WN;                      // waves across the voxels; n-subtiles of one wave
+  constexpr int MT = TZ * TY * TX / 16, MS = MT / WM;           // m-subtiles of one wave
   static_assert(MT % 4 == 0 && MS >= 1, "tile must give every wave at least one m-subtile");
+  static_assert(WN == 1 || ((WN == 2 || WN == 4) && TX == 8 && sizeof(T) == 2 && NS % WN == 0), "channel-split waves: the small-tile 16-bit instances only");
   static_assert((HV * GPT + 255) / 256 <= STEPS, "one staged piece per MFMA step");
   static_assert(sizeof(T) != 2 || wreg_next(STEPS, (HV * GPT + 255) / 256, (STEPS + (STEPS - (HV * GPT + 255) / 256) - 1) / (STEPS - (HV * GPT + 255) / 256)) == STEPS, "weight re-load schedule must cover every fragment");
   constexpr int RED_BYTES = 4 * NS * 16 * 2 * 4;
@@ -119,18 +130,20 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
   static_assert(NS * 16 * 2 * 4 * 4 <= RED_BYTES, "reduction scratch");
   constexpr int NBUF = 2;
   static_assert(KG == 1 || (TX == 8 && sizeof(T) == 2), "two K groups: the small-tile 16-bit instances only");
-  constexpr int XCH_BYTES = KG == 2 ? MS * NS * 256 * 16 : 0;     // the accumulator hand-over [ms][ns][thread] f32x4 re-uses the halo buffers
+  constexpr int XCH_BYTES = KG == 2 ? MS * NW * 256 * 16 : 0;     // the accumulator hand-over [ms][ns][thread] f32x4 re-uses the halo buffers
   static_assert(XCH_BYTES <= KG * NBUF * BUFB, "accumulator exchange fits the halo buffers");
   __shared__ __attribute__((aligned(16))) unsigned char smem_all[KG * NBUF * BUFB + RED_BYTES];
 
   const int kg = KG == 2 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;      // K group of this wave
   unsigned char* const smem = smem_all + kg * NBUF * BUFB;                                     // this group's pair of halo buffers
   const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
+  const int wm = WN == 1 ? wave : wave / WN, wn = WN == 1 ? 0 : wave % WN;    // (WN == 1 is spelt out wherever it keeps the expression the one-mapping kernel had)
   const int j = lane & 15, g = lane >> 4;
   const int tile = blockIdx.x % p.tilesPerSample, n = blockIdx.x / p.tilesPerSample;
   const int txi = tile % p.tilesX, tyi = (tile / p.tilesX) % p.tilesY, tzi = tile / (p.tilesX * p.tilesY);
   const int z0 = tzi * TZ, y0 = tyi * TY, x0 = txi * TX;
-  const int co_base = blockIdx.y * 16 * NS;
+  const int co_wg = blockIdx.y * 16 * NS;            // the workgroup's first output channel
+  const int co_base = WN == 1 ? co_wg : co_wg + wn * (16 * NW);        // this wave's
   const int Cout = p.Cout;
 
   int stamp_i = 0;
@@ -139,21 +152,24 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
   if (p.stamps && tid == 0 && kg == 0 && blockIdx.y == 0)  // slot 15: where the workgroup ran (HW_ID | XCC_ID << 32)
     p.stamps[(size_t)blockIdx.x * 16 + 15] =
         (long long)(((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4));
-  f32x4_t acc[MS][NS];
+  f32x4_t acc[MS][NW];
 #pragma unroll
   for (int ms = 0; ms < MS; ++ms)
 #pragma unroll
-    for (int ns = 0; ns < NS; ++ns) acc[ms][ns] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int ns = 0; ns < NW; ++ns) acc[ms][ns] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   // A wave's MS m-subtiles are consecutive rows (TX = 16) or row pairs (TX = 8) of ONE z-slice of the tile, so the LDS
   // address of subtile ms is the address of subtile 0 plus a compile-time stride: every ds_read below is
-  // VGPR base + immediate.
-  static_assert(TZ == 4 && MS * 16 == TY * TX && (TX == 16 || TX == 8), "wave = z-slice mapping");
+  // VGPR base + immediate.  WN > 1: a wave spans WN consecutive z-slices, MPZ m-subtiles in each; the slice stride is a constant too.
+  static_assert(TZ == 4 && MS * 16 == WN * TY * TX && (TX == 16 || TX == 8), "wave = z-slice mapping");
+  constexpr int MPZ = MS / WN;                                   // m-subtiles per z-slice
   constexpr int HSTR = (TX >= 16 ? 1 : 16 / TX) * HX * VB;      // halo-buffer stride between m-subtiles
+  constexpr int ZSTR = HY * HX * VB;                             // and between z-slices
+#define BPX_MOFF(ms) (WN == 1 ? (ms) * HSTR : ((ms) / MPZ) * ZSTR + ((ms) % MPZ) * HSTR)
   constexpr int TSTR = 16 * VB;                                  // same for the un-haloed [voxel][16ch] block (shortcut)
   int hb0, tb0;
   {
-    int t = (wave * MS) * 16 + j;
+    int t = (wm * MS) * 16 + j;
     int tz = t / (TY * TX), ty = (t / TX) % TY, tx = t % TX;
     hb0 = ((tz * HY + ty) * HX + tx) * VB;
     tb0 = t * VB;
@@ -256,13 +272,13 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
   constexpr int NWR = WREG ? STEPS : 1;
   constexpr int WSTEPS = STEPS - NP;                                  // steps without a staging piece
   constexpr int PER = WREG ? (STEPS + WSTEPS - 1) / WSTEPS : 1;       // fragments re-loaded per such step
-  u32x4_t wreg[NWR][NS];
+  u32x4_t wreg[NWR][NW];
   if (WREG) {
     const T* wl0 = wp + ((size_t)kg * QPAD * Cout + (size_t)g * Cout + co_base + j) * KPL;
 #pragma unroll
     for (int s = 0; s < NWR; ++s)
 #pragma unroll
-      for (int ns = 0; ns < NS; ++ns) wreg[s][ns] = *reinterpret_cast<const u32x4_t*>(wl0 + ((size_t)s * 4 * Cout + ns * 16) * KPL);
+      for (int ns = 0; ns < NW; ++ns) wreg[s][ns] = *reinterpret_cast<const u32x4_t*>(wl0 + ((size_t)s * 4 * Cout + ns * 16) * KPL);
   }
   // Round 4 (cycle stamps of the <= 16^3 layers, one workgroup per CU = one wave per SIMD): a step was ONE exposed latency - 486 cycles per step for
   // the 8 MFMAs (128 cycles) of the NS = 4 instances, whose next step's weights were requested one step ahead (L2 latency ~500 cycles), and 264
@@ -275,13 +291,13 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
   constexpr bool SMALL = TX == 8;
   constexpr int WD = SMALL ? 3 : 1;
   constexpr int NAF = SMALL ? 2 : 1;
-  u32x4_t wq[WREG ? 1 : WD + 1][NS];
+  u32x4_t wq[WREG ? 1 : WD + 1][NW];
   if (!WREG) {
     const T* wl0 = wp + ((size_t)kg * QPAD * Cout + (size_t)g * Cout + co_base + j) * KPL;
 #pragma unroll
     for (int d = 0; d < WD; ++d)
 #pragma unroll
-      for (int ns = 0; ns < NS; ++ns) wq[d][ns] = *reinterpret_cast<const u32x4_t*>(wl0 + ((size_t)d * 4 * Cout + ns * 16) * KPL);
+      for (int ns = 0; ns < NW; ++ns) wq[d][ns] = *reinterpret_cast<const u32x4_t*>(wl0 + ((size_t)d * 4 * Cout + ns * 16) * KPL);
   }
   int cur = 0;
   for (int chunk = kg; chunk < nchunks; chunk += KG) {
@@ -295,14 +311,14 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
       const int cls = (GPT == 2) ? (s_ < 9 ? 0 : s_ < 12 ? 1 : s_ == 12 ? 2 : 3) : 0;
       const int imm = tap_off<HY, HX, VB>(tapA);
 #pragma unroll
-      for (int ms = 0; ms < MS; ++ms) f[ms] = *reinterpret_cast<const u32x4_t*>(smem + lbase[cls] + ms * HSTR + imm);
+      for (int ms = 0; ms < MS; ++ms) f[ms] = *reinterpret_cast<const u32x4_t*>(smem + lbase[cls] + BPX_MOFF(ms) + imm);
     };
     if (NAF == 2) read_frags(0, af[0]);
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
       if (!WREG && s + WD < STEPS) {
 #pragma unroll
-        for (int ns = 0; ns < NS; ++ns)
+        for (int ns = 0; ns < NW; ++ns)
           wq[WREG ? 0 : (s + WD) % (WD + 1)][ns] = *reinterpret_cast<const u32x4_t*>(wl + ((size_t)(s + WD) * 4 * Cout + ns * 16) * KPL);
       }
       // the NEXT step's LDS reads are issued before this step's MFMAs; sched_barrier keeps the compiler from re-serialising to save VGPRs
@@ -312,7 +328,7 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
 #pragma unroll
       for (int ms = 0; ms < MS; ++ms) {
 #pragma unroll
-        for (int ns = 0; ns < NS; ++ns) acc[ms][ns] = mfma_step<T>(WREG ? wreg[WREG ? s : 0][ns] : wq[WREG ? 0 : s % (WD + 1)][ns], af[s % NAF][ms], acc[ms][ns]);
+        for (int ns = 0; ns < NW; ++ns) acc[ms][ns] = mfma_step<T>(WREG ? wreg[WREG ? s : 0][ns] : wq[WREG ? 0 : s % (WD + 1)][ns], af[s % NAF][ms], acc[ms][ns]);
       }
       if (s < NP && stage_next) BPX_STAGE_PIECE(s < NP ? s : 0, nxt, chunk + 2 * KG);
       if (WREG && s >= NP && stage_next) {
@@ -321,7 +337,7 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
 #pragma unroll
         for (int k = k0; k < k1; ++k) {
 #pragma unroll
-          for (int ns = 0; ns < NS; ++ns)
+          for (int ns = 0; ns < NW; ++ns)
             wreg[WREG ? (k < STEPS ? k : 0) : 0][ns] = *reinterpret_cast<const u32x4_t*>(wl1 + ((size_t)k * 4 * Cout + ns * 16) * KPL);
         }
       }
@@ -330,7 +346,7 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
 #pragma unroll
       for (int d = 0; d < WD; ++d)
 #pragma unroll
-        for (int ns = 0; ns < NS; ++ns) wq[WREG ? 0 : d][ns] = *reinterpret_cast<const u32x4_t*>(wl1 + ((size_t)d * 4 * Cout + ns * 16) * KPL);
+        for (int ns = 0; ns < NW; ++ns) wq[WREG ? 0 : d][ns] = *reinterpret_cast<const u32x4_t*>(wl1 + ((size_t)d * 4 * Cout + ns * 16) * KPL);
     }
     BPX_STAMP();  // 4,6,8..: step loop of the chunk done
     BPX_LOAD_NORM(chunk + 2 * KG);
@@ -351,14 +367,14 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
 #pragma unroll
       for (int ms = 0; ms < MS; ++ms)
 #pragma unroll
-        for (int ns = 0; ns < NS; ++ns) xch[(ms * NS + ns) * 256 + tid] = acc[ms][ns];
+        for (int ns = 0; ns < NW; ++ns) xch[(ms * NW + ns) * 256 + tid] = acc[ms][ns];
     }
     __syncthreads();
     if (kg == 0) {
 #pragma unroll
       for (int ms = 0; ms < MS; ++ms)
 #pragma unroll
-        for (int ns = 0; ns < NS; ++ns) acc[ms][ns] += xch[(ms * NS + ns) * 256 + tid];
+        for (int ns = 0; ns < NW; ++ns) acc[ms][ns] += xch[(ms * NW + ns) * 256 + tid];
     }
   }
 
@@ -373,24 +389,27 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
       __syncthreads();
       if (kg != 0) continue;
       const T* wl = wsc + ((size_t)chunk * 4 * Cout + (size_t)g * Cout + co_base + j) * KPL;
-      u32x4_t wf[NS];
+      u32x4_t wf[NW];
 #pragma unroll
-      for (int ns = 0; ns < NS; ++ns) wf[ns] = *reinterpret_cast<const u32x4_t*>(wl + (size_t)ns * 16 * KPL);
+      for (int ns = 0; ns < NW; ++ns) wf[ns] = *reinterpret_cast<const u32x4_t*>(wl + (size_t)ns * 16 * KPL);
 #pragma unroll
       for (int ms = 0; ms < MS; ++ms) {
         u32x4_t af = *reinterpret_cast<const u32x4_t*>(smem + tb0 + ms * TSTR + cg_off);
 #pragma unroll
-        for (int ns = 0; ns < NS; ++ns) acc[ms][ns] = mfma_step<T>(wf[ns], af, acc[ms][ns]);
+        for (int ns = 0; ns < NW; ++ns) acc[ms][ns] = mfma_step<T>(wf[ns], af, acc[ms][ns]);
       }
     }
   }
 
   // ---- epilogue ---------------------------------------------------------------------------------
-  float s1[NS][4], s2[NS][4];
+  // statistics: one partial per z-slice (the m-subtiles a WN = 1 wave owns), so that the sums keep their order whatever WN
+  float s1[WN][NW][4], s2[WN][NW][4];
 #pragma unroll
-  for (int ns = 0; ns < NS; ++ns)
+  for (int pz = 0; pz < WN; ++pz)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) s1[ns][r] = s2[ns][r] = 0.f;
+    for (int ns = 0; ns < NW; ++ns)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s1[pz][ns][r] = s2[pz][ns][r] = 0.f;
 
   if (kg == 0) {
   T* __restrict__ yout = reinterpret_cast<T*>(p.y);
@@ -404,26 +423,26 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
   bool okv[MS];
   size_t voxv[MS];
   float imgv[MS];
-  TRaw traw[MS][NS];
-  float addv[NS][4], w1v[NS][4];
-  bpx_norm_rec recv[(EPI == EPI_FWD) ? 1 : NS][4];
+  TRaw traw[MS][NW];
+  float addv[NW][4], w1v[NW][4];
+  bpx_norm_rec recv[(EPI == EPI_FWD) ? 1 : NW][4];
 #pragma unroll
   for (int ms = 0; ms < MS; ++ms) {
-    const int t = (wave * MS + ms) * 16 + j;
+    const int t = (wm * MS + ms) * 16 + j;
     const int z = z0 + t / (TY * TX), y = y0 + (t / TX) % TY, x = x0 + t % TX;
     okv[ms] = z < p.D && y < p.H && x < p.W;
     voxv[ms] = okv[ms] ? (((size_t)n * p.D + z) * p.H + y) * p.W + x : vox00;
     imgv[ms] = rank1 ? reinterpret_cast<const float*>(p.sc)[voxv[ms]] : 0.f;
     if (has_t) {
 #pragma unroll
-      for (int ns = 0; ns < NS; ++ns) {
+      for (int ns = 0; ns < NW; ++ns) {
         const int co = co_base + ns * 16 + g * 4;
         traw[ms][ns] = *reinterpret_cast<const TRaw*>(reinterpret_cast<const TT*>(p.t) + voxv[ms] * (size_t)p.t_ld + (size_t)(co >> 4) * p.t_cs + (co & 15));
       }
     }
   }
 #pragma unroll
-  for (int ns = 0; ns < NS; ++ns) {
+  for (int ns = 0; ns < NW; ++ns) {
     const int co = co_base + ns * 16 + g * 4;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -439,7 +458,7 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
   }
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), once
 #pragma unroll
-  for (int ns = 0; ns < NS; ++ns) {
+  for (int ns = 0; ns < NW; ++ns) {
     const int co = co_base + ns * 16 + g * 4;
 #pragma unroll
     for (int ms = 0; ms < MS; ++ms) {
@@ -449,8 +468,8 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             v[r] = acc[ms][ns][r] + addv[ns][r] + imgv[ms] * w1v[ns][r];
-            s1[ns][r] += v[r];
-            s2[ns][r] += v[r] * v[r];
+            s1[WN == 1 ? 0 : ms / MPZ][ns][r] += v[r];
+            s2[WN == 1 ? 0 : ms / MPZ][ns][r] += v[r] * v[r];
           }
         } else {
           if (has_t) {
@@ -463,8 +482,8 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
               float u = fmaf(rc.scale, tv, rc.shift);
               v[r] = acc[ms][ns][r] * apply_act_bwd_rt<T, ACTK>(u, p.t_act);
               float xh = (tv - rc.mean) * rc.rstd;
-              s1[ns][r] += v[r];
-              s2[ns][r] += v[r] * xh;
+              s1[WN == 1 ? 0 : ms / MPZ][ns][r] += v[r];
+              s2[WN == 1 ? 0 : ms / MPZ][ns][r] += v[r] * xh;
             }
           } else {
 #pragma unroll
@@ -485,17 +504,20 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
   }   // kg == 0
   BPX_STAMP();  // epilogue stores issued
   if (p.part != nullptr) {
-    float* red = reinterpret_cast<float*>(smem_all + KG * NBUF * BUFB);  // [wave][NS*16][2]
+    float* red = reinterpret_cast<float*>(smem_all + KG * NBUF * BUFB);  // [z-slice][NS*16][2]
 #pragma unroll
-    for (int ns = 0; ns < NS; ++ns)
+    for (int pz = 0; pz < WN; ++pz)
+#pragma unroll
+    for (int ns = 0; ns < NW; ++ns)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float a = s1[ns][r], b = s2[ns][r];
+        float a = s1[pz][ns][r], b = s2[pz][ns][r];
 #pragma unroll
         for (int m = 1; m < 16; m <<= 1) { a += __shfl_xor(a, m, 64); b += __shfl_xor(b, m, 64); }
         if (j == 0 && kg == 0) {
-          red[((wave * NS * 16) + ns * 16 + g * 4 + r) * 2 + 0] = a;
-          red[((wave * NS * 16) + ns * 16 + g * 4 + r) * 2 + 1] = b;
+          const int row = WN == 1 ? wave : wm * WN + pz, col = WN == 1 ? ns * 16 : (wn * NW + ns) * 16;
+          red[((row * NS * 16) + col + g * 4 + r) * 2 + 0] = a;
+          red[((row * NS * 16) + col + g * 4 + r) * 2 + 1] = b;
         }
       }
     __syncthreads();
@@ -503,9 +525,22 @@ __global__ void __launch_bounds__(256 * KG, 2) conv3_kernel(const Conv3Params p)
       int c = tid >> 1, k = tid & 1;
       float a = red[(0 * NS * 16 + c) * 2 + k] + red[(1 * NS * 16 + c) * 2 + k] + red[(2 * NS * 16 + c) * 2 + k] +
                 red[(3 * NS * 16 + c) * 2 + k];
-      p.part[(((size_t)n * p.tilesPerSample + tile) * 2 + k) * Cout + co_base + c] = a;
+      p.part[(((size_t)n * p.tilesPerSample + tile) * 2 + k) * Cout + co_wg + c] = a;
     }
   }
+#undef BPX_MOFF
+}
+
+// WN of a 4x4x8 16-bit launch with NS n-subtiles.  The launcher's own choice per instance class (NS 2 = the 8^3 level, NS 4 = 16^3; forward,
+// dgrad) is measured (profiles/conv_wn_ab.txt, cfg-2 layers, B = 4, us at WN 1 / 2 / 4): fwd 16^3 384->128 71.5 / 59.4 / 64.3, dgrad 16^3 128->384
+// 70.7 / 61.1 / 70.9, dgrad 16^3 128->64 22.6 / 18.8 / 22.8, fwd 8^3 256->256+sc 38.0 / 34.6 / -, dgrad 8^3 256->128 23.2 / 21.6 / -: two waves
+// across the channels win in every class; four lose what they gain on the weights to the eight LDS fragment reads per step.
+static int conv_wn_pick(int ns, int epi) {
+  static const int wn_env = getenv("BPX_CONV_WN") ? atoi(getenv("BPX_CONV_WN")) : 0;
+  const int want = g_conv_wn < 0 ? wn_env : g_conv_wn;
+  if (want == 1 || want == 2 || want == 4) return want <= ns ? want : 1;
+  static const int table[2][2] = {{2, 2}, {2, 2}};   // [NS 2, NS 4][forward, dgrad]
+  return table[ns == 4][epi == EPI_DGRAD];
 }
 
 template <typename T, int EPI, typename TT = T>
@@ -520,20 +555,23 @@ int launch_conv3(const Conv3Params& p0, const TileCfg& c, hipStream_t s) {
   dim3 grid((unsigned)(p.N * p.tilesPerSample), (unsigned)(p.Cout / (16 * c.ns)));
   const bool elu = (EPI == EPI_FWD ? p.act : p.t_act) == BPX_ACT_ELU;
   const bool ext = (EPI == EPI_FWD ? p.act : p.t_act) > BPX_ACT_SILU;   // leaky_relu ... softplus: the ACTK = 2 instances
-  // two K groups per workgroup (KG = 2) for the small-tile 16-bit launches with an even number of >= 4 input chunks: the <= 16^3 layers
+  // the small-tile 16-bit launches (the <= 16^3 layers): two K groups per workgroup (KG = 2) with an even number of >= 4 input chunks, and WN of a
+  // group's four waves across the output channels (conv_wn_pick)
   if constexpr (sizeof(T) == 2) {
     static const bool kg_env = getenv("BPX_CONV_KG") == nullptr || atoi(getenv("BPX_CONV_KG")) != 0;   // A/B: BPX_CONV_KG=0
     const int nchunks = p.Cin / 16;
-    if ((g_conv_kg < 0 ? kg_env : g_conv_kg != 0) && c.tz == 4 && c.ty == 4 && c.tx == 8 && (c.ns == 2 || c.ns == 4) && nchunks >= 4 && nchunks % 2 == 0) {
-#define LK(NS)                                                                                   \
-      if (c.ns == NS) {                                                                          \
-        if (elu) conv3_kernel<T, 4, 4, 8, NS, EPI, 1, TT, 2><<<grid, 512, 0, s>>>(p);            \
-        else if (ext) conv3_kernel<T, 4, 4, 8, NS, EPI, 2, TT, 2><<<grid, 512, 0, s>>>(p);       \
-        else conv3_kernel<T, 4, 4, 8, NS, EPI, 0, TT, 2><<<grid, 512, 0, s>>>(p);                \
-        return 0;                                                                                \
+    if (c.tz == 4 && c.ty == 4 && c.tx == 8 && (c.ns == 2 || c.ns == 4)) {
+      const bool kg2 = (g_conv_kg < 0 ? kg_env : g_conv_kg != 0) && nchunks >= 4 && nchunks % 2 == 0;
+      const int wn = conv_wn_pick(c.ns, EPI);
+#define LW(NS, KG_, WN_)                                                                                      \
+      if (c.ns == NS && kg2 == (KG_ == 2) && wn == WN_) {                                                     \
+        if (elu) conv3_kernel<T, 4, 4, 8, NS, EPI, 1, TT, KG_, WN_><<<grid, 256 * KG_, 0, s>>>(p);            \
+        else if (ext) conv3_kernel<T, 4, 4, 8, NS, EPI, 2, TT, KG_, WN_><<<grid, 256 * KG_, 0, s>>>(p);       \
+        else conv3_kernel<T, 4, 4, 8, NS, EPI, 0, TT, KG_, WN_><<<grid, 256 * KG_, 0, s>>>(p);                \
+        return 0;                                                                                             \
       }
-      LK(2) LK(4)
-#undef LK
+      LW(2, 2, 1) LW(4, 2, 1) LW(2, 2, 2) LW(4, 2, 2) LW(4, 2, 4) LW(2, 1, 2) LW(4, 1, 2) LW(4, 1, 4)
+#undef LW
     }
   }
 #define L(TZ, TY, TX, NS)                                                        \
@@ -582,6 +620,15 @@ static bool use_lean(int dtype, const Conv3Params& p) {
   auto ext = [](int cs, int C) { return cs == 16 ? (int64_t)0 : (int64_t)cs * (C / 16); };
   const int64_t planar = std::max(std::max(ext(p.x_cs, p.Cin), ext(p.y_cs, p.Cout)), std::max(p.sc ? ext(p.sc_cs, p.sc_C) : 0, p.t ? ext(p.t_cs, p.Cout) : 0));
   return p.W > 8 && vox * ldmax < (1ll << 31) && planar < (1ll << 31) && vox < (1ll << 30) && al(p.bias) && al(p.bias_sc) && al(p.wsc) && al(p.in_norm) && al(p.t_norm);
+}
+
+// 1 when a launch of this shape has a conv3_kernel instance with `wn` waves across the output channels (16-bit storage, 4x4x8 tiles,
+// wn <= NS; the plain kernel must be the one that runs: below 32^3 voxels per sample)
+extern "C" int bpx_conv3d_wn_supported(int dtype, int D, int H, int W, int Cout, int wn) {
+  if (wn == 1) return 1;
+  if (dtype != BPX_BF16 && dtype != BPX_F16 && dtype != BPX_MIX16) return 0;
+  TileCfg c = pick_cfg(dtype == BPX_MIX16 ? BPX_BF16 : dtype, D, H, W, Cout);
+  return (wn == 2 || wn == 4) && c.tx == 8 && (c.ns == 2 || c.ns == 4) && wn <= c.ns ? 1 : 0;
 }
 
 extern "C" int bpx_conv3d_stats_tiles(int dtype, int N, int D, int H, int W, int Cout) {

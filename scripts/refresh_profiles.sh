@@ -73,6 +73,13 @@ for zm in 1 0; do BPX_CONV_ZM=$zm python bench.py --mode infer --steps 40 --warm
   echo "# whole step, 40 graph-replayed steps, same box, alternating (bench.py --mode train / infer)"
   for kg in 1 0 1 0; do BPX_CONV_KG=$kg python bench.py --mode train --feed device --steps 40 --warmup 8 --no-cpu-baseline --no-bf16-record --no-launch-events 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('BPX_CONV_KG=$kg train ms_per_step %.4f (device-resident batch)' % d['ms_per_step'])"; done
   for kg in 1 0 1 0; do BPX_CONV_KG=$kg python bench.py --mode infer --steps 40 --warmup 8 --no-cpu-baseline --no-launch-events 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('BPX_CONV_KG=$kg infer ms_per_step %.4f' % d['ms_per_step'])"; done ) 2>&1 | grep -v amdgpu.ids > $O/${R}_step_conv_kg_ab.txt
+# waves across the output channels in the small-tile kernel (conv3_kernel<..., WN>): kernel times (forward rows and their dgrad twins) and the whole step, alternating
+( echo "# conv3_kernel<..., WN>: forward rows of tests/bench_kernels.py conv_fwd (BPX_CONV_WN alternating), then scripts/bench_conv_wn.py (forward in fp16 + dgrad twins, hook alternating in one process)"
+  for wn in 1 2 4 1 2 4; do echo "== BPX_CONV_WN=$wn"; BPX_CONV_WN=$wn python tests/bench_kernels.py conv_fwd --only 11,12,13,14,15,16 2>&1 | grep -E "^conv_fwd"; done
+  python scripts/bench_conv_wn.py
+  echo "# whole step, 40 graph-replayed steps, same box, alternating (bench.py --mode train / infer); 0 = the launcher's choice"
+  for wn in 0 1 0 1 0 1; do BPX_CONV_WN=$wn python bench.py --mode train --steps 40 --warmup 8 --no-cpu-baseline --no-bf16-record --no-launch-events 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('BPX_CONV_WN=$wn train ms_per_step %.4f' % d['ms_per_step'])"; done
+  for wn in 0 1 0 1 0 1; do BPX_CONV_WN=$wn python bench.py --mode infer --steps 40 --warmup 8 --no-cpu-baseline --no-launch-events 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('BPX_CONV_WN=$wn infer ms_per_step %.4f' % d['ms_per_step'])"; done ) 2>&1 | grep -v amdgpu.ids > $O/${R}_conv_wn_ab.txt
 ( python tests/bench_kernels.py k1 --reps 20; python tests/bench_kernels.py pws --reps 20 ) 2>&1 | grep -v amdgpu.ids > $O/${R}_stream_vs_tile.txt
 # round 5: transposed-conv forward of level 0 (convt_k1_kernel against pw_kernel) and the first layer (buffer- against pointer-addressed), event timing
 # in the network; the store-pattern probe
