@@ -89,6 +89,10 @@ _SIGS = {
     "bpx_region_moments": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "bpx_region_faces": ([_vp, _i, _i, _i, _i, _vp, _vp], _i),
     "bpx_region_perimeter2d": ([_vp, _i, _i, _i, _vp, _vp], _i),
+    "bpx_intensity_props": ([_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "bpx_debug_set_intensityprops_wave": ([_i], _i),
+    "bpx_intensity_pieces_host": ([C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)], _i),
+    "bpx_intensity_round_host": ([C.POINTER(C.c_int64), _i, C.POINTER(C.c_double)], _i),
     "bpx_morph": ([_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "bpx_peaks_workspace": ([_i, _i, _i], _i64),
     "bpx_peak_local_max": ([_vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp], _i),
@@ -239,7 +243,8 @@ def _load() -> C.CDLL:
                       ("BPX_BWD_RS", "bpx_debug_set_bwd_rs"), ("BPX_FUSED_BITS", "bpx_debug_set_bwd_fused"),
                       ("BPX_CT_BWD", "bpx_debug_set_convt_bwd"), ("BPX_LABEL_TILED", "bpx_debug_set_label_tiled"),
                       ("BPX_OVERLAP_PER_VOXEL", "bpx_debug_set_overlap_per_voxel"),
-                      ("BPX_REGIONPROPS_LOCAL", "bpx_debug_set_regionprops_local")):
+                      ("BPX_REGIONPROPS_LOCAL", "bpx_debug_set_regionprops_local"),
+                      ("BPX_INTENSITYPROPS_WAVE", "bpx_debug_set_intensityprops_wave")):
         if os.environ.get(env) is not None:
             getattr(lib, hook)(int(os.environ[env]))
     return lib

@@ -28,6 +28,9 @@ percentiles / histogram on the host.
 * ``shape_props`` and ``elongation`` / ``axis_lengths`` / ``surface_area`` / ``sphericity`` / ``perimeter`` / ``circularity`` finish that
   filter (``csrc/shapeprops.hip``): exact second-order coordinate sums, the covariance from their exact 128-bit numerator, voxel faces per axis
   and the weight classes of scikit-image's 2-D perimeter - integer sums, bit for bit a NumPy twin - and the measures as torch expressions;
+* ``intensity_props`` measures an image over them (``csrc/intensityprops.hip``): minimum, maximum, the EXACT sum in ``int64`` limbs, that sum
+  rounded once to ``float64`` (``math.fsum``'s value) and the mean of every label, for ``float32``, ``uint8`` and ``uint16`` images - the mean
+  foreground probability of an instance as its confidence, one ``select_objects`` away;
 * ``binary_erosion`` / ``binary_dilation`` / ``binary_opening`` / ``binary_closing``, ``erosion`` / ``dilation``, ``find_boundaries``,
   ``binary_fill_holes`` and ``clear_border`` are the steps between those calls (``csrc/morph.hip``: one 3 x 3 x 3 stencil pass over ``uint8``,
   ``int32`` or ``float32``; the structuring element is ``generate_binary_structure(ndim, connectivity)``): ``scipy.ndimage``'s ``binary_*``,
@@ -694,9 +697,9 @@ def matching(y_true: torch.Tensor, y_pred: torch.Tensor, thresh=0.5, criterion: 
 # What every consumer of label() / watershed() does next: the detection workflow takes the centroids of its labelled blobs, the instance workflow
 # measures every instance and drops those that fail a property test, and a crop of an instance needs its box (skimage.measure.regionprops,
 # scipy.ndimage.find_objects / center_of_mass on the host there).  Offered: area, bbox, the exact coordinate sums and the centroid; second
-# moments, voxel faces, the 2-D perimeter and the measures derived from them are shape_props, below.  NOT offered: intensity properties (a
-# float sum by atomics depends on the order and would break "the same bits every run"; min / max need a segmented scan that the closed-form
-# runs avoid); a meshed surface; coords, image, convex_*; volumes of 2^31 voxels or more; multi-GPU slabs.
+# moments, voxel faces, the 2-D perimeter and the measures derived from them are shape_props, below; minimum, maximum, exact sum and mean of
+# an image over every label are intensity_props, further below.  NOT offered: intensity_std and the weighted moments; a meshed surface; coords,
+# image, convex_*; volumes of 2^31 voxels or more; multi-GPU slabs.
 
 class RegionProps(NamedTuple):
     """``region_props``' result, every field a device tensor with one row per label ``0..N``; row 0 is the background's and holds zeros (NaN in
@@ -720,7 +723,8 @@ def region_props(labels: torch.Tensor, num=None) -> RegionProps:
 
     Refused before anything is launched: a negative ``num`` and a rank other than 2 / 3 (``ValueError``); a CPU tensor (``RuntimeError``); a dtype
     other than ``int32``, an empty volume and 2^31 voxels or more (``NotImplementedError``).  Second moments, faces and the 2-D perimeter:
-    ``shape_props``.  Not offered: intensity properties, ``coords`` / ``image`` / ``convex_*``, multi-GPU slabs (see the comment above)."""
+    ``shape_props``; minimum, maximum, sum and mean of an image: ``intensity_props``.  Not offered: ``intensity_std``, ``coords`` / ``image`` /
+    ``convex_*``, multi-GPU slabs (see the comment above)."""
     n_max = None if num is None else int(num)
     if n_max is not None and n_max < 0:
         raise ValueError(f"num must not be negative (got {n_max})")
@@ -810,7 +814,7 @@ def shape_props(labels: torch.Tensor, num=None) -> ShapeProps:
     ``num`` as for ``region_props``.  Launches fixed by the shape and ``N`` (``bpx_region_props``, ``bpx_region_moments``, ``bpx_region_faces``
     and, in 2-D, ``bpx_region_perimeter2d``), nothing else read back: capturable.  Refused before anything is launched, in this order: what
     ``region_props`` refuses up to the voxel count; a shape with ``n * (Emax - 1)**2 >= 2**63`` (``NotImplementedError``, ``moments_fit``);
-    then its dtype, device and empty-volume refusals.  Not offered: intensity properties, ``coords`` / ``image`` / ``convex_*``, multi-GPU slabs.
+    then its dtype, device and empty-volume refusals.  Intensities: ``intensity_props``.  Not offered: ``coords`` / ``image`` / ``convex_*``, multi-GPU slabs.
 
     The measures on top - ``principal_moments``, ``axis_lengths``, ``elongation``, ``surface_area``, ``perimeter``, ``circularity``,
     ``sphericity`` - are torch expressions of one row per label; ``select_objects(labels, elongation(p) < 3)`` filters by them."""
@@ -842,6 +846,92 @@ def shape_props(labels: torch.Tensor, num=None) -> ShapeProps:
         sums, bbox, mom, faces = sums[:, 1:], _columns(bbox, (1, 2, 4, 5)), _columns(mom, (1, 2, 5)), faces[:, 1:]
     cov = _columns(cov, [c for row in (_COV_2D if two_d else _COV_3D) for c in row]).reshape(rows, labels.dim(), labels.dim())
     return ShapeProps(area, bbox, sums, sums.double() / area.double()[:, None], mom, cov, faces, classes)
+
+
+# ---- intensity properties: exact sum, mean, min, max of an image over every label (csrc/intensityprops.hip) -----------------------------------------
+# The one per-label measurement with a second volume-sized operand: the mean foreground probability of an instance as its confidence, the mean /
+# minimum / maximum raw intensity of a cell (skimage's intensity_mean / intensity_min / intensity_max, scipy.ndimage.mean / minimum / maximum
+# with an index, on the host there).  "The same bits every run" holds: min / max are integer atomics on an order-preserving key, and the sum is
+# kept EXACTLY in int64 limbs of a fixed-point line (integer adds commute) and rounded once.  NOT offered: intensity_std or any second moment of
+# a float32 image (the exact product needs 18 limbs - a named follow-up); centroid_weighted and the weighted moments; multi-channel images; int32,
+# float64 or 16-bit float images; percentiles per label; volumes of 2^31 voxels or more; multi-GPU slabs.
+
+class IntensityProps(NamedTuple):
+    """``intensity_props``' result, every field a device tensor with one row per label ``0..N``; row 0 and the row of a label that no voxel
+    carries hold zeros (NaN in ``mean``)."""
+    area: torch.Tensor        # int32 (N + 1,): equals region_props(...).area bit for bit
+    min: torch.Tensor         # (N + 1,) float32 for a float32 image, int32 for uint8 / uint16
+    max: torch.Tensor         # likewise
+    sum: torch.Tensor         # float64 (N + 1,): the exact sum, rounded once (to nearest even)
+    mean: torch.Tensor        # float64 (N + 1,): sum / area, one IEEE division; NaN where area == 0
+    sum_limbs: torch.Tensor   # int64 (N + 1, NL): NL = 9 for float32 (unit 2^-149), 1 for uint8 / uint16 (unit 1)
+    nonfinite: torch.Tensor   # int32 (N + 1, 3): the numbers of NaN, +inf, -inf voxels (zeros for integer images)
+
+
+_INTENSITY_DTYPES = {torch.float32: (L.F32, 9, torch.float32), torch.uint8: (L.U8, 1, torch.int32)}
+if hasattr(torch, "uint16"):
+    _INTENSITY_DTYPES[torch.uint16] = (L.U16, 1, torch.int32)
+
+
+def intensity_props(labels: torch.Tensor, image: torch.Tensor, num=None) -> IntensityProps:
+    """Count, minimum, maximum, EXACT sum and mean of ``image`` over every label ``1..N`` of a 2-D ``(Y, X)`` or 3-D ``(Z, Y, X)`` ``int32``
+    label tensor, as an ``IntensityProps`` named tuple of DEVICE tensors.  ``image`` has the labels' shape and is ``float32``, ``uint8`` or
+    ``torch.uint16``.  Every field but ``mean`` is bit for bit the same on every run, and ``mean`` follows from two of them by one division.
+
+    ``sum_limbs[l, j]`` is the sum, over the finite voxels of label ``l``, of that voxel's piece for limb ``j``: with ``bits`` the voxel's
+    ``float32`` word, ``E = (bits >> 23) & 255`` and ``f = bits & 0x7fffff``, ``(m, q) = (f, 0)`` if ``E == 0`` else ``(f | 0x800000, E - 1)``,
+    ``w = m << (q & 31)``; the piece for limb ``q >> 5`` is ``w & 0xffffffff``, the piece for limb ``(q >> 5) + 1`` is ``w >> 32``, both negated
+    for a negative voxel.  For integer images limb 0 is the plain integer sum.  ``sum`` is the exact value ``sum_j limbs[j] * 2**(32 j - 149)``
+    (unit 1 for integers) rounded ONCE to ``float64``, to nearest even - what ``math.fsum`` returns; below ``2**159`` in magnitude and, if
+    nonzero, at least ``2**-149``, so it neither overflows nor underflows; an exact zero is ``+0.0``.  ``mean = sum / area`` rounds twice (the
+    sum, then the division).  NaN voxels are left out of ``min``, ``max`` and ``sum_limbs``, are counted in ``nonfinite`` and make ``sum`` and
+    ``mean`` NaN; a label whose voxels are all NaN has ``min = max = NaN``.  Infinite voxels take part in ``min`` and ``max``, are left out of
+    the limbs and make ``sum`` that infinity, or NaN when both signs occur in the label.  ``min`` and ``max`` follow the order of the bits:
+    ``-0.0 < +0.0``, and the bits of the winning voxel are returned.  Voxels with a label ``<= 0`` or ``> N`` contribute nothing.
+
+    ``num`` as for ``region_props``: a Python int, a 0-d tensor, or ``None``, which reads ``labels.max()`` back.  Views are taken via
+    ``.contiguous()``.  Three launches fixed by the shape, the dtype and ``N``, nothing else read back: capturable.
+    ``select_objects(labels, p.mean >= t)`` filters instances by their mean probability.
+
+    Refused before anything is launched, in this order: a rank other than 2 / 3, a negative ``num``, an image of another shape (``ValueError``);
+    a CPU tensor or operands on two devices (``RuntimeError``); labels that are not ``int32``, an image dtype other than the three named, an
+    empty volume, 2^31 voxels or more (``NotImplementedError``).  Not offered: ``intensity_std`` and other second moments, weighted centroids
+    and moments, multi-channel images, ``int32`` / ``float64`` / 16-bit float images, percentiles, multi-GPU slabs (see the comment above)."""
+    if labels.dim() not in (2, 3):
+        raise ValueError(f"biapy_amd.prepost.intensity_props takes a 2-D (Y, X) or 3-D (Z, Y, X) tensor (got {labels.dim()} dimensions)")
+    n_max = None if num is None else int(num)
+    if n_max is not None and n_max < 0:
+        raise ValueError(f"num must not be negative (got {n_max})")
+    if tuple(image.shape) != tuple(labels.shape):
+        raise ValueError(f"biapy_amd.prepost.intensity_props: the image must have the labels' shape {tuple(labels.shape)} (got {tuple(image.shape)})")
+    if not labels.is_cuda or not image.is_cuda:
+        raise RuntimeError("biapy_amd.prepost runs on the MI355X only (labels are on %s, the image on %s); there is no CPU path" % (labels.device, image.device))
+    if labels.device != image.device:
+        raise RuntimeError(f"biapy_amd.prepost.intensity_props: labels ({labels.device}) and image ({image.device}) must be on the same device")
+    if labels.dtype != torch.int32:
+        raise NotImplementedError(f"biapy_amd.prepost.intensity_props works on the int32 labels of label() (got {labels.dtype})")
+    if image.dtype not in _INTENSITY_DTYPES:
+        raise NotImplementedError(f"biapy_amd.prepost.intensity_props works on float32, uint8 or uint16 images (got {image.dtype})")
+    if labels.numel() < 1:
+        raise NotImplementedError("biapy_amd.prepost.intensity_props: empty volumes are not supported")
+    if labels.numel() >= 2 ** 31:
+        raise NotImplementedError(f"biapy_amd.prepost.intensity_props: {labels.numel()} voxels - volumes of 2^31 voxels or more are not supported")
+    Z, Y, X = (1,) + tuple(labels.shape) if labels.dim() == 2 else tuple(labels.shape)
+    lab, img = labels.contiguous(), image.contiguous()
+    if n_max is None:
+        n_max = max(int(lab.max()), 0)
+    code, nl, out_dtype = _INTENSITY_DTYPES[img.dtype]
+    dev, rows = lab.device, n_max + 1
+    area = torch.empty(rows, dtype=torch.int32, device=dev)
+    lo = torch.empty(rows, dtype=out_dtype, device=dev)
+    hi = torch.empty(rows, dtype=out_dtype, device=dev)
+    limbs = torch.empty((rows, nl), dtype=torch.int64, device=dev)
+    nonf = torch.empty((rows, 3), dtype=torch.int32, device=dev)
+    total = torch.empty(rows, dtype=torch.float64, device=dev)
+    mean = torch.empty(rows, dtype=torch.float64, device=dev)
+    L.check(lib.bpx_intensity_props(lab.data_ptr(), img.data_ptr(), code, Z, Y, X, n_max, area.data_ptr(), lo.data_ptr(), hi.data_ptr(), limbs.data_ptr(),
+                                    nonf.data_ptr(), total.data_ptr(), mean.data_ptr(), L.stream_ptr()))
+    return IntensityProps(area, lo, hi, total, mean, limbs, nonf)
 
 
 def _shape_props(p, what: str) -> int:

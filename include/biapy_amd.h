@@ -978,6 +978,35 @@ int bpx_region_moments(const int32_t* labels_d, int Z, int Y, int X, int n_max, 
 int bpx_region_faces(const int32_t* labels_d, int Z, int Y, int X, int n_max, int64_t* faces_d, bpx_stream_t stream);
 int bpx_region_perimeter2d(const int32_t* labels_d, int Y, int X, int n_max, int32_t* classes_d, bpx_stream_t stream);
 
+/* ---- intensity properties of a label volume (biapy_amd/prepost.py: intensity_props; csrc/intensityprops.hip, csrc/intensityprops_core.h) ----
+ * labels (Z,Y,X) int32 and image (Z,Y,X) of image_dtype BPX_F32, BPX_U8 or BPX_U16, both contiguous; 2-D is Z = 1; Z * Y * X < 2^31;
+ * 0 <= n_max < 2^31 - 1; a label <= 0 or > n_max is background 0 (as for bpx_region_props).  NL = 9 for BPX_F32, 1 for the integer types.  For
+ * every label l in 1..n_max, over the voxels that carry it:
+ *   area_d[l]         = their number (int32; bpx_region_props' area),
+ *   min_d[l], max_d[l] = the smallest and the largest image value: float32 for BPX_F32 (the winning voxel's bits, -0.0 < +0.0, NaN voxels left
+ *                       out, NaN when every voxel is NaN), int32 for the integer types,
+ *   limbs_d[l][NL]    = the exact sum of the finite voxels as int64 limbs.  BPX_F32: unit 2^-149, limb j weighs 2^(32 j); with E = (bits >> 23)
+ *                       & 255, f = bits & 0x7fffff, (m, q) = (f, 0) if E == 0 else (f | 0x800000, E - 1) and w = m << (q & 31) a voxel adds
+ *                       w & 0xffffffff to limb q >> 5 and w >> 32 to limb (q >> 5) + 1, both negated for a negative voxel.  Integers: the plain sum,
+ *   nonfinite_d[l][3] = the numbers of NaN, +inf and -inf voxels (int32; zeros for the integer types),
+ *   sum_d[l]          = sum_j limbs[j] * 2^(32 j - 149) (unit 1 for integers) rounded ONCE to float64, to nearest even; +0.0 for an exact zero; NaN
+ *                       with a NaN voxel or infinities of both signs, else the infinity present,
+ *   mean_d[l]         = sum_d[l] / area_d[l], one IEEE division (a second rounding).
+ * Row 0 and the row of a label that no voxel carries are all zeros, with NaN in mean_d.
+ * Three launches (init, accumulate, finish) fixed by the shape, the dtype and n_max; the outputs are the accumulators (min_d / max_d hold
+ * order-preserving keys until the finish pass), no workspace; relaxed integer atomics only (uint32 / int64 add, uint32 min / max), no float
+ * atomics: the same bits every run; nothing read back; capturable.
+ * Argument checks run on the host before anything is launched, in this order, and set bpx_last_error: null pointers, extents, the voxel
+ * count, n_max, the dtype, alignment (4 bytes for labels, area, min, max, nonfinite; 8 for limbs, sum, mean; the element size for the image). */
+int bpx_intensity_props(const int32_t* labels_d, const void* image_d, int image_dtype, int Z, int Y, int X, int n_max, int32_t* area_d, void* min_d,
+                        void* max_d, int64_t* limbs_d, int32_t* nonfinite_d, double* sum_d, double* mean_d, bpx_stream_t stream);
+int bpx_debug_set_intensityprops_wave(int on); /* test / A-B hook of bpx_intensity_props' accumulate pass: 0 = form (a), each lane merges its four voxels and sends them to the block's table; 1 = form (b), in addition a trip of 256 voxels of one label and one limb pair is reduced across the wave and sent once; negative = back to the default; same bits (environment: BPX_INTENSITYPROPS_WAVE) */
+/* the per-voxel decomposition and the rounding of bpx_intensity_props on HOST memory (nothing is launched; for tests without a device):
+ * the limb (q >> 5; -1 for NaN and the infinities, which have no pieces) and the two signed pieces of a float32's bits; the float64 nearest to
+ * nl limbs (nl 9: unit 2^-149; nl 1: unit 1), every limb below 2^63 - 2^32 in magnitude. */
+int bpx_intensity_pieces_host(uint32_t bits, int* limb, int64_t* lo, int64_t* hi);
+int bpx_intensity_round_host(const int64_t* limbs, int nl, double* out);
+
 /* ---- morphology: erosion, dilation and the boundary map (biapy_amd/prepost.py: binary_erosion, binary_dilation, binary_opening, binary_closing,
  * erosion, dilation, find_boundaries; csrc/morph.hip, csrc/morph_core.h) ----
  * in (Z,Y,X) contiguous, dtype BPX_U8, BPX_I32 or BPX_F32 (the 4-byte types 4-byte aligned; uint8 at any address); ndim 3, or 2 with Z = 1;
