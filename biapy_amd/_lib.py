@@ -84,6 +84,13 @@ _SIGS = {
     "bpx_overlap_workspace": ([_i64], _i64),
     "bpx_label_overlap": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp], _i),
     "bpx_debug_set_overlap_per_voxel": ([_i], _i),
+    "bpx_stitch_begin": ([_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "bpx_stitch_first": ([_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp], _i),
+    "bpx_stitch_shell": ([_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp], _i),
+    "bpx_stitch_contact_workspace": ([_i, _i, _i, _i, _i, _i, _i, _i64], _i64),
+    "bpx_stitch_contact": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp], _i),
+    "bpx_stitch_resolve": ([_vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
+    "bpx_stitch_apply": ([_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp], _i),
     "bpx_region_props": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "bpx_debug_set_regionprops_local": ([_i], _i),
     "bpx_region_moments": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
@@ -280,6 +287,12 @@ class PatchVol(C.Structure):
     """bpx_patch_vol (include/biapy_amd.h)."""
     _fields_ = [("img", C.c_void_p), ("tgt", C.c_void_p), ("cls", C.c_void_p), ("Z", C.c_int32), ("Y", C.c_int32), ("X", C.c_int32),
                 ("reserved", C.c_int32), ("row0", C.c_int64)]
+
+
+class StitchBlock(C.Structure):
+    """bpx_stitch_block (include/biapy_amd.h)."""
+    _fields_ = [("labels", C.c_void_p), ("z0", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32), ("ez", C.c_int32), ("ey", C.c_int32),
+                ("ex", C.c_int32)]
 
 
 class PatchCfg(C.Structure):

@@ -12,6 +12,8 @@ percentiles / histogram on the host.
 * mean / std use double accumulation on the device (NumPy: float32 pairwise sums) - equal to ~1e-7 relative, not bitwise;
 * ``label`` / ``component_sizes`` / ``remove_small_objects`` carry on from the binarised mask: connected components with
   ``scipy.ndimage.label``'s numbering bit for bit (``csrc/label.hip``), so the mask no longer leaves the device to be labelled;
+* ``LabelStitcher`` / ``label_blocks`` join the labels of the blocks of a regular grid into the labels of the whole volume (``csrc/stitch.hip``): a
+  union-find over label ids fed by the block shells, ``scipy.ndimage.label``'s numbering bit for bit, so labelling is not bound to one call's 2^31 voxels;
 * ``distance_transform_edt`` / ``label_distance`` give the exact Euclidean distance map of the mask or of the labels
   (``csrc/edt.hip``): on a unit grid ``scipy.ndimage.distance_transform_edt`` bit for bit;
 * ``distance_transform_edt(return_indices=...)`` adds the nearest background voxel itself (``csrc/edt_index.hip``; among equally near ones the
@@ -232,7 +234,7 @@ def binarize(pred: torch.Tensor, threshold: Optional[float] = None) -> torch.Ten
 # ---- connected components of the binarised mask (csrc/label.hip) ----------------------------------------------------------------
 # What follows binarize() in every segmentation workflow of the reference: label(seed_map) ahead of the instance watershed, the
 # detection workflow's blobs, object counts and small-object removal of semantic masks (skimage.measure.label / scipy.ndimage.label
-# on the host there).  The watershed is watershed() below, the matcher matching() at the end; instance merging is not offered.
+# on the host there).  The watershed is watershed() below, the matcher matching() at the end; the labels of several calls are joined by LabelStitcher / label_blocks, next section.
 
 def _label_volume(t: torch.Tensor, what: str) -> Tuple[int, int, int]:
     if t.dim() not in (2, 3):
@@ -310,6 +312,257 @@ def remove_small_objects(labels: torch.Tensor, min_size: int = 64, relabel: bool
     L.check(lib.bpx_label_filter(out.data_ptr(), out.numel(), n_max, sizes.data_ptr(), int(min_size), 1 if relabel else 0, left.data_ptr(),
                                  L.stream_ptr()))
     return (out, left) if return_num else out
+
+
+# ---- labels of several calls joined into the labels of the whole volume (csrc/stitch.hip, csrc/stitch_core.h) ----------------------------------
+# Every call above and below ends at 2^31 voxels, and watershed()'s workspace makes per-block processing the only route for large volumes long
+# before that; the predictors of chunked.py deliver volumes of any size.  LabelStitcher joins what the calls on the blocks of a regular grid
+# produce - a union-find over label ids, fed by the voxels on the block shells alone, and one renumbering pass - and label_blocks is label() for
+# a mask of any size on top of it.  Not offered: overlapping blocks (halo matching by IoU), blocks resident on the host or on other GPUs (only
+# the shells would have to travel: the named follow-up), any other call past 2^31 voxels, int64 labels, more than 3 dimensions.
+
+def _grid_shapes(shape, block_shape, what: str):
+    shape = tuple(int(v) for v in shape)
+    if len(shape) not in (2, 3):
+        raise ValueError(f"biapy_amd.prepost.{what} takes a 2-D (Y, X) or 3-D (Z, Y, X) shape (got {len(shape)} dimensions)")
+    if min(shape) < 1:
+        raise ValueError(f"biapy_amd.prepost.{what}: every extent must be at least 1 (got {shape})")
+    block = tuple(int(v) for v in block_shape)
+    if len(block) != len(shape):
+        raise ValueError(f"biapy_amd.prepost.{what}: block_shape must have {len(shape)} entries for a {len(shape)}-D shape (got {block})")
+    if min(block) < 1:
+        raise ValueError(f"biapy_amd.prepost.{what}: block extents must be at least 1 (got {block})")
+    block = tuple(min(b, s) for b, s in zip(block, shape))
+    if math.prod(block) >= 2 ** 31:
+        raise NotImplementedError(f"biapy_amd.prepost.{what}: {math.prod(block)} voxels per block - blocks of 2^31 voxels or more are not supported (int32 indices)")
+    if len(shape) == 2:
+        shape, block = (1,) + shape, (1,) + block
+    return shape, block
+
+
+class LabelStitcher:
+    """Joins the ``int32`` labels of the blocks of a regular grid into the labels of the whole volume, in place and on the device.
+
+    The volume ``shape`` (2-D is handled as ``Z = 1``) is cut every ``block_shape``; the last block of an axis may be ragged; block ``(i, j, k)``
+    covers ``[i*bz, min((i+1)*bz, Z))`` and likewise in y and x.  Each block is a contiguous ``int32`` device tensor of its own with local labels
+    ``1..n_b`` (``<= 0`` or ``> n_b``: background) - what ``label`` or ``watershed`` returns for it.  Two uniting rules:
+
+    * ``rule="touch"`` (connected components): two labels are united when a voxel of one has a voxel of the other among its neighbours at
+      ``connectivity`` in ANOTHER block - across faces, and at connectivity 2 and 3 across block edges and corners too.  On blocks that ``label``
+      produced at the same connectivity the result is ``scipy.ndimage.label`` of the whole mask BIT FOR BIT.
+    * ``rule="contact"`` (instances, e.g. per-block ``watershed``; connectivity 1 only; product-defined, checked against a host twin,
+      ``tests/stitch_ref.py``): only face-adjacent blocks take part.  For A (low side) and B (high side) along an axis, ``c(a, b)`` counts the
+      in-plane positions where A's last plane holds ``a`` and B's first plane holds ``b``, ``s_A(a)`` / ``s_B(b)`` the positions of each plane that
+      hold the label, partner or not; ``a`` and ``b`` are united iff ``c(a, b) * q >= p * min(s_A(a), s_B(b))`` with ``min_contact = (p, q)``
+      integers, ``0 < p <= q <= 32768``.  UNIONS ARE TRANSITIVE: a chain of contacts fuses into one object, whatever the ratio between its ends.
+
+    Numbering: the merged objects are ``1..M`` in raster order of each object's first voxel in the WHOLE volume - ``scipy.ndimage.label``'s.
+
+    ``add(index, labels, num)`` registers a block, ``resolve()`` returns ``M`` as a 0-d ``int32`` device tensor (``-1``: more than ``max_labels``
+    labels over all blocks, or at ``"contact"`` more distinct pairs on the faces than the table holds), ``apply()`` renumbers all blocks in place
+    (on overflow they stay as they were).  ``max_labels`` defaults to ``min(total voxels, 2**22)`` and sizes five tables of 4 to 8 bytes per entry.
+    ``resolve()`` + ``apply()`` are a launch sequence fixed by the grid, read nothing back and can be captured in a graph and replayed on
+    overwritten block contents; ``add`` uploads a descriptor and is NOT capturable.  No float arithmetic: the same bits every run."""
+
+    def __init__(self, shape, block_shape, connectivity: int = 1, rule: str = "touch", min_contact=(1, 2), max_labels: Optional[int] = None):
+        self.ndim = len(tuple(shape))
+        self.shape, self.block_shape = _grid_shapes(shape, block_shape, "LabelStitcher")
+        c = int(connectivity)
+        if not 1 <= c <= self.ndim:
+            raise ValueError(f"connectivity must be in 1..{self.ndim} for a {self.ndim}-D volume (got {connectivity})")
+        if rule not in ("touch", "contact"):
+            raise ValueError(f"rule must be 'touch' or 'contact' (got {rule!r})")
+        if rule == "contact" and c != 1:
+            raise ValueError(f"rule='contact' looks at block faces only: connectivity must be 1 (got {connectivity})")
+        p, q = (int(v) for v in min_contact)
+        if not 0 < p <= q <= 32768:
+            raise ValueError(f"min_contact = (p, q) needs integers with 0 < p <= q <= 32768 (got {tuple(min_contact)})")
+        total = math.prod(self.shape)
+        t_max = min(total, 2 ** 22) if max_labels is None else int(max_labels)
+        if not 1 <= t_max < 2 ** 31 - 1:
+            raise ValueError(f"max_labels must be in [1, 2^31 - 1) (got {max_labels})")
+        self.connectivity, self.rule, self.min_contact, self.max_labels = c, rule, (p, q), t_max
+        self.grid = tuple(-(-s // b) for s, b in zip(self.shape, self.block_shape))
+        self.nblocks = math.prod(self.grid)
+        if self.nblocks >= 2 ** 20:
+            raise NotImplementedError(f"biapy_amd.prepost.LabelStitcher: {self.nblocks} blocks - grids of 2^20 blocks or more are not supported")
+        self._blocks = [None] * self.nblocks          # (labels, num: int / 0-d tensor / None)
+        self._dev = None
+
+    def _index(self, index) -> Tuple[int, int, int]:
+        idx = tuple(int(v) for v in index)
+        if len(idx) != self.ndim:
+            raise ValueError(f"biapy_amd.prepost.LabelStitcher.add: index must have {self.ndim} entries (got {idx})")
+        idx = (0,) * (3 - self.ndim) + idx
+        if not all(0 <= v < g for v, g in zip(idx, self.grid)):
+            raise ValueError(f"biapy_amd.prepost.LabelStitcher.add: block {idx[3 - self.ndim:]} lies outside the grid {self.grid[3 - self.ndim:]}")
+        return idx
+
+    def _extents(self, idx):
+        origin = tuple(i * b for i, b in zip(idx, self.block_shape))
+        return origin, tuple(min(o + b, s) - o for o, b, s in zip(origin, self.block_shape, self.shape))
+
+    def _allocate(self, device) -> None:
+        t = self.max_labels + 1
+        self._dev = device
+        self._nums = torch.zeros(self.nblocks, dtype=torch.int32, device=device)
+        self._offs = torch.zeros(self.nblocks + 1, dtype=torch.int64, device=device)
+        self._desc = torch.zeros((self.nblocks, 32), dtype=torch.uint8, device=device)
+        self._parent = torch.empty(t, dtype=torch.int32, device=device)
+        self._first = torch.empty(t, dtype=torch.int64, device=device)
+        self._key = torch.empty(t, dtype=torch.int64, device=device)
+        self._map = torch.zeros(t, dtype=torch.int32, device=device)
+        self._flag = torch.ones((), dtype=torch.int32, device=device)      # up until the first resolve(): apply() before it writes nothing
+        self._M = torch.full((), -1, dtype=torch.int32, device=device)
+        self._iota = torch.arange(t, dtype=torch.int64, device=device)
+        self._ws = None
+        if self.rule == "contact":
+            Z, Y, X = self.shape
+            faces = (self.grid[0] - 1) * Y * X + (self.grid[1] - 1) * Z * X + (self.grid[2] - 1) * Z * Y
+            self._max_pairs = max(1, min(faces, 2 ** 21))
+            need = int(lib.bpx_stitch_contact_workspace(*self.shape, *self.block_shape, self.max_labels, self._max_pairs))
+            if need < 0:
+                raise NotImplementedError("biapy_amd.prepost.LabelStitcher: the block faces of this grid hold 2^31 positions or more")
+            self._ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+
+    def add(self, index, labels: torch.Tensor, num=None) -> None:
+        """Registers block ``index`` (``(i, j, k)``; ``(j, k)`` in 2-D): an ``int32`` contiguous device tensor of exactly that block's extents,
+        kept alive by the stitcher and renumbered in place by ``apply()``.  ``num``: the block's label count ``n_b`` as an int, or the 0-d device
+        count of ``label(..., return_num=True)`` (read again, on the device, by every ``resolve()``); ``None`` takes ``labels.amax()`` on the
+        device at every ``resolve()``.  Nothing is read back.  Uploads the block's descriptor: NOT capturable."""
+        if labels.dtype != torch.int32:
+            raise NotImplementedError(f"biapy_amd.prepost.LabelStitcher.add works on the int32 labels of label() / watershed() (got {labels.dtype})")
+        if not labels.is_cuda:
+            raise RuntimeError("biapy_amd.prepost runs on the MI355X only (tensor is on %s); there is no CPU path" % labels.device)
+        idx = self._index(index)
+        origin, ext = self._extents(idx)
+        if labels.dim() != self.ndim or tuple(labels.shape) != ext[3 - self.ndim:]:
+            raise ValueError(f"biapy_amd.prepost.LabelStitcher.add: block {idx[3 - self.ndim:]} has extents {ext[3 - self.ndim:]} (got a tensor of shape {tuple(labels.shape)})")
+        if not labels.is_contiguous():
+            raise ValueError("biapy_amd.prepost.LabelStitcher.add: the block must be contiguous (it is renumbered in place)")
+        if isinstance(num, torch.Tensor):
+            if num.dtype != torch.int32 or num.dim() != 0 or not num.is_cuda:
+                raise ValueError(f"num must be an int or the 0-d int32 device count of label() (got a {num.dtype} tensor of shape {tuple(num.shape)} on {num.device})")
+        elif num is not None:
+            num = int(num)
+            if not 0 <= num < 2 ** 31 - 1:
+                raise ValueError(f"num must be in [0, 2^31 - 1) (got {num})")
+        if self._dev is None:
+            self._allocate(labels.device)
+        elif labels.device != self._dev:
+            raise ValueError(f"biapy_amd.prepost.LabelStitcher.add: the blocks must live on one device (got {labels.device} after {self._dev})")
+        b = (idx[0] * self.grid[1] + idx[1]) * self.grid[2] + idx[2]
+        d = L.StitchBlock(labels.data_ptr(), *origin, *ext)
+        self._desc[b].copy_(torch.frombuffer(bytearray(bytes(d)), dtype=torch.uint8))
+        if isinstance(num, int):
+            self._nums[b] = num
+        self._blocks[b] = (labels, num, origin, ext)
+
+    def resolve(self) -> torch.Tensor:
+        """Unites the labels across the blocks and numbers the merged objects: ``M`` as a 0-d ``int32`` device tensor (the same tensor at every
+        call, so a graph replay refreshes it), ``-1`` on overflow.  Every block must have been added."""
+        missing = [b for b, e in enumerate(self._blocks) if e is None]
+        if missing:
+            names = [tuple(np.unravel_index(b, self.grid))[3 - self.ndim:] for b in missing[:4]]
+            raise ValueError(f"biapy_amd.prepost.LabelStitcher.resolve: {len(missing)} of {self.nblocks} blocks have not been added (first: "
+                             + ", ".join(str(tuple(int(v) for v in n)) for n in names) + ")")
+        s, t = L.stream_ptr(), self.max_labels
+        Z, Y, X = self.shape
+        for b, (lab, num, _, _) in enumerate(self._blocks):
+            if num is None:
+                torch.amax(lab.view(-1), dim=0, out=self._nums[b])
+            elif isinstance(num, torch.Tensor):
+                self._nums[b].copy_(num)
+        L.check(lib.bpx_stitch_begin(self._nums.data_ptr(), self.nblocks, t, self._offs.data_ptr(), self._parent.data_ptr(), self._first.data_ptr(),
+                                     self._key.data_ptr(), self._flag.data_ptr(), s))
+        for b, (lab, _, origin, ext) in enumerate(self._blocks):
+            L.check(lib.bpx_stitch_first(lab.data_ptr(), *ext, *origin, Y, X, self._nums.data_ptr() + 4 * b, self._offs.data_ptr() + 8 * b, t,
+                                         self._first.data_ptr(), s))
+        if self.rule == "touch":
+            L.check(lib.bpx_stitch_shell(self._desc.data_ptr(), Z, Y, X, *self.block_shape, self.connectivity, self._nums.data_ptr(),
+                                         self._offs.data_ptr(), t, self._parent.data_ptr(), s))
+        else:
+            L.check(lib.bpx_stitch_contact(self._desc.data_ptr(), Z, Y, X, *self.block_shape, self._nums.data_ptr(), self._offs.data_ptr(), t,
+                                           *self.min_contact, self._max_pairs, self._parent.data_ptr(), self._flag.data_ptr(), self._ws.data_ptr(),
+                                           self._ws.numel(), s))
+        L.check(lib.bpx_stitch_resolve(self._parent.data_ptr(), self._first.data_ptr(), self._key.data_ptr(), self._offs.data_ptr() + 8 * self.nblocks,
+                                       t, self._flag.data_ptr(), s))
+        # the roots that hold a voxel, ranked by key: one sort over the fixed-size key table, as label_overlap ranks its pairs
+        order = torch.sort(self._key).indices
+        rank = torch.empty_like(order).scatter_(0, order, self._iota)
+        live = self._key != torch.iinfo(torch.int64).max
+        of_root = torch.where(live, rank + 1, 0).to(torch.int32)
+        torch.index_select(of_root, 0, self._parent.to(torch.int64), out=self._map)
+        self._M.copy_(torch.where(self._flag > 0, -1, live.sum()).to(torch.int32))
+        return self._M
+
+    def apply(self) -> None:
+        """Renumbers every block in place with the map of the last ``resolve()``; background (``<= 0`` or ``> n_b``) becomes 0.  After an
+        overflow - and before the first ``resolve()`` - nothing is written."""
+        if self._dev is None or any(e is None for e in self._blocks):
+            raise ValueError("biapy_amd.prepost.LabelStitcher.apply: resolve() comes first, after every block has been added")
+        s = L.stream_ptr()
+        for b, (lab, _, _, _) in enumerate(self._blocks):
+            L.check(lib.bpx_stitch_apply(lab.data_ptr(), lab.numel(), self._nums.data_ptr() + 4 * b, self._offs.data_ptr() + 8 * b, self.max_labels,
+                                         self._map.data_ptr(), self._flag.data_ptr(), s))
+
+
+def label_blocks(mask: torch.Tensor, block_shape=None, connectivity: Optional[int] = None, return_num: bool = False, max_labels: Optional[int] = None):
+    """``label`` for a binary 2-D / 3-D ``uint8`` or ``bool`` device mask of ANY size: the whole ``int32`` volume, numbered as ``label`` numbers it
+    - ``scipy.ndimage.label`` bit for bit - by labelling block after block and stitching (``LabelStitcher``, rule ``"touch"``).
+
+    ``block_shape=None`` takes the thickest Z slabs that stay below 2^31 voxels; a single slab means exactly ``label``'s launches.  Blocks
+    ``(bz, Y, X)`` - Z slabs - are labelled and renumbered in place in contiguous views of the result, with no copies; any other block shape is
+    copied in and out with torch.  With ``return_num`` the count comes back as a 0-d ``int32`` device tensor, ``-1`` when the blocks hold more than
+    ``max_labels`` labels in all (default ``min(voxels, 2**22)``; the result is then the blocks' own numbering).
+
+    Refused before anything is launched: other dtypes (``NotImplementedError``), a CPU tensor (``RuntimeError``), other ranks, block extents
+    below 1 and a connectivity outside ``1..ndim`` (``ValueError``), a block or - without ``block_shape`` - one plane ``Y * X`` of 2^31 voxels or
+    more (``NotImplementedError``)."""
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise NotImplementedError(f"biapy_amd.prepost.label_blocks works on uint8 or bool masks (got {mask.dtype}); binarize() makes one")
+    if not mask.is_cuda:
+        raise RuntimeError("biapy_amd.prepost runs on the MI355X only (tensor is on %s); there is no CPU path" % mask.device)
+    if mask.dim() not in (2, 3):
+        raise ValueError(f"biapy_amd.prepost.label_blocks takes a 2-D (Y, X) or 3-D (Z, Y, X) tensor (got {mask.dim()} dimensions)")
+    nd = mask.dim()
+    if block_shape is None:
+        plane = math.prod(mask.shape[-2:])
+        if plane >= 2 ** 31:
+            raise NotImplementedError(f"biapy_amd.prepost.label_blocks: one plane Y * X has {plane} voxels - Z slabs of 2^31 voxels or more are not supported; give a block_shape")
+        block_shape = tuple(mask.shape) if nd == 2 else (max(1, min(mask.shape[0], (2 ** 31 - 1) // max(plane, 1))),) + tuple(mask.shape[1:])
+    shape, block = _grid_shapes(mask.shape, block_shape, "label_blocks")
+    c = nd if connectivity is None else int(connectivity)
+    if not 1 <= c <= nd:
+        raise ValueError(f"connectivity must be in 1..{nd} for a {nd}-D mask (got {connectivity})")
+    if block == shape:
+        return label(mask, c, return_num)
+    st = LabelStitcher(mask.shape, block[3 - nd:], c, "touch", max_labels=max_labels)
+    m = mask.contiguous()
+    m = (m.view(torch.uint8) if m.dtype == torch.bool else m).view(shape)
+    out = torch.empty(shape, dtype=torch.int32, device=m.device)
+    nums = torch.empty(st.nblocks, dtype=torch.int32, device=m.device)
+    slabs = block[1:] == shape[1:]
+    need = int(lib.bpx_label_workspace(*block))
+    ws = torch.empty(need, dtype=torch.uint8, device=m.device)
+    pieces = []
+    for b in range(st.nblocks):
+        idx = tuple(int(v) for v in np.unravel_index(b, st.grid))
+        (z0, y0, x0), (ez, ey, ex) = st._extents(idx)
+        src = m[z0:z0 + ez, y0:y0 + ey, x0:x0 + ex]
+        if slabs:
+            dst = out[z0:z0 + ez]
+        else:
+            src, dst = src.contiguous(), torch.empty((ez, ey, ex), dtype=torch.int32, device=m.device)
+            pieces.append((dst, (z0, y0, x0)))
+        L.check(lib.bpx_label_u8(src.data_ptr(), ez, ey, ex, c, dst.data_ptr(), nums.data_ptr() + 4 * b, ws.data_ptr(), need, L.stream_ptr()))
+        st.add(idx[3 - nd:], dst if nd == 3 else dst.view(ey, ex), nums[b])
+    num = st.resolve()
+    st.apply()
+    for dst, (z0, y0, x0) in pieces:
+        out[z0:z0 + dst.shape[0], y0:y0 + dst.shape[1], x0:x0 + dst.shape[2]] = dst
+    out = out.view(mask.shape)
+    return (out, num) if return_num else out
 
 
 # ---- exact Euclidean distance transform of the mask or of the labels (csrc/edt.hip, csrc/edt_index.hip) -----------------------------------
@@ -549,7 +802,7 @@ def watershed(image: torch.Tensor, markers: torch.Tensor, mask: Optional[torch.T
 # What judges the instances the steps above produce: the reference's biapy/utils/matching.py (the StarDist matcher) builds a dense
 # (1 + max_true) x (1 + max_pred) overlap matrix in a host loop, turns it into IoU and runs scipy's linear_sum_assignment over all of it.  Here
 # the table is sparse and built on the device; only its K rows come back.  Not offered: the criteria "iot" / "iop", report_matches and
-# matching_dataset's aggregation over images; instance merging across chunk faces (it can start from label_overlap of the two faces).
+# matching_dataset's aggregation over images; instance merging across chunk faces is LabelStitcher(rule="contact"), which counts the two faces with label_overlap.
 
 def _overlap_inputs(a: torch.Tensor, b: torch.Tensor, max_pairs, what: str):
     for t in (a, b):

@@ -939,6 +939,43 @@ int bpx_label_overlap(const int32_t* a_d, const int32_t* b_d, int64_t n, int64_t
                       void* ws_d, int64_t ws_bytes, bpx_stream_t stream);
 int bpx_debug_set_overlap_per_voxel(int on); /* timing hook of bpx_label_overlap's count pass: 0 (default) = spans, run lengths and the carried run; 1 = one table insert per voxel; the same table (environment: BPX_OVERLAP_PER_VOXEL) */
 
+/* ---- stitching per-block labels into the labels of the whole volume (biapy_amd/prepost.py: LabelStitcher, label_blocks; csrc/stitch.hip, csrc/stitch_core.h) ----
+ * A volume (Z,Y,X) is cut by a regular grid of blocks (bz,by,bx), the last block of an axis may be ragged; blocks are numbered in raster order of
+ * (i,j,k).  Block b is a contiguous int32 array of its own extents with local labels 1..n_b (<= 0 or > n_b: background), n_b = nums_d[b] on the
+ * device.  offs_d[b] = exclusive prefix sum of max(n_b, 0), offs_d[nblocks] = T; the global id of (b, l) is offs_d[b] + l; parent_d[0..t_max] is a
+ * union-find over these ids (bpx_label_u8's, integer atomic min only); first_d / key_d[0..t_max] are int64.  When T > t_max flag_d becomes 1, ids
+ * above t_max take part in nothing and bpx_stitch_apply writes nothing.
+ *   bpx_stitch_begin   : offs_d from nums_d, parent = identity, first = key = INT64_MAX, *flag_d = 0.
+ *   bpx_stitch_first   : per block: first_d[g] = the smallest global linear index (z Y + y) X + x of g's voxels (64-bit atomic min, issued by run
+ *                        heads only).  num_d / off_d point at the block's entries of nums_d / offs_d.
+ *   bpx_stitch_shell   : rule "touch": every labelled shell voxel of every block is united with every labelled backward neighbour (3 / 9 / 13
+ *                        offsets at connectivity 1 / 2 / 3) that lies inside the volume in another block - face, edge and corner neighbours.
+ *   bpx_stitch_contact : rule "contact": for every pair of face-adjacent blocks A (low), B (high): c(a,b) = in-plane positions where A's last
+ *                        plane holds a and B's first plane holds b, s_A(a) / s_B(b) = positions of the plane that hold the label; a and b are
+ *                        united iff c(a,b) q >= p min(s_A(a), s_B(b)) in int64.  Unions are transitive.  More than max_pairs distinct pairs raise
+ *                        the flag.  bpx_stitch_contact_workspace: the bytes it needs, NEGATIVE when refused.
+ *   bpx_stitch_resolve : parent_d[g] = root of g, key_d[root] = min of first_d over the root's set (INT64_MAX: no voxel), the flag when
+ *                        *total_d > t_max (total_d = offs_d + nblocks).  Numbering the roots 1..M by ascending key - raster order of each object's
+ *                        first voxel, scipy.ndimage.label's numbering - is one sort over t_max + 1 keys on the caller's side.
+ *   bpx_stitch_apply   : per block, in place: labels[i] = map_d[off + labels[i]] (0 for background); nothing when *flag_d != 0.
+ * No float arithmetic: the same bits every run.  Launches fixed by the grid, nothing read back, capturable.  A block stays below 2^31 voxels, the
+ * volume need not.  Argument checks run on the host, in the order of the arguments' mention above, and set bpx_last_error. */
+typedef struct bpx_stitch_block { void* labels; int32_t z0, y0, x0, ez, ey, ex; } bpx_stitch_block; /* 32 bytes: pointer, origin, extents */
+int bpx_stitch_begin(const int32_t* nums_d, int nblocks, int t_max, int64_t* offs_d, int32_t* parent_d, int64_t* first_d, int64_t* key_d,
+                     int32_t* flag_d, bpx_stream_t stream);
+int bpx_stitch_first(const int32_t* labels_d, int ez, int ey, int ex, int z0, int y0, int x0, int Y, int X, const int32_t* num_d,
+                     const int64_t* off_d, int t_max, int64_t* first_d, bpx_stream_t stream);
+int bpx_stitch_shell(const bpx_stitch_block* blocks_d, int Z, int Y, int X, int bz, int by, int bx, int connectivity, const int32_t* nums_d,
+                     const int64_t* offs_d, int t_max, int32_t* parent_d, bpx_stream_t stream);
+int64_t bpx_stitch_contact_workspace(int Z, int Y, int X, int bz, int by, int bx, int t_max, int64_t max_pairs);
+int bpx_stitch_contact(const bpx_stitch_block* blocks_d, int Z, int Y, int X, int bz, int by, int bx, const int32_t* nums_d, const int64_t* offs_d,
+                       int t_max, int p, int q, int64_t max_pairs, int32_t* parent_d, int32_t* flag_d, void* ws_d, int64_t ws_bytes,
+                       bpx_stream_t stream);
+int bpx_stitch_resolve(int32_t* parent_d, const int64_t* first_d, int64_t* key_d, const int64_t* total_d, int t_max, int32_t* flag_d,
+                       bpx_stream_t stream);
+int bpx_stitch_apply(int32_t* labels_d, int64_t n, const int32_t* num_d, const int64_t* off_d, int t_max, const int32_t* map_d,
+                     const int32_t* flag_d, bpx_stream_t stream);
+
 /* ---- region properties of a label volume (biapy_amd/prepost.py: region_props, centroids, select_objects; csrc/regionprops.hip, csrc/regionprops_core.h) ----
  * labels (Z,Y,X) int32, contiguous, 4-byte aligned; 2-D is Z = 1; Z * Y * X < 2^31; 0 <= n_max < 2^31 - 1.  For every label l in 1..n_max:
  *   area_d[l]    = the number of voxels that carry l (int32; bpx_label_sizes' count),
