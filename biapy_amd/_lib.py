@@ -68,6 +68,12 @@ _SIGS = {
     "bpx_elastic_draw": ([C.c_uint64, C.c_uint64, _f, _f, _i, _vp, _vp, _vp], _i),
     "bpx_elastic_noise": ([C.c_uint64, _i, _i, _i, _vp, _vp, _vp], _i),
     "bpx_elastic_apply": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp], _i),
+    "bpx_n2v_boxes": ([_vp, _i, _i, _i], _i64),
+    "bpx_n2v_mask": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "bpx_n2v_loss_blocks": ([_i64], _i),
+    "bpx_n2v_loss_sums": ([_vp, _vp, _i, _i, _i64, _vp, _vp], _i),
+    "bpx_n2v_loss_finish": ([_vp, _i, _i, _i64, _vp, _vp], _i),
+    "bpx_n2v_loss_bwd": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp], _i),
     "bpx_patch_draw": ([_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp], _i),
     "bpx_patch_gather": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp], _i),
     "bpx_label_workspace": ([_i, _i, _i], _i64),
@@ -281,6 +287,11 @@ class WarpCfg(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("thr", C.c_uint64), ("enable", C.c_uint32), ("reserved", C.c_uint32), ("rot_lo", C.c_float),
                 ("rot_hi", C.c_float), ("zoom_lo", C.c_float), ("zoom_hi", C.c_float), ("shear_lo", C.c_float), ("shear_hi", C.c_float),
                 ("shift_lo", C.c_float), ("shift_hi", C.c_float)]
+
+
+class N2VCfg(C.Structure):
+    """bpx_n2v_cfg (include/biapy_amd.h)."""
+    _fields_ = [("seed", C.c_uint64), ("box", C.c_int32 * 3), ("radius", C.c_int32 * 3), ("manipulator", C.c_int32), ("sigma", C.c_float)]
 
 
 class PatchVol(C.Structure):

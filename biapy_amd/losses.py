@@ -505,3 +505,52 @@ class InstanceChannelsLoss(torch.nn.Module):
         if logits.shape != target.shape or logits.shape[1] != self.weights.numel():
             raise ValueError(f"logits {tuple(logits.shape)} / target {tuple(target.shape)} do not match the {self.weights.numel()} configured channels")
         return _ChanLossFn.apply(logits, target, self.codes, self.weights.to(logits.device))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# denoising (Noise2Void): the masked MSE on the target biapy_amd.n2v.N2VMasker writes
+# ---------------------------------------------------------------------------------------------------------------------------
+class _N2VLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target):
+        if not pred.is_cuda or not target.is_cuda:
+            raise RuntimeError("biapy_amd.losses run on the MI355X only (pred is on %s, target on %s); there is no CPU path" % (pred.device, target.device))
+        z, t = pred.contiguous().to(torch.float32), target.contiguous().to(torch.float32)
+        N, Cc = z.shape[:2]
+        vox = z[0, 0].numel()
+        nb = lib.bpx_n2v_loss_blocks(vox)
+        part = torch.empty((2, N, Cc, nb), dtype=torch.float32, device=z.device)
+        L.check(lib.bpx_n2v_loss_sums(z.data_ptr(), t.data_ptr(), N, Cc, vox, part.data_ptr(), L.stream_ptr()))
+        out = torch.empty(2, dtype=torch.float32, device=z.device)           # [the loss, 1 / sum m]
+        L.check(lib.bpx_n2v_loss_finish(part.data_ptr(), N, Cc, vox, out.data_ptr(), L.stream_ptr()))
+        ctx.save_for_backward(z, t, out)
+        ctx.cfg = (N, Cc, vox)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        z, t, out = ctx.saved_tensors
+        N, Cc, vox = ctx.cfg
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.to(torch.float32).contiguous()
+        dz = torch.empty_like(z)
+        L.check(lib.bpx_n2v_loss_bwd(z.data_ptr(), t.data_ptr(), N, Cc, vox, out.data_ptr(), g.data_ptr(), dz.data_ptr(), L.stream_ptr()))
+        return dz, None
+
+
+class N2VLoss(torch.nn.Module):
+    """The masked MSE of Noise2Void (the reference's ``n2v_loss_mse``, written from memory of it) on a LINEAR head: ``pred (B, C, ...)`` against the
+    ``target (B, 2C, ...)`` of ``biapy_amd.n2v.N2VMasker``, ``v = target[:, :C]`` the original values at the masked voxels, ``m = target[:, C:]`` the
+    mask; ``e = v - pred m``, ``loss = sum e^2 / sum m`` over the whole batch, ``d pred = g (-2 m e) / sum m``.  One stated difference: ``sum m = 0``
+    gives loss 0 and a zero gradient where the reference gives 0 / 0.  One fused pass each way (``bpx_n2v_loss_*``): per-block fp32 partials of
+    both sums in a fixed order, a one-block finish in double that also leaves ``1 / sum m`` for the backward; deterministic, no host read-back,
+    capturable.  The head stays linear: the loss sets no ``fused_head_activations``."""
+
+    def forward(self, pred, target):
+        pred = pred["pred"] if isinstance(pred, dict) else pred
+        if pred.dim() < 3 or target.dim() != pred.dim() or target.shape[0] != pred.shape[0] or target.shape[1] != 2 * pred.shape[1] \
+                or target.shape[2:] != pred.shape[2:]:
+            raise ValueError(f"pred {tuple(pred.shape)} needs a target of twice its channels (values, then masks), got {tuple(target.shape)}")
+        if not 1 <= pred.shape[1] <= 8:
+            raise NotImplementedError(f"N2VLoss takes 1 to 8 channels, got {pred.shape[1]}")
+        return _N2VLossFn.apply(pred, target)

@@ -801,6 +801,49 @@ int bpx_elastic_noise(uint64_t seed, int B, int Y, int X, const uint32_t* elasti
 int bpx_elastic_apply(const float* x_d, const void* t_d, int t_dtype, int B, int Z, int Y, int X, int C, int Ct, const uint32_t* elastic_d,
                       const float* field_d, int mode, float cval, float* x_out_d, void* t_out_d, bpx_stream_t stream);
 
+/* ---- Noise2Void: blind-spot masking and its masked MSE (biapy_amd/n2v.py states the semantics; csrc/n2v.hip, csrc/n2v_core.h) -------------
+ * x (B,Z,Y,X,C) float32, 1 <= C <= 8, B < 2^24, fewer than 2^31 voxels per sample; 2-D data is Z = 1.  The sample is cut into boxes of
+ * box[0] x box[1] x box[2] voxels (each 1..64; 1 on an axis of extent 1), n_a = ceil(dim_a / s_a) per axis, box index i = (iz n_y + iy) n_x + ix,
+ * fewer than 2^31 per sample.  Every (sample b, channel c, box i) draws on its own from Philox4x32-10 with the key (seed low ^ 0x4E32564D, seed
+ * high) and the counter words (i, (b << 4) | c | (stream << 28), q low, q high), q = the call's counter value; mulhi(r, n) = (r * n) >> 32.
+ *   stream 0: p_a = i_a s_a + mulhi(r_a, s_a) for a = z, y, x from words 0, 1, 2; any p_a >= dim_a: the box masks nothing.
+ *   stream 1: the window [max(0, p_a - R_a), min(dim_a, p_a + R_a + 1)) per axis (radius 0..15; 0 on an axis of extent 1), n its voxels, cen the
+ *     raster index of p in it.  BPX_N2V_UNIFORM_WITH_CP: k = mulhi(r0, n); _WITHOUT_CP: k = mulhi(r0, n - 1), k += (k >= cen), a one-voxel
+ *     window masks nothing; the new value is the INPUT at the window's voxel of raster index k.  _IDENTITY: the value stays.  _NORMAL_ADDITIVE:
+ *     x[p] + sigma n (one fp32 multiply, one add), n = sqrtf(-2 logf(u1)) cosf(2 pi u2), u1 = ((r0 >> 8) + 1) 2^-24, u2 = (r1 >> 8) 2^-24.
+ *   bpx_n2v_boxes : boxes per sample of a configuration on a (Z, Y, X) sample, -1 (and bpx_last_error) when the configuration is refused.
+ *   bpx_n2v_mask  : x_out = x except at the masked voxels; target (B,2C,Z,Y,X) channel-first: plane c the ORIGINAL value at the masked voxels of
+ *                   channel c and 0 elsewhere, plane C + c 1 there and 0 elsewhere; coords / sources [B][C][boxes] int32: the linear (z, y, x)
+ *                   index within the sample of the masked voxel and of its source (itself for identity / normal_additive), -1 and -1 when the
+ *                   box masks nothing.  state_d[0] is the counter (the call draws with it and adds 1), state_d[1] the value the call drew with.
+ *                   Two launches, no atomics, no workspace, nothing read back: capturable, a replay draws anew.  Out-of-place only.
+ * Argument checks, in this order, before anything is launched: null pointers, B, C, extents, the 2^31-voxel sample, the manipulator, box and radius
+ * per axis, sigma, the box count, alignment, overlap. */
+#define BPX_N2V_UNIFORM_WITH_CP 0
+#define BPX_N2V_UNIFORM_WITHOUT_CP 1
+#define BPX_N2V_IDENTITY 2
+#define BPX_N2V_NORMAL_ADDITIVE 3
+typedef struct {
+  uint64_t seed;
+  int32_t box[3];          /* z, y, x */
+  int32_t radius[3];       /* z, y, x */
+  int32_t manipulator;     /* BPX_N2V_* */
+  float sigma;             /* normal_additive only */
+} bpx_n2v_cfg;
+int64_t bpx_n2v_boxes(const bpx_n2v_cfg* cfg, int Z, int Y, int X);
+int bpx_n2v_mask(const float* x_d, int B, int Z, int Y, int X, int C, const bpx_n2v_cfg* cfg, uint64_t* state_d, float* x_out_d, float* target_d,
+                 int32_t* coords_d, int32_t* sources_d, bpx_stream_t stream);
+/* The masked MSE: pred (N,C,voxels), target (N,2C,voxels) fp32 planar, v = target[:, :C], m = target[:, C:], e = v - pred m,
+ * loss = sum e^2 / sum m over the whole batch (0 when sum m = 0).  bpx_chan_loss_*'s layout: grid (bpx_n2v_loss_blocks(voxels), N C).
+ *   bpx_n2v_loss_sums  : partials_d[2][N C][blocks]: the blocks' partial sums of e^2, then those of m; fixed order.
+ *   bpx_n2v_loss_finish: out_d[0] = the loss, out_d[1] = 1 / sum m (0 when sum m = 0), from fixed-order double sums in one block.
+ *   bpx_n2v_loss_bwd   : dpred = (gup_d[0] saved_d[1]) * (-2 (m e)), saved_d = the finish's out_d. */
+int bpx_n2v_loss_blocks(int64_t voxels);
+int bpx_n2v_loss_sums(const float* pred_d, const float* target_d, int N, int C, int64_t voxels, float* partials_d, bpx_stream_t stream);
+int bpx_n2v_loss_finish(const float* partials_d, int N, int C, int64_t voxels, float* out_d, bpx_stream_t stream);
+int bpx_n2v_loss_bwd(const float* pred_d, const float* target_d, int N, int C, int64_t voxels, const float* saved_d, const float* gup_d,
+                     float* dpred_d, bpx_stream_t stream);
+
 /* ---- random training patches from device-resident volumes (biapy_amd/sampler.py states the semantics; csrc/sampler.hip) ---------
  * V volumes stay on the device: image (Z,Y,X,C), 1 <= C <= 16, float32 / uint8 / uint16; target (Z,Y,X,Ct), 1 <= Ct <= 8, uint8 / float32;
  * 2-D data is Z = 1.  A call draws B patch origins and copies the B windows of Pz x Py x Px voxels into a (B,Pz,Py,Px,C) float32 batch
