@@ -25,15 +25,11 @@
 // more than they save (float32 balls at 1024^3: 2.56 ms against 2.95 ms, uint8: 1.39 against 1.51).  Form (b) stays selectable because it wins on
 // one measured input, one label over the whole volume (1024^3: 2.57 ms against 4.45 ms).  bpx_debug_set_intensityprops_wave picks the form
 // (environment: BPX_INTENSITYPROPS_WAVE); figures: profiles/intensityprops_timing.json, DESIGN.md section 4.
-#include <algorithm>
-
 #include "bpx_common.h"
 #include "intensityprops_core.h"
+#include "label_walk.h"
 
 namespace {
-
-#define IP_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-#define IP_RLX_WG __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
 
 template <int NL> struct IpDev {     // the global per-label arrays, the atomics at the memory side
   unsigned* area_p;
@@ -41,55 +37,30 @@ template <int NL> struct IpDev {     // the global per-label arrays, the atomics
   unsigned* kmax_p;
   long long* limbs_p;
   unsigned* nonf_p;
-  __device__ __forceinline__ void count(uint32_t r, uint32_t c) const { __hip_atomic_fetch_add(area_p + r, c, IP_RLX_AGENT); }
-  __device__ __forceinline__ void kmin(uint32_t r, uint32_t k) const { __hip_atomic_fetch_min(kmin_p + r, k, IP_RLX_AGENT); }
-  __device__ __forceinline__ void kmax(uint32_t r, uint32_t k) const { __hip_atomic_fetch_max(kmax_p + r, k, IP_RLX_AGENT); }
-  __device__ __forceinline__ void limb(uint32_t r, int j, int64_t v) const { __hip_atomic_fetch_add(limbs_p + (int64_t)r * NL + j, (long long)v, IP_RLX_AGENT); }
-  __device__ __forceinline__ void nonf(uint32_t r, int k, uint32_t c) const { __hip_atomic_fetch_add(nonf_p + (int64_t)r * 3 + k, c, IP_RLX_AGENT); }
+  __device__ __forceinline__ void count(uint32_t r, uint32_t c) const { __hip_atomic_fetch_add(area_p + r, c, LW_RLX_AGENT); }
+  __device__ __forceinline__ void kmin(uint32_t r, uint32_t k) const { __hip_atomic_fetch_min(kmin_p + r, k, LW_RLX_AGENT); }
+  __device__ __forceinline__ void kmax(uint32_t r, uint32_t k) const { __hip_atomic_fetch_max(kmax_p + r, k, LW_RLX_AGENT); }
+  __device__ __forceinline__ void limb(uint32_t r, int j, int64_t v) const { __hip_atomic_fetch_add(limbs_p + (int64_t)r * NL + j, (long long)v, LW_RLX_AGENT); }
+  __device__ __forceinline__ void nonf(uint32_t r, int k, uint32_t c) const { __hip_atomic_fetch_add(nonf_p + (int64_t)r * 3 + k, c, LW_RLX_AGENT); }
 };
 
-template <int NL> struct IpLds {     // the block's table in LDS
-  int* keys;
+template <int NL> struct IpLds : LwKeysLds {     // the block's table in LDS
   unsigned* count_p;
   unsigned* kmin_p;
   unsigned* kmax_p;
   long long* limbs_p;
   unsigned* nonf_p;
-  unsigned* claimed;
-  __device__ __forceinline__ int32_t kload(uint32_t s) const { return __hip_atomic_load(keys + s, IP_RLX_WG); }
-  __device__ __forceinline__ int32_t kcas(uint32_t s, int32_t label) const {
-    int expected = 0;
-    __hip_atomic_compare_exchange_strong(keys + s, &expected, (int)label, __ATOMIC_RELAXED, IP_RLX_WG);
-    return expected;                                  // the value before, 0 when the exchange took place
-  }
-  __device__ __forceinline__ uint32_t nclaimed() const { return __hip_atomic_load(claimed, IP_RLX_WG); }
-  __device__ __forceinline__ void claim() const { __hip_atomic_fetch_add(claimed, 1u, IP_RLX_WG); }
-  __device__ __forceinline__ void count(uint32_t s, uint32_t c) const { __hip_atomic_fetch_add(count_p + s, c, IP_RLX_WG); }
-  __device__ __forceinline__ void kmin(uint32_t s, uint32_t k) const { __hip_atomic_fetch_min(kmin_p + s, k, IP_RLX_WG); }
-  __device__ __forceinline__ void kmax(uint32_t s, uint32_t k) const { __hip_atomic_fetch_max(kmax_p + s, k, IP_RLX_WG); }
-  __device__ __forceinline__ void limb(uint32_t s, int j, int64_t v) const { __hip_atomic_fetch_add(limbs_p + s * NL + j, (long long)v, IP_RLX_WG); }
-  __device__ __forceinline__ void nonf(uint32_t s, int k, uint32_t c) const { __hip_atomic_fetch_add(nonf_p + s * 3 + k, c, IP_RLX_WG); }
+  __device__ __forceinline__ void count(uint32_t s, uint32_t c) const { __hip_atomic_fetch_add(count_p + s, c, LW_RLX_WG); }
+  __device__ __forceinline__ void kmin(uint32_t s, uint32_t k) const { __hip_atomic_fetch_min(kmin_p + s, k, LW_RLX_WG); }
+  __device__ __forceinline__ void kmax(uint32_t s, uint32_t k) const { __hip_atomic_fetch_max(kmax_p + s, k, LW_RLX_WG); }
+  __device__ __forceinline__ void limb(uint32_t s, int j, int64_t v) const { __hip_atomic_fetch_add(limbs_p + s * NL + j, (long long)v, LW_RLX_WG); }
+  __device__ __forceinline__ void nonf(uint32_t s, int k, uint32_t c) const { __hip_atomic_fetch_add(nonf_p + s * 3 + k, c, LW_RLX_WG); }
   __device__ __forceinline__ uint32_t count_of(uint32_t s) const { return count_p[s]; }
   __device__ __forceinline__ uint32_t kmin_of(uint32_t s) const { return kmin_p[s]; }
   __device__ __forceinline__ uint32_t kmax_of(uint32_t s) const { return kmax_p[s]; }
   __device__ __forceinline__ int64_t limb_of(uint32_t s, int j) const { return limbs_p[s * NL + j]; }
   __device__ __forceinline__ uint32_t nonf_of(uint32_t s, int k) const { return nonf_p[s * 3 + k]; }
 };
-
-// labels i .. i + 3, those below `end`: one 16-byte load where `vec`, 4-byte loads otherwise and at the end of the span; 0 past the end
-__device__ __forceinline__ void load4_labels(const int* __restrict__ x, int64_t i, int64_t end, bool vec, int v[OVL_VPL]) {
-  if (i + OVL_VPL <= end) {
-    if (vec) {
-      const u32x4_t w = *reinterpret_cast<const u32x4_t*>(x + i);
-      v[0] = (int)w[0]; v[1] = (int)w[1]; v[2] = (int)w[2]; v[3] = (int)w[3];
-    } else {
-      v[0] = x[i]; v[1] = x[i + 1]; v[2] = x[i + 2]; v[3] = x[i + 3];
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < OVL_VPL; ++e) v[e] = (i + e < end) ? x[i + e] : 0;
-  }
-}
 
 // the image's voxels i .. i + 3 as 32-bit words (the float's bits, the integer widened): one load of 4 elements where `vec`
 template <int DT> __device__ __forceinline__ void load4_image(const void* __restrict__ image, int64_t i, int64_t end, bool vec, uint32_t b[OVL_VPL]) {
@@ -180,7 +151,7 @@ __global__ void __launch_bounds__(64 * OVL_WAVES) ip_accumulate_kernel(IpDev<DT 
   __shared__ long long llimbs[IP_LOCAL_SLOTS * NL];
   __shared__ unsigned lnonf[IP_LOCAL_SLOTS * 3];
   __shared__ unsigned lclaimed;
-  const IpLds<NL> loc{lkeys, lcount, lkmin, lkmax, llimbs, lnonf, &lclaimed};
+  const IpLds<NL> loc{{lkeys, &lclaimed}, lcount, lkmin, lkmax, llimbs, lnonf};
   for (int s = threadIdx.x; s < IP_LOCAL_SLOTS; s += 64 * OVL_WAVES) {
     lkeys[s] = 0;
     lcount[s] = 0;
@@ -198,15 +169,15 @@ __global__ void __launch_bounds__(64 * OVL_WAVES) ip_accumulate_kernel(IpDev<DT 
   if (begin < n) {                                                      // the whole wave
     const int64_t end = begin + OVL_SPAN < n ? begin + OVL_SPAN : n;
     // spans start at multiples of 8192 voxels and a lane at a multiple of 4: aligned as the pointers are
-    const bool lvec = ((uintptr_t)labels & 15) == 0;
+    const bool lvec = lw_aligned16(labels);
     const bool ivec = ((uintptr_t)image & (F32 ? 15 : DT == BPX_U16 ? 7 : 3)) == 0;
     int v[OVL_VPL], nv[OVL_VPL] = {0, 0, 0, 0};
     uint32_t b[OVL_VPL], nb[OVL_VPL] = {0, 0, 0, 0};
-    load4_labels(labels, begin + OVL_VPL * lane, end, lvec, v);
+    lw_load4(labels, begin + OVL_VPL * lane, end, lvec, v);
     load4_image<DT>(image, begin + OVL_VPL * lane, end, ivec, b);
     for (int64_t t = begin; t < end; t += OVL_TRIP) {
       if (t + OVL_TRIP < end) {                                         // on their way while this trip is worked on
-        load4_labels(labels, t + OVL_TRIP + OVL_VPL * lane, end, lvec, nv);
+        lw_load4(labels, t + OVL_TRIP + OVL_VPL * lane, end, lvec, nv);
         load4_image<DT>(image, t + OVL_TRIP + OVL_VPL * lane, end, ivec, nb);
       }
       int32_t lab[OVL_VPL];
@@ -262,9 +233,6 @@ __global__ void __launch_bounds__(64 * OVL_WAVES) ip_accumulate_kernel(IpDev<DT 
 constexpr int IP_DEFAULT_WAVE = 0;
 int g_intensityprops_wave = IP_DEFAULT_WAVE;   // bpx_debug_set_intensityprops_wave: 1 = form (b), uniform trips reduced across the wave; 0 = form (a), the lane merge alone; same bits
 
-// 16 blocks of 256 threads per CU at most for the passes over the rows (as regionprops.hip's grid_of)
-unsigned grid_of(int64_t n) { return (unsigned)std::min<int64_t>(cdiv64(n, 256), 4096); }
-
 template <int DT> void launch(const int32_t* labels_d, const void* image_d, int64_t n, int n_max, int32_t* area_d, void* min_d, void* max_d, int64_t* limbs_d,
                               int32_t* nonfinite_d, double* sum_d, double* mean_d, hipStream_t s) {
   constexpr bool F32 = DT == BPX_F32;
@@ -275,11 +243,11 @@ template <int DT> void launch(const int32_t* labels_d, const void* image_d, int6
   uint32_t* kmax = static_cast<uint32_t*>(max_d);
   uint32_t* nonf = reinterpret_cast<uint32_t*>(nonfinite_d);
   const IpDev<NL> m{area, kmin, kmax, reinterpret_cast<long long*>(limbs_d), nonf};
-  const unsigned blocks = (unsigned)cdiv64(cdiv64(n, OVL_SPAN), OVL_WAVES);
-  ip_init_kernel<NL><<<grid_of(rows), 256, 0, s>>>(area, kmin, kmax, limbs_d, nonf, rows);
+  const unsigned blocks = lw_span_blocks(n);
+  ip_init_kernel<NL><<<lw_rows_grid(rows), 256, 0, s>>>(area, kmin, kmax, limbs_d, nonf, rows);
   if (g_intensityprops_wave) ip_accumulate_kernel<DT, true><<<blocks, 64 * OVL_WAVES, 0, s>>>(m, labels_d, image_d, n, n_max);
   else ip_accumulate_kernel<DT, false><<<blocks, 64 * OVL_WAVES, 0, s>>>(m, labels_d, image_d, n, n_max);
-  ip_finish_kernel<NL, F32><<<grid_of(rows), 256, 0, s>>>(area, kmin, kmax, limbs_d, nonf, sum_d, mean_d, rows);
+  ip_finish_kernel<NL, F32><<<lw_rows_grid(rows), 256, 0, s>>>(area, kmin, kmax, limbs_d, nonf, sum_d, mean_d, rows);
 }
 
 }  // namespace
@@ -290,10 +258,7 @@ extern "C" int bpx_intensity_props(const int32_t* labels_d, const void* image_d,
                                    void* min_d, void* max_d, int64_t* limbs_d, int32_t* nonfinite_d, double* sum_d, double* mean_d, bpx_stream_t stream) {
   const char* fn = "bpx_intensity_props";
   BPX_CHECK(labels_d && image_d && area_d && min_d && max_d && limbs_d && nonfinite_d && sum_d && mean_d, "%s: null pointer", fn);
-  BPX_CHECK(Z >= 1 && Y >= 1 && X >= 1, "%s: extents must be at least 1 (got %d x %d x %d)", fn, Z, Y, X);
-  const int64_t n = (int64_t)Z * Y * X;
-  BPX_CHECK(n < ((int64_t)1 << 31), "%s: %lld voxels: volumes of 2^31 voxels or more are not supported", fn, (long long)n);
-  BPX_CHECK(n_max >= 0 && n_max < INT32_MAX, "%s: n_max must be in [0, 2^31 - 1) (got %d)", fn, n_max);
+  LW_CHECK_VOLUME(fn, Z, Y, X, n_max);
   BPX_CHECK(image_dtype == BPX_F32 || image_dtype == BPX_U8 || image_dtype == BPX_U16, "%s: image dtype must be BPX_F32, BPX_U8 or BPX_U16 (got %d)", fn,
             image_dtype);
   const uintptr_t esize = image_dtype == BPX_F32 ? 4 : image_dtype == BPX_U16 ? 2 : 1;

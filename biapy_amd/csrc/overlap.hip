@@ -24,9 +24,8 @@
 // at one address of the global table.  What the local table does not take goes to the global one directly, and at the end of the block every
 // occupied local slot is added to the global table once: an all-background block costs one global add.
 // bpx_debug_set_overlap_per_voxel(1) selects the form with one insert per voxel, for scripts/overlap_timing.py only; the same table.
-#include <algorithm>
-
 #include "bpx_common.h"
+#include "label_walk.h"
 #include "overlap_core.h"
 
 namespace {
@@ -65,23 +64,6 @@ struct OvlLds {    // the block's table in LDS
   __device__ __forceinline__ void claim() const { __hip_atomic_fetch_add(claimed, 1u, OVL_RLX_WG); }
 };
 
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// voxels i .. i + 3 of x, those below `end`: one 16-byte load where x allows it, 4-byte loads otherwise and at the end of the span; 0 past the end
-__device__ __forceinline__ void load4(const int* __restrict__ x, int64_t i, int64_t end, bool vec, int v[OVL_VPL]) {
-  if (i + OVL_VPL <= end) {
-    if (vec) {
-      const u32x4_t w = *reinterpret_cast<const u32x4_t*>(x + i);
-      v[0] = (int)w[0]; v[1] = (int)w[1]; v[2] = (int)w[2]; v[3] = (int)w[3];
-    } else {
-      v[0] = x[i]; v[1] = x[i + 1]; v[2] = x[i + 2]; v[3] = x[i + 3];
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < OVL_VPL; ++e) v[e] = (i + e < end) ? x[i + e] : 0;
-  }
-}
-
 // clear: thread t takes slots t, t + T ... - ceil(slots / T) trips, fixed by the launch
 __global__ void __launch_bounds__(256) ovl_clear_kernel(OvlDev m, unsigned* cursor, int64_t slots, int64_t max_pairs, long long* __restrict__ keys_out,
                                                         int* __restrict__ counts_out) {
@@ -108,16 +90,16 @@ __global__ void __launch_bounds__(64 * OVL_WAVES) ovl_count_kernel(OvlDev m, con
   const int64_t begin = ((int64_t)blockIdx.x * OVL_WAVES + (threadIdx.x >> 6)) * OVL_SPAN;
   if (begin < n) {                                                      // the whole wave
     const int64_t end = begin + OVL_SPAN < n ? begin + OVL_SPAN : n;
-    const bool vec = aligned16(a) && aligned16(b);                      // spans start at multiples of 8192 voxels: aligned as the pointers are
+    const bool vec = lw_aligned16(a) && lw_aligned16(b);                // spans start at multiples of 8192 voxels: aligned as the pointers are
     OvlRun run{OVL_EMPTY, 0};
     int va[OVL_VPL], vb[OVL_VPL], na[OVL_VPL] = {0, 0, 0, 0}, nb[OVL_VPL] = {0, 0, 0, 0};
-    load4(a, begin + OVL_VPL * lane, end, vec, va);
-    load4(b, begin + OVL_VPL * lane, end, vec, vb);
+    lw_load4(a, begin + OVL_VPL * lane, end, vec, va);
+    lw_load4(b, begin + OVL_VPL * lane, end, vec, vb);
     for (int64_t t = begin; t < end; t += OVL_TRIP) {
       const uint32_t valid = (uint32_t)(end - t < OVL_TRIP ? end - t : OVL_TRIP);
       if (t + OVL_TRIP < end) {                                         // the next trip's voxels are on their way while this trip is worked on
-        load4(a, t + OVL_TRIP + OVL_VPL * lane, end, vec, na);
-        load4(b, t + OVL_TRIP + OVL_VPL * lane, end, vec, nb);
+        lw_load4(a, t + OVL_TRIP + OVL_VPL * lane, end, vec, na);
+        lw_load4(b, t + OVL_TRIP + OVL_VPL * lane, end, vec, nb);
       }
       uint64_t key[OVL_VPL];
 #pragma unroll
@@ -190,9 +172,6 @@ __global__ void __launch_bounds__(256) ovl_compact_kernel(OvlDev m, unsigned* cu
 
 int g_overlap_per_voxel = 0;   // bpx_debug_set_overlap_per_voxel: 0 (default) = spans, run lengths and the carry; 1 = one insert per voxel; same table
 
-// 16 blocks of 256 threads per CU at most for the passes that walk the table (as watershed.hip's grid_of)
-unsigned grid_of(int64_t n) { return (unsigned)std::min<int64_t>(cdiv64(n, 256), 4096); }
-
 }  // namespace
 
 extern "C" int bpx_debug_set_overlap_per_voxel(int on) { g_overlap_per_voxel = on ? 1 : 0; return 0; }
@@ -224,10 +203,10 @@ extern "C" int bpx_label_overlap(const int32_t* a_d, const int32_t* b_d, int64_t
   const OvlDev m{tkeys, tcounts, claimed};
   const uint32_t mask = (uint32_t)(slots - 1), mp = (uint32_t)max_pairs;
   long long* keys_out = reinterpret_cast<long long*>(keys_d);
-  ovl_clear_kernel<<<grid_of(slots), 256, 0, s>>>(m, cursor, slots, max_pairs, keys_out, counts_d);
-  if (g_overlap_per_voxel) ovl_count_per_voxel_kernel<<<grid_of(n), 256, 0, s>>>(m, a_d, b_d, n, mask, mp);
-  else ovl_count_kernel<<<(unsigned)cdiv64(cdiv64(n, OVL_SPAN), OVL_WAVES), 64 * OVL_WAVES, 0, s>>>(m, a_d, b_d, n, mask, mp);
-  ovl_compact_kernel<<<grid_of(slots), 256, 0, s>>>(m, cursor, slots, max_pairs, keys_out, counts_d, num_d);
+  ovl_clear_kernel<<<lw_rows_grid(slots), 256, 0, s>>>(m, cursor, slots, max_pairs, keys_out, counts_d);
+  if (g_overlap_per_voxel) ovl_count_per_voxel_kernel<<<lw_rows_grid(n), 256, 0, s>>>(m, a_d, b_d, n, mask, mp);
+  else ovl_count_kernel<<<lw_span_blocks(n), 64 * OVL_WAVES, 0, s>>>(m, a_d, b_d, n, mask, mp);
+  ovl_compact_kernel<<<lw_rows_grid(slots), 256, 0, s>>>(m, cursor, slots, max_pairs, keys_out, counts_d, num_d);
   BPX_LAUNCH_CHECK(fn);
   return 0;
 }

@@ -6,11 +6,12 @@
 // Integer atomics only (uint32 / uint64 add, relaxed): the same bits every run.  Nothing is read back, capturable; every loop is bounded by a
 // launch parameter or a constant of shapeprops_core.h / regionprops_core.h, none by what another thread does.
 //
-// bpx_region_moments: zero, accumulate, finish (the finish only with cov_d).  THE ACCUMULATE PASS is regionprops.hip's: a wave owns a span of
-// OVL_SPAN voxels and walks it in trips of 256, four voxels a lane; a head is a label change or a row start, four ballots give every lane the
-// heads of the trip, the run open at a trip's end is carried in registers; a run x0 .. x0 + L - 1 of row (z, y) contributes in closed form
-// (sp_apply_moments) into the block's 256-slot table keyed by label in LDS (13 KB), which is merged into the global rows once per occupied slot.
-// The walk is written out here a second time, not shared with regionprops.hip, so that bpx_region_props keeps its code and its bits.
+// bpx_region_moments: zero, accumulate, finish (the finish only with cov_d).  THE ACCUMULATE PASS is regionprops.hip's, the one walk of
+// label_walk.h (lw_walk_runs: spans, trips, heads, the carried run) with another emit: a run x0 .. x0 + L - 1 of row (z, y) contributes in
+// closed form (sp_apply_moments) into the block's 256-slot table keyed by label in LDS (13 KB), which is merged into the global rows once per
+// occupied slot.  An earlier version wrote the walk out here a second time for fear of what sharing would cost bpx_region_props in registers
+// and speed (its bits cannot change: integers reached by commutative atomics); inlined with its emit the shared walk costs neither kernel a
+// register, a wave per SIMD or scratch (profiles/kernel_resources.txt; timings: DESIGN.md section 4).
 //
 // bpx_region_faces: zero, count.  The same spans, trips and lanes; no runs: a lane that holds a labelled voxel also loads its voxels' neighbours
 // in the rows y - 1, y + 1 and the planes z - 1, z + 1 (16-byte loads where the pointer and X allow it; they come from cache: a volume is read
@@ -23,79 +24,46 @@
 #include <algorithm>
 
 #include "bpx_common.h"
+#include "label_walk.h"
 #include "shapeprops_core.h"
 
 namespace {
 
-#define SP_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-#define SP_RLX_WG __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
-
-// the key policy of a block's table (regionprops_core.h: rp_local_slot)
-struct SpKeys {
-  int* keys;
-  unsigned* claimed;
-  __device__ __forceinline__ int32_t kload(uint32_t s) const { return __hip_atomic_load(keys + s, SP_RLX_WG); }
-  __device__ __forceinline__ int32_t kcas(uint32_t s, int32_t label) const {
-    int expected = 0;
-    __hip_atomic_compare_exchange_strong(keys + s, &expected, (int)label, __ATOMIC_RELAXED, SP_RLX_WG);
-    return expected;                                  // the value before, 0 when the exchange took place
-  }
-  __device__ __forceinline__ uint32_t nclaimed() const { return __hip_atomic_load(claimed, SP_RLX_WG); }
-  __device__ __forceinline__ void claim() const { __hip_atomic_fetch_add(claimed, 1u, SP_RLX_WG); }
-};
-
 struct MomDev {    // the global rows
   unsigned long long* mom_p;
   __device__ __forceinline__ void mom(uint32_t r, int k, uint64_t v) const {
-    __hip_atomic_fetch_add(mom_p + (int64_t)r * SP_MOMENTS + k, (unsigned long long)v, SP_RLX_AGENT);
+    __hip_atomic_fetch_add(mom_p + (int64_t)r * SP_MOMENTS + k, (unsigned long long)v, LW_RLX_AGENT);
   }
 };
-struct MomLds : SpKeys {
+struct MomLds : LwKeysLds {
   unsigned long long* mom_p;
-  __device__ __forceinline__ void mom(uint32_t s, int k, uint64_t v) const { __hip_atomic_fetch_add(mom_p + s * SP_MOMENTS + k, (unsigned long long)v, SP_RLX_WG); }
+  __device__ __forceinline__ void mom(uint32_t s, int k, uint64_t v) const { __hip_atomic_fetch_add(mom_p + s * SP_MOMENTS + k, (unsigned long long)v, LW_RLX_WG); }
   __device__ __forceinline__ uint64_t mom_of(uint32_t s, int k) const { return mom_p[s * SP_MOMENTS + k]; }
 };
 
 template <class T> struct CntDev {    // T: unsigned long long (faces), unsigned (perimeter classes)
   T* cnt_p;
-  __device__ __forceinline__ void cnt(uint32_t r, int k, uint32_t v) const { __hip_atomic_fetch_add(cnt_p + (int64_t)r * SP_COUNTERS + k, (T)v, SP_RLX_AGENT); }
+  __device__ __forceinline__ void cnt(uint32_t r, int k, uint32_t v) const { __hip_atomic_fetch_add(cnt_p + (int64_t)r * SP_COUNTERS + k, (T)v, LW_RLX_AGENT); }
 };
-struct CntLds : SpKeys {
+struct CntLds : LwKeysLds {
   unsigned* cnt_p;
-  __device__ __forceinline__ void cnt(uint32_t s, int k, uint32_t v) const { __hip_atomic_fetch_add(cnt_p + s * SP_COUNTERS + k, v, SP_RLX_WG); }
+  __device__ __forceinline__ void cnt(uint32_t s, int k, uint32_t v) const { __hip_atomic_fetch_add(cnt_p + s * SP_COUNTERS + k, v, LW_RLX_WG); }
   __device__ __forceinline__ uint32_t cnt_of(uint32_t s, int k) const { return cnt_p[s * SP_COUNTERS + k]; }
 };
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// voxels i .. i + 3 of x, those below `end`: one 16-byte load where x allows it, 4-byte loads otherwise and at the end of the span; 0 past the end
-__device__ __forceinline__ void load4(const int* __restrict__ x, int64_t i, int64_t end, bool vec, int v[OVL_VPL]) {
-  if (i + OVL_VPL <= end) {
-    if (vec) {
-      const u32x4_t w = *reinterpret_cast<const u32x4_t*>(x + i);
-      v[0] = (int)w[0]; v[1] = (int)w[1]; v[2] = (int)w[2]; v[3] = (int)w[3];
-    } else {
-      v[0] = x[i]; v[1] = x[i + 1]; v[2] = x[i + 2]; v[3] = x[i + 3];
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < OVL_VPL; ++e) v[e] = (i + e < end) ? x[i + e] : 0;
-  }
-}
 
 // thread t zeroes the words t, t + T ...  LOOP BOUND: ceil(words / T) trips, fixed by the launch
 __global__ void __launch_bounds__(256) sp_zero_kernel(uint32_t* __restrict__ p, int64_t words) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) p[i] = 0;
 }
 
-// moments: wave w of the grid owns the voxels [w * OVL_SPAN, (w + 1) * OVL_SPAN) below n.  LOOP BOUND: OVL_SPAN / OVL_TRIP = 32 trips; the clear
-// and the flush of the block's table RP_LOCAL_SLOTS / 256 = 1 trip.  Every wave reaches both barriers, with or without voxels.
+// moments: wave w of the grid owns the voxels [w * OVL_SPAN, (w + 1) * OVL_SPAN) below n and walks their runs (label_walk.h: lw_walk_runs, 32
+// trips).  LOOP BOUND: the clear and the flush of the block's table RP_LOCAL_SLOTS / 256 = 1 trip.  Every wave reaches both barriers, with or
+// without voxels.
 __global__ void __launch_bounds__(64 * OVL_WAVES) sp_moments_kernel(MomDev m, const int* __restrict__ labels, int64_t n, int Y, int X, int n_max, RpStride stride) {
   __shared__ int lkeys[RP_LOCAL_SLOTS];
   __shared__ unsigned long long lmom[RP_LOCAL_SLOTS * SP_MOMENTS];
   __shared__ unsigned lclaimed;
-  MomLds loc;
-  loc.keys = lkeys; loc.claimed = &lclaimed; loc.mom_p = lmom;
+  const MomLds loc{{lkeys, &lclaimed}, lmom};
   for (int s = threadIdx.x; s < RP_LOCAL_SLOTS; s += 64 * OVL_WAVES) {
     lkeys[s] = 0;
 #pragma unroll
@@ -107,57 +75,8 @@ __global__ void __launch_bounds__(64 * OVL_WAVES) sp_moments_kernel(MomDev m, co
   const int64_t begin = ((int64_t)blockIdx.x * OVL_WAVES + (threadIdx.x >> 6)) * OVL_SPAN;
   if (begin < n) {                                                      // the whole wave
     const int64_t end = begin + OVL_SPAN < n ? begin + OVL_SPAN : n;
-    const bool vec = aligned16(labels);                                 // spans start at multiples of 8192 voxels: aligned as the pointer is
-    auto emit = [&](int32_t label, int32_t z, int32_t y, int32_t x0, uint32_t L) { sp_emit_moments(loc, m, label, z, y, x0, L); };
-    RpRun run{RP_NO_LABEL, 0, 0, 0, 0};
-    RpPos at = rp_pos_of((uint32_t)(begin + OVL_VPL * lane), Y, X);     // of this lane's first voxel of the trip
-    int v[OVL_VPL], nv[OVL_VPL] = {0, 0, 0, 0};
-    load4(labels, begin + OVL_VPL * lane, end, vec, v);
-    for (int64_t t = begin; t < end; t += OVL_TRIP) {
-      const uint32_t valid = (uint32_t)(end - t < OVL_TRIP ? end - t : OVL_TRIP);
-      if (t + OVL_TRIP < end) load4(labels, t + OVL_TRIP + OVL_VPL * lane, end, vec, nv);     // on its way while this trip is worked on
-      int32_t lab[OVL_VPL];
-      RpPos pos[OVL_VPL];
-      pos[0] = at;
-#pragma unroll
-      for (int e = 0; e < OVL_VPL; ++e) {
-        lab[e] = rp_label(v[e], n_max);
-        if (e) { pos[e] = pos[e - 1]; rp_step(pos[e], Y, X); }
-      }
-      int32_t prev = __shfl_up(lab[OVL_VPL - 1], 1, OVL_LANES);
-      if (lane == 0) prev = run.label;
-      uint64_t H[OVL_VPL];
-#pragma unroll
-      for (int e = 0; e < OVL_VPL; ++e)
-        H[e] = __ballot((uint32_t)(OVL_VPL * lane + e) < valid && rp_is_head(lab[e], e ? lab[e - 1] : prev, pos[e].x));
-      const bool any = (H[0] | H[1] | H[2] | H[3]) != 0;                // uniform, as everything derived from H alone
-      uint32_t first = 0, last = 0;
-      int32_t last_label = 0;
-      RpPos last_pos{0, 0, 0};
-      if (any) {
-        first = ovl_first_head(H);
-        last = ovl_last_head(H);
-#pragma unroll
-        for (int e = 0; e < OVL_VPL; ++e) {
-          const uint32_t p = (uint32_t)(OVL_VPL * lane + e);
-          if (((H[e] >> lane) & 1) && p != last && lab[e] > 0)          // a labelled run that ends inside the trip: its head's lane sends it
-            emit(lab[e], pos[e].z, pos[e].y, pos[e].x, ovl_next_head(H, lane, e, valid) - p);
-        }
-        const int le = (int)(last & (OVL_VPL - 1)), ll = (int)(last / OVL_VPL);
-        const int32_t my_label = le == 0 ? lab[0] : le == 1 ? lab[1] : le == 2 ? lab[2] : lab[3];
-        const int32_t my_z = le == 0 ? pos[0].z : le == 1 ? pos[1].z : le == 2 ? pos[2].z : pos[3].z;      // field by field: registers, not addresses
-        const int32_t my_y = le == 0 ? pos[0].y : le == 1 ? pos[1].y : le == 2 ? pos[2].y : pos[3].y;
-        const int32_t my_x = le == 0 ? pos[0].x : le == 1 ? pos[1].x : le == 2 ? pos[2].x : pos[3].x;
-        last_label = __shfl(my_label, ll, OVL_LANES);
-        last_pos = RpPos{__shfl(my_z, ll, OVL_LANES), __shfl(my_y, ll, OVL_LANES), __shfl(my_x, ll, OVL_LANES)};
-      }
-      RpRun done{RP_NO_LABEL, 0, 0, 0, 0};
-      if (rp_carry_step(run, done, any, first, last, last_label, last_pos, valid) && lane == 0) emit(done.label, done.z, done.y, done.x0, done.count);
-      rp_advance(at, stride, Y, X);
-#pragma unroll
-      for (int e = 0; e < OVL_VPL; ++e) v[e] = nv[e];
-    }
-    if (lane == 0 && run.count != 0 && run.label > 0) emit(run.label, run.z, run.y, run.x0, run.count);
+    lw_walk_runs(labels, begin, end, lane, Y, X, n_max, stride,
+                 [&](int32_t label, int32_t z, int32_t y, int32_t x0, uint32_t L) { sp_emit_moments(loc, m, label, z, y, x0, L); });
   }
   __syncthreads();
   for (int s = threadIdx.x; s < RP_LOCAL_SLOTS; s += 64 * OVL_WAVES) sp_merge_moments(loc, (uint32_t)s, m);   // the flush: every label of the block once
@@ -190,8 +109,7 @@ __global__ void __launch_bounds__(64 * OVL_WAVES) sp_faces_kernel(CntDev<unsigne
   __shared__ int lkeys[RP_LOCAL_SLOTS];
   __shared__ unsigned lcnt[RP_LOCAL_SLOTS * SP_COUNTERS];
   __shared__ unsigned lclaimed;
-  CntLds loc;
-  loc.keys = lkeys; loc.claimed = &lclaimed; loc.cnt_p = lcnt;
+  const CntLds loc{{lkeys, &lclaimed}, lcnt};
   for (int s = threadIdx.x; s < RP_LOCAL_SLOTS; s += 64 * OVL_WAVES) {
     lkeys[s] = 0;
 #pragma unroll
@@ -203,14 +121,14 @@ __global__ void __launch_bounds__(64 * OVL_WAVES) sp_faces_kernel(CntDev<unsigne
   const int64_t begin = ((int64_t)blockIdx.x * OVL_WAVES + (threadIdx.x >> 6)) * OVL_SPAN;
   if (begin < n) {                                                      // the whole wave
     const int64_t end = begin + OVL_SPAN < n ? begin + OVL_SPAN : n;
-    const bool vec = aligned16(labels);
+    const bool vec = lw_aligned16(labels);
     const bool rowvec = vec && (X & 3) == 0;                            // a lane's four voxels share a row, and the rows above and below are aligned as it is
     const int64_t plane = (int64_t)Y * X;
     RpPos at = rp_pos_of((uint32_t)(begin + OVL_VPL * lane), Y, X);
     int v[OVL_VPL], nv[OVL_VPL] = {0, 0, 0, 0};
-    load4(labels, begin + OVL_VPL * lane, end, vec, v);
+    lw_load4(labels, begin + OVL_VPL * lane, end, vec, v);
     for (int64_t t = begin; t < end; t += OVL_TRIP) {
-      if (t + OVL_TRIP < end) load4(labels, t + OVL_TRIP + OVL_VPL * lane, end, vec, nv);
+      if (t + OVL_TRIP < end) lw_load4(labels, t + OVL_TRIP + OVL_VPL * lane, end, vec, nv);
       const int64_t i0 = t + OVL_VPL * lane;                            // this lane's first voxel; voxel e exists when i0 + e < end (else its label is 0)
       int32_t lab[OVL_VPL];
       RpPos pos[OVL_VPL];
@@ -263,8 +181,7 @@ __global__ void __launch_bounds__(256) sp_perimeter_kernel(CntDev<unsigned> m, c
   __shared__ unsigned lclaimed;
   __shared__ int lab[SP_LH * SP_LW];
   __shared__ unsigned char bor[SP_BH * SP_BW];
-  CntLds loc;
-  loc.keys = lkeys; loc.claimed = &lclaimed; loc.cnt_p = lcnt;
+  const CntLds loc{{lkeys, &lclaimed}, lcnt};
   for (int s = threadIdx.x; s < RP_LOCAL_SLOTS; s += 256) {
     lkeys[s] = 0;
 #pragma unroll
@@ -294,33 +211,23 @@ __global__ void __launch_bounds__(256) sp_perimeter_kernel(CntDev<unsigned> m, c
   for (int s = threadIdx.x; s < RP_LOCAL_SLOTS; s += 256) sp_merge_counts(loc, (uint32_t)s, m);
 }
 
-// 16 blocks of 256 threads per CU at most for the passes over the rows (as regionprops.hip's grid_of)
-unsigned grid_of(int64_t n) { return (unsigned)std::min<int64_t>(cdiv64(n, 256), 4096); }
-
 }  // namespace
-
-// the refusals of bpx_region_props, in its order; `fn` names the entry
-#define SP_CHECK_VOLUME(fn, Z, Y, X, n_max)                                                                                                       \
-  BPX_CHECK((Z) >= 1 && (Y) >= 1 && (X) >= 1, "%s: extents must be at least 1 (got %d x %d x %d)", fn, Z, Y, X);                                  \
-  const int64_t n = (int64_t)(Z) * (Y) * (X);                                                                                                     \
-  BPX_CHECK(n < ((int64_t)1 << 31), "%s: %lld voxels: volumes of 2^31 voxels or more are not supported", fn, (long long)n);                       \
-  BPX_CHECK((n_max) >= 0 && (n_max) < INT32_MAX, "%s: n_max must be in [0, 2^31 - 1) (got %d)", fn, n_max)
 
 extern "C" int bpx_region_moments(const int32_t* labels_d, int Z, int Y, int X, int n_max, const int32_t* area_d, const int64_t* sums_d, int64_t* mom_d,
                                   double* cov_d, bpx_stream_t stream) {
   const char* fn = "bpx_region_moments";
   BPX_CHECK(labels_d && mom_d && (!cov_d || (area_d && sums_d)), "%s: null pointer", fn);
-  SP_CHECK_VOLUME(fn, Z, Y, X, n_max);
+  LW_CHECK_VOLUME(fn, Z, Y, X, n_max);
   BPX_CHECK((((uintptr_t)labels_d | (uintptr_t)area_d) & 3) == 0 && (((uintptr_t)sums_d | (uintptr_t)mom_d | (uintptr_t)cov_d) & 7) == 0,
             "%s: labels and area must be 4-byte aligned, sums, moments and covariance 8-byte aligned", fn);
   BPX_CHECK(sp_moments_fit(n, std::max(Z, std::max(Y, X))), "%s: %d x %d x %d: n * (Emax - 1)^2 must stay below 2^63 for the moments to fit int64", fn, Z, Y, X);
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)n_max + 1;
   const MomDev m{reinterpret_cast<unsigned long long*>(mom_d)};
-  const unsigned blocks = (unsigned)cdiv64(cdiv64(n, OVL_SPAN), OVL_WAVES);
-  sp_zero_kernel<<<grid_of(rows * SP_MOMENTS * 2), 256, 0, s>>>(reinterpret_cast<uint32_t*>(mom_d), rows * SP_MOMENTS * 2);
+  const unsigned blocks = lw_span_blocks(n);
+  sp_zero_kernel<<<lw_rows_grid(rows * SP_MOMENTS * 2), 256, 0, s>>>(reinterpret_cast<uint32_t*>(mom_d), rows * SP_MOMENTS * 2);
   sp_moments_kernel<<<blocks, 64 * OVL_WAVES, 0, s>>>(m, labels_d, n, Y, X, n_max, rp_stride(Y, X));
-  if (cov_d) sp_finish_kernel<<<grid_of(rows), 256, 0, s>>>(area_d, sums_d, mom_d, cov_d, rows);
+  if (cov_d) sp_finish_kernel<<<lw_rows_grid(rows), 256, 0, s>>>(area_d, sums_d, mom_d, cov_d, rows);
   BPX_LAUNCH_CHECK(fn);
   return 0;
 }
@@ -328,13 +235,13 @@ extern "C" int bpx_region_moments(const int32_t* labels_d, int Z, int Y, int X, 
 extern "C" int bpx_region_faces(const int32_t* labels_d, int Z, int Y, int X, int n_max, int64_t* faces_d, bpx_stream_t stream) {
   const char* fn = "bpx_region_faces";
   BPX_CHECK(labels_d && faces_d, "%s: null pointer", fn);
-  SP_CHECK_VOLUME(fn, Z, Y, X, n_max);
+  LW_CHECK_VOLUME(fn, Z, Y, X, n_max);
   BPX_CHECK(((uintptr_t)labels_d & 3) == 0 && ((uintptr_t)faces_d & 7) == 0, "%s: labels must be 4-byte aligned, faces 8-byte aligned", fn);
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)n_max + 1;
   const CntDev<unsigned long long> m{reinterpret_cast<unsigned long long*>(faces_d)};
-  const unsigned blocks = (unsigned)cdiv64(cdiv64(n, OVL_SPAN), OVL_WAVES);
-  sp_zero_kernel<<<grid_of(rows * SP_COUNTERS * 2), 256, 0, s>>>(reinterpret_cast<uint32_t*>(faces_d), rows * SP_COUNTERS * 2);
+  const unsigned blocks = lw_span_blocks(n);
+  sp_zero_kernel<<<lw_rows_grid(rows * SP_COUNTERS * 2), 256, 0, s>>>(reinterpret_cast<uint32_t*>(faces_d), rows * SP_COUNTERS * 2);
   sp_faces_kernel<<<blocks, 64 * OVL_WAVES, 0, s>>>(m, labels_d, n, Z, Y, X, n_max, rp_stride(Y, X));
   BPX_LAUNCH_CHECK(fn);
   return 0;
@@ -343,14 +250,14 @@ extern "C" int bpx_region_faces(const int32_t* labels_d, int Z, int Y, int X, in
 extern "C" int bpx_region_perimeter2d(const int32_t* labels_d, int Y, int X, int n_max, int32_t* classes_d, bpx_stream_t stream) {
   const char* fn = "bpx_region_perimeter2d";
   BPX_CHECK(labels_d && classes_d, "%s: null pointer", fn);
-  SP_CHECK_VOLUME(fn, 1, Y, X, n_max);
+  LW_CHECK_VOLUME(fn, 1, Y, X, n_max);
   BPX_CHECK((((uintptr_t)labels_d | (uintptr_t)classes_d) & 3) == 0, "%s: labels and classes must be 4-byte aligned", fn);
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)n_max + 1;
   const CntDev<unsigned> m{reinterpret_cast<unsigned*>(classes_d)};
   const int tiles_x = (int)cdiv64(X, SP_TX);                            // tiles_x * tiles_y <= n / 1024 + X / 64 + Y / 16 + 1: below 2^31
   const int64_t tiles = (int64_t)tiles_x * cdiv64(Y, SP_TY);
-  sp_zero_kernel<<<grid_of(rows * SP_COUNTERS), 256, 0, s>>>(reinterpret_cast<uint32_t*>(classes_d), rows * SP_COUNTERS);
+  sp_zero_kernel<<<lw_rows_grid(rows * SP_COUNTERS), 256, 0, s>>>(reinterpret_cast<uint32_t*>(classes_d), rows * SP_COUNTERS);
   sp_perimeter_kernel<<<(unsigned)tiles, 256, 0, s>>>(m, labels_d, Y, X, n_max, tiles_x);
   BPX_LAUNCH_CHECK(fn);
   return 0;

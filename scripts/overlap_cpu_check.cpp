@@ -55,7 +55,7 @@ static void count_span(const HostMem& loc, const HostMem& m, const std::vector<i
     for (int l = 0; l < OVL_LANES; ++l)
       for (int e = 0; e < OVL_VPL; ++e) {
         const int64_t i = t + OVL_VPL * l + e;
-        key[l][e] = i < end ? ovl_key(a[(size_t)i], b[(size_t)i]) : ovl_key(0, 0);      // load4: 0 past the end
+        key[l][e] = i < end ? ovl_key(a[(size_t)i], b[(size_t)i]) : ovl_key(0, 0);      // lw_load4: 0 past the end
       }
     uint64_t H[OVL_VPL] = {0, 0, 0, 0};
     for (int l = 0; l < OVL_LANES; ++l)

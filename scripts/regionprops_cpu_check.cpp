@@ -3,8 +3,9 @@
 // keyed by label and its merge, the init and finish rows; csrc/overlap_core.h: the head positions in a trip) in the launch sequence of
 // bpx_region_props - init; accumulate over spans of `span` voxels walked in trips of 256 by a "wave" of 64 lanes, four waves to a block, in form
 // (a) straight to the per-label arrays and in form (b) through the block's own table that is merged into them; finish - sequentially and with the
-// blocks and their waves spread over std::threads on std::atomic, checked against a brute-force loop over the voxels.  The wave's shuffle and
-// ballots are plain loops here; everything that decides a run, its coordinates or its contribution is the shared code.
+// blocks and their waves spread over std::threads on std::atomic, checked against a brute-force loop over the voxels.  The walk of a span is
+// scripts/label_walk_host.h's (shared with shapeprops_cpu_check.cpp): the wave's shuffle and ballots are plain loops there; everything that
+// decides a run, its coordinates or its contribution is the shared code.
 // Cases: random label volumes (runs of geometric length that continue across row ends), 0 / 1 / 7 / 1000 labels (1000 overflow the block's
 // table), X = 1, X one below, at and above 64, 256 and 8192, one label filling a row of 1 100 000 voxels (L x0 passes 2^32), every voxel its own
 // label, all background, labels above n_max and negative ones, n_max = 0.  Spans of OVL_SPAN and, to meet many span ends in small volumes, of
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "regionprops_core.h"
+#include "label_walk_host.h"
 
 template <class T> static void atomic_min(std::atomic<T>& a, T v) {
   T cur = a.load(std::memory_order_relaxed);
@@ -68,53 +70,12 @@ static void parallel_for(int threads, int64_t count, const std::function<void(in
 
 struct Geom { int Z, Y, X, n_max; };
 
-// one wave's span [begin, end): rp_accumulate_kernel, step for step; loc == nullptr is form (a)
+// one wave's span [begin, end): rp_accumulate_kernel's call of the walk (label_walk_host.h); loc == nullptr is form (a)
 static void accumulate_span(const HostMem* loc, const HostMem& m, const std::vector<int32_t>& labels, const Geom& g, int64_t begin, int64_t end) {
-  auto emit = [&](int32_t label, int32_t z, int32_t y, int32_t x0, uint32_t L) {
+  lw_walk_runs_host(labels, g, begin, end, [&](int32_t label, int32_t z, int32_t y, int32_t x0, uint32_t L) {
     if (loc) rp_emit(*loc, m, label, z, y, x0, L);
     else rp_emit(m, label, z, y, x0, L);
-  };
-  const RpStride stride = rp_stride(g.Y, g.X);
-  RpRun run{RP_NO_LABEL, 0, 0, 0, 0};
-  RpPos at[OVL_LANES];
-  for (int l = 0; l < OVL_LANES; ++l) at[l] = rp_pos_of((uint32_t)(begin + OVL_VPL * l), g.Y, g.X);
-  for (int64_t t = begin; t < end; t += OVL_TRIP) {
-    const uint32_t valid = (uint32_t)std::min<int64_t>(OVL_TRIP, end - t);
-    int32_t lab[OVL_LANES][OVL_VPL];
-    RpPos pos[OVL_LANES][OVL_VPL];
-    for (int l = 0; l < OVL_LANES; ++l)
-      for (int e = 0; e < OVL_VPL; ++e) {
-        const int64_t i = t + OVL_VPL * l + e;
-        lab[l][e] = rp_label(i < end ? labels[(size_t)i] : 0, g.n_max);               // load4: 0 past the end
-        if (e) { pos[l][e] = pos[l][e - 1]; rp_step(pos[l][e], g.Y, g.X); } else pos[l][0] = at[l];
-      }
-    uint64_t H[OVL_VPL] = {0, 0, 0, 0};
-    for (int l = 0; l < OVL_LANES; ++l)
-      for (int e = 0; e < OVL_VPL; ++e) {
-        const int32_t prev = e ? lab[l][e - 1] : l ? lab[l - 1][OVL_VPL - 1] : run.label;
-        if ((uint32_t)(OVL_VPL * l + e) < valid && rp_is_head(lab[l][e], prev, pos[l][e].x)) H[e] |= (uint64_t)1 << l;
-      }
-    const bool any = (H[0] | H[1] | H[2] | H[3]) != 0;
-    uint32_t first = 0, last = 0;
-    int32_t last_label = 0;
-    RpPos last_pos{0, 0, 0};
-    if (any) {
-      first = ovl_first_head(H);
-      last = ovl_last_head(H);
-      for (int l = 0; l < OVL_LANES; ++l)
-        for (int e = 0; e < OVL_VPL; ++e) {
-          const uint32_t p = (uint32_t)(OVL_VPL * l + e);
-          if (((H[e] >> l) & 1) && p != last && lab[l][e] > 0)
-            emit(lab[l][e], pos[l][e].z, pos[l][e].y, pos[l][e].x, ovl_next_head(H, l, e, valid) - p);
-        }
-      last_label = lab[last / OVL_VPL][last % OVL_VPL];
-      last_pos = pos[last / OVL_VPL][last % OVL_VPL];
-    }
-    RpRun done{RP_NO_LABEL, 0, 0, 0, 0};
-    if (rp_carry_step(run, done, any, first, last, last_label, last_pos, valid)) emit(done.label, done.z, done.y, done.x0, done.count);
-    for (int l = 0; l < OVL_LANES; ++l) rp_advance(at[l], stride, g.Y, g.X);
-  }
-  if (run.count != 0 && run.label > 0) emit(run.label, run.z, run.y, run.x0, run.count);
+  });
 }
 
 struct Props {

@@ -40,15 +40,17 @@ def test_entry_points_are_declared_exported_and_bound():
     lib_src = open(os.path.join(ROOT, "biapy_amd", "_lib.py")).read()
     assert re.search(r'\("BPX_INTENSITYPROPS_WAVE", "bpx_debug_set_intensityprops_wave"\)', lib_src)      # with the other BPX_* switches
     make = open(os.path.join(ROOT, "biapy_amd", "csrc", "Makefile")).read()
-    assert "intensityprops.hip" in make and re.search(r"^intensityprops\.o:.*intensityprops_core\.h.*regionprops_core\.h.*peaks_core\.h", make, re.M)
+    assert "intensityprops.hip" in make and re.search(r"^intensityprops\.o:.*intensityprops_core\.h.*regionprops_core\.h.*peaks_core\.h.*label_walk\.h", make, re.M)
     core = open(os.path.join(ROOT, "biapy_amd", "csrc", "intensityprops_core.h")).read()
     assert '#include "intensityprops_core.h"' in source and not re.search(r"\bIP_HD \w+ ip_\w+\(", source)      # the shared steps, not a copy
     for fn in ("ip_voxel_f32", "ip_voxel_int", "ip_fits", "ip_absorb", "ip_apply", "ip_emit", "ip_merge", "ip_round_bits", "ip_sum_rule", "ip_init_row",
                "ip_finish_row"):
         assert re.search(r"IP_HD \w+ %s\(" % fn, core) and fn in source + core, fn
     assert "peaks_okey" in core and "peaks_unokey" in core and "rp_local_slot" in core      # the key and the slot scheme are the shared ones
-    assert "atomicAdd" not in source and set(re.findall(r"__hip_atomic_(\w+)\(", source)) == {"fetch_add", "fetch_min", "fetch_max", "load",
-                                                                                                "compare_exchange_strong"}      # integer atomics only
+    walk = open(os.path.join(ROOT, "biapy_amd", "csrc", "label_walk.h")).read()       # the table's key policy and the label load are the shared ones
+    assert '#include "label_walk.h"' in source and ": LwKeysLds" in source and "lw_load4(" in source and "kcas(" not in source
+    assert "atomicAdd" not in source + walk and set(re.findall(r"__hip_atomic_(\w+)\(", source)) == {"fetch_add", "fetch_min", "fetch_max"}
+    assert set(re.findall(r"__hip_atomic_(\w+)\(", walk)) == {"fetch_add", "load", "compare_exchange_strong"}      # integer atomics only
     check = open(os.path.join(ROOT, "scripts", "intensityprops_cpu_check.cpp")).read()
     assert '#include "intensityprops_core.h"' in check and "int main()" in check and "-fsanitize=address,undefined" in check
     from biapy_amd import prepost

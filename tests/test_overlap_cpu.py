@@ -27,12 +27,13 @@ def test_entry_points_are_declared_exported_and_bound():
         assert re.search(r"^(int|int64_t) %s\(" % name, header, re.M), name
         assert name in L.EXPORTS and getattr(L.lib._raw, name) is not None, name
     make = open(os.path.join(ROOT, "biapy_amd", "csrc", "Makefile")).read()
-    assert "overlap.hip" in make and re.search(r"^overlap\.o:.*overlap_core\.h", make, re.M)
+    assert "overlap.hip" in make and re.search(r"^overlap\.o:.*overlap_core\.h.*label_walk\.h", make, re.M)
     assert L.lib._raw.bpx_overlap_workspace.restype is L.C.c_int64
     assert L.lib._raw.bpx_label_overlap.restype is L.C.c_int
     core = open(os.path.join(ROOT, "biapy_amd", "csrc", "overlap_core.h")).read()
     assert '#include "overlap_core.h"' in source and "ovl_insert(" in source and "ovl_carry_step(" in source      # the shared steps, not a copy
     assert not re.search(r"\bOVL_HD \w+ ovl_\w+\(", source)
+    assert '#include "label_walk.h"' in source and "lw_load4(" in source and "label_walk" not in core      # the label load is the shared one; the core header stays the base
     for fn in ("ovl_key", "ovl_hash", "ovl_insert", "ovl_next_head", "ovl_carry_step", "ovl_slots"):
         assert re.search(r"OVL_HD \w+ %s\(" % fn, core), fn
     check = open(os.path.join(ROOT, "scripts", "overlap_cpu_check.cpp")).read()

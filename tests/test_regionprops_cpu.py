@@ -32,14 +32,30 @@ def test_entry_points_are_declared_exported_and_bound():
     assert re.search(r"int bpx_region_props\(const int32_t\* labels_d, int Z, int Y, int X, int n_max, int32_t\* area_d, int64_t\* sums_d, "
                      r"int32_t\* bbox_d,\s+bpx_stream_t stream\);", header)
     make = open(os.path.join(ROOT, "biapy_amd", "csrc", "Makefile")).read()
-    assert "regionprops.hip" in make and re.search(r"^regionprops\.o:.*regionprops_core\.h", make, re.M)
-    core = open(os.path.join(ROOT, "biapy_amd", "csrc", "regionprops_core.h")).read()
-    assert '#include "regionprops_core.h"' in source and "rp_carry_step(" in source and "rp_is_head(" in source      # the shared steps, not a copy
+    assert "regionprops.hip" in make and re.search(r"^regionprops\.o:.*regionprops_core\.h.*label_walk\.h", make, re.M)
+    assert re.search(r"^shapeprops\.o:.*regionprops_core\.h.*label_walk\.h", make, re.M)
+    csrc = os.path.join(ROOT, "biapy_amd", "csrc")
+    core = open(os.path.join(csrc, "regionprops_core.h")).read()
+    walk = open(os.path.join(csrc, "label_walk.h")).read()
+    # the shared steps, not a copy: the one walk calls them, and both kernels that walk runs call the walk instead of writing it out
+    assert '#include "regionprops_core.h"' in source and '#include "regionprops_core.h"' in walk
+    assert "rp_carry_step(" in walk and "rp_is_head(" in walk and "ovl_first_head(" in walk
+    for name in ("regionprops.hip", "shapeprops.hip"):
+        text = source if name == "regionprops.hip" else open(os.path.join(csrc, name)).read()
+        assert '#include "label_walk.h"' in text and "lw_walk_runs(" in text, name
+        assert "rp_carry_step(" not in text and "__ballot(" not in text, name
+    everything = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp"))}
+    for definition in (r"void lw_walk_runs\(", r"int32_t kcas\(uint32_t s, int32_t label\)", r"void lw_load4\(", r"define LW_CHECK_VOLUME\("):
+        assert [f for f, text in everything.items() for _ in re.findall(definition, text)] == ["label_walk.h"], definition      # one definition each
     assert not re.search(r"\bRP_HD \w+ rp_\w+\(", source)
     for fn in ("rp_label", "rp_is_head", "rp_step", "rp_advance", "rp_apply", "rp_local_slot", "rp_merge", "rp_carry_step", "rp_finish_row"):
         assert re.search(r"RP_HD \w+ %s\(" % fn, core), fn
     check = open(os.path.join(ROOT, "scripts", "regionprops_cpu_check.cpp")).read()
     assert '#include "regionprops_core.h"' in check and "int main()" in check and "-fsanitize=address,undefined" in check
+    replay = open(os.path.join(ROOT, "scripts", "label_walk_host.h")).read()      # the host's one walk, called by both check programs
+    assert "rp_carry_step(" in replay and "ovl_first_head(" in replay and "rp_carry_step(" not in check
+    for prog in (check, open(os.path.join(ROOT, "scripts", "shapeprops_cpu_check.cpp")).read()):
+        assert '#include "label_walk_host.h"' in prog and "lw_walk_runs_host(" in prog and "ovl_first_head(" not in prog
     assert "BPX_REGIONPROPS_LOCAL" in open(os.path.join(ROOT, "biapy_amd", "_lib.py")).read()
 
 

@@ -38,7 +38,7 @@ def test_entry_points_are_declared_exported_and_bound():
     assert L._SIGS["bpx_region_faces"][0] == [vp, i, i, i, i, vp, vp]
     assert L._SIGS["bpx_region_perimeter2d"][0] == [vp, i, i, i, vp, vp]
     make = open(os.path.join(ROOT, "biapy_amd", "csrc", "Makefile")).read()
-    assert "shapeprops.hip" in make and re.search(r"^shapeprops\.o:.*shapeprops_core\.h.*regionprops_core\.h", make, re.M)
+    assert "shapeprops.hip" in make and re.search(r"^shapeprops\.o:.*shapeprops_core\.h.*regionprops_core\.h.*label_walk\.h", make, re.M)
     core = open(os.path.join(ROOT, "biapy_amd", "csrc", "shapeprops_core.h")).read()
     assert '#include "shapeprops_core.h"' in source and not re.search(r"\bSP_HD \w+ sp_\w+\(", source)      # the shared steps, not a copy
     for fn in ("sp_moments_fit", "sp_apply_moments", "sp_cov_numerator", "sp_cov_entry", "sp_finish_row", "sp_face", "sp_lane_faces", "sp_count_step",
