@@ -12,15 +12,20 @@ Public surface mirrors the reference names for this path:
   biapy_amd.augment.DeviceAugmenter               <- the flips / rot90 / brightness / contrast / noise / cutout subset of biapy.data.generators.augmentors
   biapy_amd.sampler.DevicePatchSampler / DevicePatchLoader <- random patch extraction (DATA.EXTRACT_RANDOM_PATCH, probability map) from resident volumes
   biapy_amd.n2v.N2VMasker (also biapy_amd.N2VMasker) + losses.N2VLoss <- the Noise2Void blind-spot manipulation of the denoising generator and n2v_loss_mse
+  biapy_amd.targets.InstanceTargets (also biapy_amd.InstanceTargets) + prepost.instance_targets <- the instance-segmentation channel targets (F, C, D, Dc, H, V, Z) from id patches, on the device
   biapy_amd.losses / prepost / tta               <- biapy.engine.metrics, biapy.data.norm + semantic_seg Otsu, biapy.data.post_processing TTA
 """
 __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # N2VMasker loads the HIP library on first use, as every other module of the package does on its own import
+    # N2VMasker and InstanceTargets load the HIP library on first use, as every other module of the package does on its own import
     if name == "N2VMasker":
         from .n2v import N2VMasker
 
         return N2VMasker
+    if name == "InstanceTargets":
+        from .targets import InstanceTargets
+
+        return InstanceTargets
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -74,6 +74,10 @@ _SIGS = {
     "bpx_n2v_loss_sums": ([_vp, _vp, _i, _i, _i64, _vp, _vp], _i),
     "bpx_n2v_loss_finish": ([_vp, _i, _i, _i64, _vp, _vp], _i),
     "bpx_n2v_loss_bwd": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp], _i),
+    "bpx_itarget_records_bytes": ([_i, _i], _i64),
+    "bpx_itarget_ids": ([_vp, _i, _i64, _i, _vp, _vp, _vp], _i),
+    "bpx_itarget_stats": ([_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp], _i),
+    "bpx_itarget_pack": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_uint32, _i, _i, _i, _i, _i, _f, C.POINTER(C.c_double), _vp, _vp], _i),
     "bpx_patch_draw": ([_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp], _i),
     "bpx_patch_gather": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp], _i),
     "bpx_label_workspace": ([_i, _i, _i], _i64),

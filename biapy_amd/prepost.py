@@ -570,7 +570,7 @@ def label_blocks(mask: torch.Tensor, block_shape=None, connectivity: Optional[in
 # marker-controlled watershed (scipy.ndimage.distance_transform_edt / the edt package on the host there), and - with the nearest background
 # voxel beside the distance - skimage.segmentation.expand_labels and the reference's "Voronoi on mask" step.  Not offered: indices for
 # label_distance, SciPy's choice among equally near voxels (the raster-first one is returned), a black border, more than 3 dimensions, 2^31
-# voxels or more, multi-GPU slabs and any normalisation of the D channel - that stays with the caller.  The watershed is watershed() below.
+# voxels or more and multi-GPU slabs.  The D channel's normalisation is instance_targets() below (biapy_amd.targets); the watershed is watershed().
 
 def _edt(t: torch.Tensor, what: str, label_mode: bool, sampling, squared: bool, distances: bool = True, indices: bool = False, invert: bool = False):
     """The distances (``indices=False``: through ``bpx_edt``, as ever), or ``(distances or None, linear indices)`` through ``bpx_edt_index``."""
@@ -998,6 +998,30 @@ def centroids(labels: torch.Tensor, num=None) -> torch.Tensor:
     """The centroids of the labels ``1..N`` as a ``float64`` device tensor of shape ``(N, ndim)`` - ``region_props(labels, num).centroid[1:]``,
     what the detection workflow takes from its labelled blobs; NaN for a label that no voxel carries."""
     return region_props(labels, num).centroid[1:]
+
+
+def instance_targets(labels: torch.Tensor, channels=("F", "C", "D"), num=None, **options) -> torch.Tensor:
+    """The instance-segmentation channel targets of ONE 2-D ``(Y, X)`` or 3-D ``(Z, Y, X)`` ``int32`` label tensor as a ``float32`` device tensor
+    ``(Ct, [Z,] Y, X)`` - the offline target generation the reference does with SciPy on the host, and ``biapy_amd.targets.InstanceTargets`` at a
+    batch of one: its channels (``F``, ``C``, ``D``, ``Dc``, ``H``, ``V``, ``Z``), its ``options`` (``contour_mode``, ``contour_connectivity``,
+    ``f_excludes_contour``, ``d_norm``, ``d_clip``, ``sampling``), its arithmetic and its refusals; the semantics are stated there.  ``num`` as for
+    ``region_props`` (an int, the 0-d tensor of ``label(..., return_num=True)``, or ``None``, which reads ``labels.max()`` back); it must stay
+    below 2^24.  A label ``<= 0`` or ``> num`` is background.  Known limit: the records pass reads the distances of a run (the voxels of one
+    label along a row) through one lane, so a volume whose rows stay inside one label for thousands of voxels pays for it; it is sized for and
+    measured at training patches, not at such volumes."""
+    from .targets import InstanceTargets, _check_channels
+
+    if "augment" in options or "n_max" in options:
+        raise ValueError("biapy_amd.prepost.instance_targets takes num= and no augmenter")
+    channels = _check_channels(channels)
+    n_max = None if num is None else int(num)
+    if n_max is not None and n_max < 0:
+        raise ValueError(f"num must not be negative (got {n_max})")
+    _label_volume(labels, "instance_targets")
+    lab = _labels(labels, "instance_targets").contiguous()
+    if n_max is None:
+        n_max = max(int(lab.max()), 0)
+    return InstanceTargets(channels, n_max=n_max, **options)(None, lab[None])[1][0]
 
 
 def select_objects(labels: torch.Tensor, keep: torch.Tensor, relabel: bool = False, return_num: bool = False):

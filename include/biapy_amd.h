@@ -844,6 +844,51 @@ int bpx_n2v_loss_finish(const float* partials_d, int N, int C, int64_t voxels, f
 int bpx_n2v_loss_bwd(const float* pred_d, const float* target_d, int N, int C, int64_t voxels, const float* saved_d, const float* gup_d,
                      float* dpred_d, bpx_stream_t stream);
 
+/* ---- instance-segmentation training targets from id patches (biapy_amd/targets.py states the semantics; csrc/itarget.hip, csrc/itarget_core.h) ----
+ * A batch of B samples (Z,Y,X), fewer than 2^31 voxels each, 1 <= B <= 65535, 0 <= n_max < 2^24, B (n_max + 1) < 2^31; 2-D data is Z = 1, ndim = 2.
+ * Everything is per sample: the record of (sample b, id l) is row b (n_max + 1) + l.
+ *   bpx_itarget_ids   : ids_d[i] = the id value i counts for: the value itself when it is an integer in 0..n_max, else 0 (background) and
+ *                       *faults_d += 1 (NaN, +-inf, a fraction, a negative value, a value above n_max).  dtype BPX_F32, BPX_U8 (any address) or
+ *                       BPX_I32.  One launch; the counter is only ever added to, the caller clears it.
+ *   bpx_itarget_stats : the records of the batch from the ids of bpx_itarget_ids and their distances dist_d (B,Z,Y,X) float32 - bpx_edt per
+ *                       sample in label mode, the float32 result.  Per present id: the area A, the coordinate sums S_a, the INCLUSIVE box lo_a, hi_a,
+ *                       dmax = the largest d (+inf where the instance fills its sample), then the centroid c_a = double(S_a) / double(A) in the
+ *                       sums' place and, with want_rc, rcmax = the largest rc over the instance,
+ *                         rc = float32(sqrt(((dz sz)^2 + (dy sy)^2) + (dx sx)^2)), d_a = double(p_a) - c_a, fp64, in this order, no FMA;
+ *                       (sz, sy, sx) = sampling, 1 when NULL.  Both maxima are taken on the uint32 bits of the non-negative float32, whose order
+ *                       they keep.  Integer atomics only (add, min, max): the same bits every run.  Launches: init, accumulate, finish, and the
+ *                       rcmax accumulate with want_rc.  records_d: bpx_itarget_records_bytes(B, n_max) bytes, 8-byte aligned (-1: refused).
+ *   bpx_itarget_pack  : target (B,channels,Z,Y,X) float32 channel-first; channel i is BPX_ITARGET_* code (codes >> 4 i) & 15.  l = the voxel's id,
+ *                       `edge` = an in-volume neighbour within generate_binary_structure(ndim, connectivity) carries another id, contour = edge
+ *                       (BPX_ITARGET_THICK) or edge and l > 0 (BPX_ITARGET_INNER).  Every channel but C is 0 where l == 0.
+ *                         F : 1; with BPX_ITARGET_F_EXCLUDES_C 0 where contour.          C : 1 where contour.
+ *                         D : d / dmax[l] (one fp32 division), 1 where d is +inf; with BPX_ITARGET_D_RAW d itself, with BPX_ITARGET_D_CLIP too
+ *                             min(d, d_clip).                                             Dc: 1.0f - rc / rcmax[l] (two fp32 operations), 1 when rcmax == 0.
+ *                         H, V, Z (axes x, y, z): o = double(p_a) - c_a, e = o >= 0 ? double(hi_a) - c_a : c_a - double(lo_a),
+ *                             float32(o / e), 0 when e == 0.  Z needs ndim = 3.
+ *                       One launch, 64-bit offsets into the target (its element count may pass 2^31), 16-byte stores where a plane's address allows.
+ * Argument checks, in this order, before anything is launched, setting bpx_last_error: null pointers, extents, the voxel count, B, n_max (and the
+ * record count), the channel count and codes, connectivity, the contour mode, the flags and d_clip, sampling, alignment, overlap. */
+#define BPX_ITARGET_F 1
+#define BPX_ITARGET_C 2
+#define BPX_ITARGET_D 3
+#define BPX_ITARGET_DC 4
+#define BPX_ITARGET_H 5
+#define BPX_ITARGET_V 6
+#define BPX_ITARGET_Z 7
+#define BPX_ITARGET_THICK 0
+#define BPX_ITARGET_INNER 1
+#define BPX_ITARGET_F_EXCLUDES_C 1
+#define BPX_ITARGET_D_RAW 2
+#define BPX_ITARGET_D_CLIP 4
+int64_t bpx_itarget_records_bytes(int B, int n_max);
+int bpx_itarget_ids(const void* t_d, int dtype, int64_t n, int n_max, int32_t* ids_d, int32_t* faults_d, bpx_stream_t stream);
+int bpx_itarget_stats(const int32_t* ids_d, const float* dist_d, int B, int Z, int Y, int X, int n_max, const double* sampling, int want_rc,
+                      void* records_d, bpx_stream_t stream);
+int bpx_itarget_pack(const int32_t* ids_d, const float* dist_d, const void* records_d, int B, int Z, int Y, int X, int n_max, uint32_t codes,
+                     int channels, int ndim, int connectivity, int mode, int flags, float d_clip, const double* sampling, float* target_d,
+                     bpx_stream_t stream);
+
 /* ---- random training patches from device-resident volumes (biapy_amd/sampler.py states the semantics; csrc/sampler.hip) ---------
  * V volumes stay on the device: image (Z,Y,X,C), 1 <= C <= 16, float32 / uint8 / uint16; target (Z,Y,X,Ct), 1 <= Ct <= 8, uint8 / float32;
  * 2-D data is Z = 1.  A call draws B patch origins and copies the B windows of Pz x Py x Px voxels into a (B,Pz,Py,Px,C) float32 batch
