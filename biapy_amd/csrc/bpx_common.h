@@ -267,6 +267,8 @@ template <> __device__ __forceinline__ f32x4_t mfma_step<float>(const u32x4_t& a
 
 __host__ __device__ __forceinline__ int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) / b; }
+// blocks of a grid-stride launch of 256 threads over `total` items: one item per thread up to 256 * 16 blocks (16 per CU), strides beyond
+inline int grid_for(int64_t total) { const int64_t b = cdiv64(total, 256); return (int)(b < 256 * 16 ? b : 256 * 16); }
 
 static inline size_t dtype_size(int dt) {
   switch (dt) {

@@ -8,9 +8,9 @@
 // Logits are planar fp32 (N, C, voxels) - what bpx_head_fwd writes.  Class mode: target (N, 1, voxels) class ids as floats, p = softmax over the
 // channels; channel mode: target (N, C, voxels), p = sigmoid per channel.  The kernels are instantiated per channel count: the 3 C + 4 sums of a
 // thread and the C loaded planes of a 4-voxel group are registers with compile-time indices (no scratch: profiles/kernel_resources.txt).
-#include <algorithm>
-
-#include "bpx_common.h"
+// The wave sum, the four-wave hand-over, the sigmoid / BCE terms, the finish's row sum and the block rule are loss_parts.h's, shared with the plain
+// losses (seg, per-channel, softmax CE: plain_losses.hip) and the N2V loss (n2v.hip).
+#include "loss_parts.h"
 
 constexpr int DICE_MAXC = 8, DICE_ROW = 3 * DICE_MAXC + 4;
 // columns of a row: I[8], P[8], T[8], {sum w nll | sum bce}, sum w, labels outside [0, C) other than ignore_index, counted voxels
@@ -58,29 +58,17 @@ __device__ __forceinline__ void dice_class_voxel(const float (&z)[C], float lab,
   }
 }
 
-__device__ __forceinline__ float dice_sigmoid(float z, float& en) {
-  en = expf(-fabsf(z));
-  const float r = 1.f / (1.f + en);
-  return z >= 0.f ? r : en * r;
-}
-
 template <int C>
 __device__ __forceinline__ void dice_chan_voxel(const float (&z)[C], const float (&t)[C], bool with_ce, DiceAcc<C>& a) {
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     float en;
-    const float p = dice_sigmoid(z[c], en);
+    const float p = sigmoid_rcp(z[c], en);
     a.I[c] += p * t[c];
     a.P[c] += p;
     a.T[c] += t[c];
-    if (with_ce) a.ce += (fmaxf(z[c], 0.f) - z[c] * t[c]) + log1pf(en);
+    if (with_ce) a.ce += bce_less_log(z[c], t[c]) + log1pf(en);
   }
-}
-
-__device__ __forceinline__ float dice_wave_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
 }
 
 // VEC: voxels % 4 == 0 and 16-byte aligned pointers - a thread walks groups of four voxels with one 16-byte load per plane; otherwise one voxel
@@ -141,23 +129,18 @@ __global__ void __launch_bounds__(256) dice_sums_kernel(const float* __restrict_
     }
   }
   __shared__ float red[4][DICE_ROW];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float row[DICE_ROW];
 #pragma unroll
-  for (int c = 0; c < DICE_MAXC; ++c) {
-    float vi = 0.f, vp = 0.f, vt = 0.f;
-    if (c < C) { vi = dice_wave_sum(a.I[c < C ? c : 0]); vp = dice_wave_sum(a.P[c < C ? c : 0]); vt = dice_wave_sum(a.T[c < C ? c : 0]); }
-    if (lane == 0) { red[wave][DR_I + c] = vi; red[wave][DR_P + c] = vp; red[wave][DR_T + c] = vt; }
+  for (int c = 0; c < DICE_MAXC; ++c) {     // the columns of the channels beyond C are zeros
+    row[DR_I + c] = row[DR_P + c] = row[DR_T + c] = 0.f;
+    if (c < C) { row[DR_I + c] = wave_sum(a.I[c < C ? c : 0]); row[DR_P + c] = wave_sum(a.P[c < C ? c : 0]); row[DR_T + c] = wave_sum(a.T[c < C ? c : 0]); }
   }
-  {
-    const float v0 = dice_wave_sum(a.ce), v1 = dice_wave_sum(a.w), v2 = dice_wave_sum(a.faults), v3 = dice_wave_sum(a.cnt);
-    if (lane == 0) { red[wave][DR_CE] = v0; red[wave][DR_W] = v1; red[wave][DR_FAULT] = v2; red[wave][DR_CNT] = v3; }
-  }
-  __syncthreads();
-  if (threadIdx.x < DICE_ROW)
-    part[((size_t)n * gridDim.x + blockIdx.x) * DICE_ROW + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  row[DR_CE] = wave_sum(a.ce); row[DR_W] = wave_sum(a.w); row[DR_FAULT] = wave_sum(a.faults); row[DR_CNT] = wave_sum(a.cnt);
+  four_wave_hand_over(row, red);
+  if (threadIdx.x < DICE_ROW) part[((size_t)n * gridDim.x + blockIdx.x) * DICE_ROW + threadIdx.x] = four_wave_sum_pairs(red, threadIdx.x);
 }
 
-// One workgroup.  Per sample: the sample's rows, eight row lanes x 32 columns in double, then the eight lanes in sequence - a fixed order.  Dice per
+// One workgroup.  Per sample: the sample's rows through rows_sum_8x32 (loss_parts.h) - a fixed order.  Dice per
 // class from the batch totals (batch_dice) or from every sample's totals; M = the number of dice terms averaged.
 //   a0 = w_dice (2 I + s) / (M (U + s)^2),  a1 = a0 - 2 w_dice / (M (U + s)),  U = P + T
 //   loss = w_ce CE + w_dice (1 - sum dice / M), a term whose weight is 0 is not formed
@@ -167,7 +150,7 @@ __global__ void __launch_bounds__(256) dice_finish_kernel(const float* __restric
   __shared__ double red[8][32];
   __shared__ double S[32];
   __shared__ double dsh[DICE_MAXC];
-  const int tid = threadIdx.x, k = tid % 32, lr = tid / 32;
+  const int tid = threadIdx.x;
   const double M = batch_dice ? (double)C : (double)N * C;
   double tot = 0., dice_sum = 0.;
   auto terms = [&](int g) {           // threads 0..C-1: the dice term and the coefficients of group g from S
@@ -180,14 +163,8 @@ __global__ void __launch_bounds__(256) dice_finish_kernel(const float* __restric
     dsh[tid] = num / den;
   };
   for (int n = 0; n < N; ++n) {
-    double a = 0.;
-    if (k < DICE_ROW)
-      for (int r = lr; r < nb; r += 8) a += (double)part[((size_t)n * nb + r) * DICE_ROW + k];
-    red[lr][k] = a;
-    __syncthreads();
+    const double v = rows_sum_8x32<DICE_ROW>(part + (size_t)n * nb * DICE_ROW, nb, red);
     if (tid < DICE_ROW) {
-      double v = 0.;
-      for (int q = 0; q < 8; ++q) v += red[q][tid];
       S[tid] = v;
       tot += v;
     }
@@ -246,7 +223,7 @@ __device__ __forceinline__ void dice_class_bwd_voxel(const float (&z)[C], float 
 
 __device__ __forceinline__ float dice_chan_bwd(float z, float t, float a0, float a1, float kce, float g) {
   float en;
-  const float p = dice_sigmoid(z, en);
+  const float p = sigmoid_rcp(z, en);
   const float A = a0 + t * (a1 - a0);
   return g * (A * (p * (1.f - p)) + kce * (p - t));
 }
@@ -329,7 +306,7 @@ static inline bool dice_aligned16(const void* p) { return (reinterpret_cast<uint
     default: DICE_DISPATCH_MODE(KERNEL, 8, __VA_ARGS__); break;     \
   }
 
-extern "C" int bpx_dice_blocks(int64_t voxels) { return (int)std::min<int64_t>(std::max<int64_t>(1, cdiv64(voxels, 1024)), 512); }
+extern "C" int bpx_dice_blocks(int64_t voxels) { return loss_blocks(voxels); }
 extern "C" int bpx_dice_row(void) { return DICE_ROW; }
 
 extern "C" int bpx_dice_sums(const float* logits_d, const float* target_d, int N, int C, int64_t voxels, int class_mode, int ignore_index,

@@ -11,13 +11,12 @@
 // Random numbers: Philox4x32-10, key (seed low ^ 0x4E32564D, seed high), counter words (box, (sample << 4) | channel | (stream << 28), counter
 // low, counter high); stream 0 the position, stream 1 the replacement.
 //
-// Loss: loss = sum e^2 / sum m over the whole batch, e = v - pred m, v = target[:, :C], m = target[:, C:]; bpx_chan_loss_*'s layout: grid (blocks,
-// N C), fp32 partials of both sums per block in a fixed order, a one-block finish in double that also stores 1 / sum m for the backward.
+// Loss: loss = sum e^2 / sum m over the whole batch, e = v - pred m, v = target[:, :C], m = target[:, C:]; the per-channel loss's layout (plain_losses.hip) from the
+// shared pieces of loss_parts.h: grid (blocks, N C), fp32 partials of both sums per block in a fixed order, a one-block finish in double
+// (strided_sums_256) that also stores 1 / sum m for the backward.
 #include <math.h>
 
-#include <algorithm>
-
-#include "bpx_common.h"
+#include "loss_parts.h"
 #include "n2v_core.h"
 
 namespace {
@@ -90,47 +89,31 @@ __global__ void __launch_bounds__(256) n2v_loss_sums_kernel(const float* __restr
   const float* pp = pred + (size_t)plane * vox;
   const float* vp = target + ((size_t)n * 2 * C + c) * vox;
   const float* mp = vp + (size_t)C * vox;
-  float se = 0.f, sm = 0.f;
+  float s[2] = {0.f, 0.f};                      // sum e^2, sum m
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < vox; i += (int64_t)gridDim.x * 256) {
     const float m = mp[i], e = vp[i] - pp[i] * m;
-    se += e * e;
-    sm += m;
+    s[0] += e * e;
+    s[1] += m;
   }
-#pragma unroll
-  for (int k = 1; k < 64; k <<= 1) {
-    se += __shfl_xor(se, k, 64);
-    sm += __shfl_xor(sm, k, 64);
-  }
-  __shared__ float red[2][4];
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = se;
-    red[1][threadIdx.x >> 6] = sm;
-  }
-  __syncthreads();
+  s[0] = wave_sum(s[0]);
+  s[1] = wave_sum(s[1]);
+  __shared__ float red[4][2];
+  four_wave_hand_over(s, red);
   if (threadIdx.x == 0) {
-    part[(size_t)plane * gridDim.x + blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    part[((size_t)gridDim.y + plane) * gridDim.x + blockIdx.x] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    part[(size_t)plane * gridDim.x + blockIdx.x] = four_wave_sum_seq(red, 0);
+    part[((size_t)gridDim.y + plane) * gridDim.x + blockIdx.x] = four_wave_sum_seq(red, 1);
   }
 }
 
 // out[0] = sum e^2 / sum m, out[1] = 1 / sum m (both 0 when nothing is masked): fixed-order double sums of the count partials of either kind
 __global__ void __launch_bounds__(256) n2v_loss_finish_kernel(const float* __restrict__ part, int64_t count, float* __restrict__ out) {
   __shared__ double red[2][256];
-  for (int k = 0; k < 2; ++k) {
-    double s = 0.;
-    for (int64_t q = threadIdx.x; q < count; q += 256) s += (double)part[(size_t)k * count + q];
-    red[k][threadIdx.x] = s;
-  }
-  __syncthreads();
+  double s[2];                                  // sum e^2, sum m
+  strided_sums_256(count, [&](int k, int64_t q) { return part[(size_t)k * count + q]; }, red, s);
   if (threadIdx.x == 0) {
-    double se = 0., sm = 0.;
-    for (int q = 0; q < 256; ++q) {
-      se += red[0][q];
-      sm += red[1][q];
-    }
-    const bool any = sm > 0.;
-    out[0] = any ? (float)(se / sm) : 0.f;
-    out[1] = any ? (float)(1. / sm) : 0.f;
+    const bool any = s[1] > 0.;
+    out[0] = any ? (float)(s[0] / s[1]) : 0.f;
+    out[1] = any ? (float)(1. / s[1]) : 0.f;
   }
 }
 
@@ -213,7 +196,7 @@ extern "C" int bpx_n2v_mask(const float* x_d, int B, int Z, int Y, int X, int C,
   return 0;
 }
 
-extern "C" int bpx_n2v_loss_blocks(int64_t voxels) { return (int)std::min<int64_t>(std::max<int64_t>(1, cdiv64(voxels, 1024)), 512); }
+extern "C" int bpx_n2v_loss_blocks(int64_t voxels) { return loss_blocks(voxels); }
 
 static int n2v_loss_args(const char* fn, int N, int C, int64_t voxels) {
   BPX_CHECK(N > 0 && C >= 1 && C <= N2V_MAX_CHANNELS && voxels > 0, "%s: bad extents (N %d, C %d, voxels %lld; 1..%d channels)", fn, N, C, (long long)voxels,

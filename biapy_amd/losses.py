@@ -5,7 +5,8 @@ channel is ``BCEWithLogitsLoss``), ``DiceLoss`` (:726-762, ``batch_dice=True``, 
 binary case: ``w_ce * BCE + w_dice * (1 - Dice)``) and ``jaccard_index`` (:138-232, threshold 0.5).  One streaming HIP kernel
 produces every sum the four need (``bpx_seg_loss_sums``); the backward is one more pass (``bpx_seg_loss_bwd``).  Round 6: the multi-class
 case of ``CrossEntropyLoss_wrapper`` (``num_classes > 2``: softmax cross entropy over 3..8 class channels with ``ignore_index`` and the "manual"
-class weights) and the confusion counts of the multi-class IoU run on the device too (``bpx_softmax_ce_*``).
+class weights) and the confusion counts of the multi-class IoU run on the device too (``bpx_softmax_ce_*``).  These two and the per-channel losses
+(``bpx_chan_loss_*``) are csrc/plain_losses.hip; the pieces every loss kernel shares are csrc/loss_parts.h.
 
 Dice and Dice + CE on heads of 2..8 channels (``bpx_dice_*``, csrc/losses.hip: sums, finish, backward - three launches per loss call whatever N,
 ``batch_dice`` or the CE weight are, no host read-back).  Logits are ``(N, C, *space)`` fp32; ``C = 1`` keeps the one-channel path above, more than

@@ -22,7 +22,7 @@ from norm_bounds import MODES, U64, exact_row, same_bits, sums_reference, trunc_
 ALL = ("f32", "bf16", "f16")
 BWD_MODES = ("f32", "bf16", "mix16")
 NA_BLOCKS = 512             # elementwise.hip: blocks (= partial-sum slots) per sample, upper bound
-GRID_CAP = 256 * 16         # elementwise.hip grid_for: min(cdiv(total, 256), 256 * 16) blocks
+GRID_CAP = 256 * 16         # bpx_common.h grid_for: min(cdiv(total, 256), 256 * 16) blocks
 UPS_BWD_CAP = 256           # bpx_upsample_c1_blocks: min(max(1, cdiv(voxels_in, 2048)), 256)
 
 

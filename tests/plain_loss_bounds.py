@@ -1,5 +1,5 @@
 """The one-channel BCE / Dice / Dice + CE loss (bpx_seg_loss_*), the per-channel instance losses (bpx_chan_loss_*) and the multi-class cross entropy
-(bpx_softmax_ce_*) of biapy_amd/losses.py and csrc/elementwise.hip in float64 - value, closed-form gradient, the sums, the counts - and per-element
+(bpx_softmax_ce_*) of biapy_amd/losses.py and csrc/plain_losses.hip (shared pieces: csrc/loss_parts.h) in float64 - value, closed-form gradient, the sums, the counts - and per-element
 bounds of what the device may differ by, derived from the kernels' operations in the manner of tests/loss_bounds.py:
 
     |got - ref| <= (error of every fp32 term pushed through on absolute values) + chain 2^-24 sum|terms| + 2^-24 |ref| (+ a floor of 2^-126)
@@ -245,7 +245,7 @@ CHAN_PLANT_MIN_VOX = 64
 
 
 def chan_codes(spec) -> int:
-    """code[c] = kind | act << 2 as csrc/elementwise.hip reads it."""
+    """code[c] = kind | act << 2 as csrc/plain_losses.hip reads it."""
     kind, act = dict(bce=0, mse=1, l1=2), dict(linear=0, tanh=1, sigmoid=2)
     return sum((kind[k] | ((act[a] if k != "bce" else 0) << 2)) << (4 * i) for i, (k, a) in enumerate(spec))
 
