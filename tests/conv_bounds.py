@@ -153,6 +153,22 @@ def fwd_reference(x, w, bias, kind, rec=None, act=0, sc=None, wsc=None, bsc=None
     return ref, finish(ref, M, E, K, kind), pre
 
 
+def shuffle_to_fine_grid(t, s):
+    """The fused store of bpx_conv3d_fwd_shuffle on a (B, D, H, W, 16 s^3) tensor whose channels are ordered [sub-position][16 channels]:
+    channel block (a s + b) s + e of voxel (z, y, x) goes to voxel (s z + a, s y + b, s x + e) of the (B, sD, sH, sW, 16) tensor."""
+    B, D, H, W, C = t.shape
+    Fc = C // s ** 3
+    return t.reshape(B, D, H, W, s, s, s, Fc).permute(0, 1, 4, 2, 5, 3, 6, 7).reshape(B, D * s, H * s, W * s, Fc)
+
+
+def shuffle_reference(x, w_sub, bias_sub, kind, s, rec=None, act=0):
+    """bpx_conv3d_fwd_shuffle in fp64: the conv Cin -> 16 s^3 (fwd_reference: the same sum, K = 27 Cin + 1, one rounding at the store) with
+    its reference, bound and pre-rounding bound moved together to the fine grid.  w_sub (16 s^3, Cin, 3, 3, 3) and bias_sub (16 s^3,) are in
+    the kernels' [sub-position][channel] row order (rcan_engine.rows_to_subposition_major)."""
+    ref, bound, pre = fwd_reference(x, w_sub, bias_sub, kind, rec=rec, act=act)
+    return tuple(shuffle_to_fine_grid(t, s) for t in (ref, bound, pre))
+
+
 def dgrad_reference(dy, w, kind, t=None, rec=None, act=0, out_kind=None):
     """bpx_conv3d_dgrad in fp64: g = convT(dy, W) * act'(scale t + shift).  dy, w, t stored values.  The accumulator is exact-operand
     (E = 0); M = convT(|dy|, |W|) |act'|; act' formed in fp32 on the device (E_d, module docstring) scales the accumulator, and the product
@@ -210,7 +226,8 @@ def compare(name, got, ref, bound, axes="nzyxc"):
 
 # ---- the forward route table ----------------------------------------------------------------------------------------------------------
 # Every dispatch route of bpx_conv3d_fwd / bpx_conv3d_fwd_pool (pick_cfg in conv3d_shared.h, launch_conv3 / use_lean in conv3d_igemm.hip,
-# launch_conv3_zm in conv3d_zmarch.hip).  cfg = the (tz, ty, tx, ns) tile configuration the row reaches; kinds = the storage types it runs at
+# launch_conv3_zm in conv3d_zmarch.hip), the lean kernel with more than one output-channel workgroup (blockIdx.y > 0: the *_two_blocks rows)
+# included; the third forward entry, bpx_conv3d_fwd_shuffle (the lean kernel's pixel-shuffle store), has its own table, SHUFFLE_ROWS, below.  cfg = the (tz, ty, tx, ns) tile configuration the row reaches; kinds = the storage types it runs at
 # (4x8x16 and the lean / z-march / two-K-group kernels are 16-bit only).  Hooks: ws (bpx_debug_set_conv_ws: 4 = double-buffered kernel,
 # 5 = lean kernel), kg (bpx_debug_set_conv_kg), zm (bpx_debug_set_conv_zm; the row expects the z-march kernel to run when zm != 0),
 # occ (bpx_debug_set_conv_occ: fewer persistent workgroups, so the grid wraps).  sc: 0, 1 (rank-1 image) or the 1x1 shortcut's channels.
@@ -250,6 +267,9 @@ FWD_ROUTES = [
     _r("lean4416_ns3_ws5_slice", W16, 3, (9, 17, 33), 16, 48, (4, 4, 16, 3), ws=5, layout="slice"),
     _r("lean4416_ns4_ws5", W16, 1, (9, 17, 33), 32, 64, (4, 4, 16, 4), ws=5, sc=32),
     _r("lean4816_wrap", W16, 2, (40, 48, 64), 16, 16, (4, 8, 16, 1), occ=1),
+    # lean kernel, two output-channel workgroups per tile (co_base = blockIdx.y * 16 NS > 0: weights, bias, shortcut, store and partials of block 1)
+    _r("lean4416_ns4_two_blocks", W16, 1, BIG, 16, 128, (4, 4, 16, 4)),
+    _r("lean4416_ns3_two_blocks", W16, 3, BIG, 16, 96, (4, 4, 16, 3), sc=16),
     # z-march kernels (16 output channels of the 4x8x16 tile)
     _r("zm_rolesplit", W16, 3, BIG, 16, 16, (4, 8, 16, 1), zm=2, sc=1),
     _r("zm_onechunk", W16, 1, BIG, 16, 16, (4, 8, 16, 1), zm=6),
@@ -264,6 +284,24 @@ FWD_ROUTES = [
     # the plain kernels' activation codes (use_lean refuses 4..8; ACTK = 0 for 2, 3, ACTK = 2 for the rest)
     _r(f"s448_act{a}", ALL, 1, (5, 9, 10), 16, 32, (4, 4, 8, 2), act=a) for a in range(2, 9)
 ] + [_r("s4816_gelu", W16, 1, BIG, 16, 16, (4, 8, 16, 1), act=5)]
+
+# bpx_conv3d_fwd_shuffle rows: the conv Cin -> 16 s^3 with the 3-D pixel shuffle by s fused into the lean kernel's store (conv3d_lean.hip,
+# p.ps > 1).  Cout = 128 (s 2: NS 4, 2 channel workgroups), 432 (s 3: NS 3, 9) or 1024 (s 4: NS 4, 16).  act: 0 = no prologue, else in_norm
+# records + that code.  samples: the samples that are compared (None: all of them) - the reference is built for those only.
+def _s(name, kinds, B, S, Cin, s, cfg, act=0, samples=None):
+    return dict(name=name, kinds=kinds, B=B, S=S, Cin=Cin, s=s, cfg=cfg, act=act, samples=samples)
+
+
+SHUFFLE_ROWS = [
+    _s("x2_ragged", W16, 3, BIG, 16, 2, (4, 4, 16, 4)),                       # edge tiles on every axis; sample 1 alone has the same bits
+    _s("x3_ragged", W16, 1, BIG, 16, 3, (4, 4, 16, 3)),                       # s not a power of two in the / and % of ysub
+    _s("x4_ragged", W16, 1, BIG, 16, 4, (4, 4, 16, 4)),
+    _s("x2_D3", ("bf16",), 1, (3, 100, 112), 16, 2, (4, 4, 16, 4)),           # D smaller than a tile, 33 600 voxels
+    _s("x2_silu_prologue", W16, 1, BIG, 16, 2, (4, 4, 16, 4), act=3),         # in_norm records + SiLU: admitted by the entry
+    _s("x2_cin32", ("bf16",), 1, BIG, 32, 2, (4, 4, 16, 4)),                  # x.C = 32: admitted by the entry
+    # the largest batch the size check admits at 32^3, s 4: 31 * 2^25 output elements (< 2^30), byte offsets up to just under 2^31
+    _s("x4_last_sample", ("bf16",), 31, (32, 32, 32), 16, 4, (4, 4, 16, 4), samples=(0, 30)),
+]
 
 # bpx_conv3d_bwd_fused rows (dtype, B, S, Ct, Cdy): every instance bpx_conv3d_bwd_fused_supported admits (MIX16 = 4, BF16 = 1)
 BWD_FUSED_ROWS = [(4, 3, BIG, 16, 16), (4, 1, BIG, 48, 16), (1, 1, BIG, 16, 16), (4, 1, BIG, 32, 32), (4, 1, BIG, 16, 32)]

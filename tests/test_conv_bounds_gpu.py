@@ -1,6 +1,8 @@
 """The conv kernels element by element against float64 (tests/conv_bounds.py): every forward route of bpx_conv3d_fwd / _fwd_pool at f32, bf16
-and f16, batch independence of a sample's bits, the first-layer / 1x1 / transposed-conv forwards at f16, the input gradient at f32, bf16
-and MIX16 with its S1 / S2 rows, and the fused backward's g, S1 / S2 rows, dW and db.  Each row records max(|got - ref| / bound) and the position of its worst element."""
+and f16 (the lean kernel with several output-channel workgroups included), batch independence of a sample's bits, bpx_conv3d_fwd_shuffle (the
+RCAN up-scaling stage: the lean kernel's pixel-shuffle store, inside guard bands, against the unfused launch, and what the entry refuses), the
+first-layer / 1x1 / transposed-conv forwards at f16, the input gradient at f32, bf16 and MIX16 with its S1 / S2 rows, the weight gradients (the
+up-scaling stage's 128- and 48-channel shapes of both included), and the fused backward's g, S1 / S2 rows, dW and db.  Each row records max(|got - ref| / bound) and the position of its worst element."""
 import pytest
 import torch
 
@@ -206,6 +208,119 @@ def test_conv3d_fwd_elementwise(row, kind):
     _check(rows)
 
 
+# ---- the fused conv + 3-D pixel shuffle: bpx_conv3d_fwd_shuffle ----------------------------------------------------------------------------------
+SENTINEL = 0x7FC1      # a NaN of bf16 and of f16 alike, with a payload no kernel produces: an element never written fails as non-finite
+GUARD = 4096           # elements of the guard band in front of and behind an output (8 KB: the view's base keeps the allocation's alignment)
+
+
+def _guarded(nbytes):
+    """An output of nbytes inside a larger sentinel-filled allocation: (whole int16 buffer, int16 view of the output)."""
+    n = nbytes // 2
+    buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=torch.int16, device=DEV)
+    y = buf[GUARD:GUARD + n]
+    assert y.data_ptr() % 16 == 0
+    return buf, y
+
+
+def _guards_untouched(buf):
+    return bool((buf[:GUARD] == SENTINEL).all().item() and (buf[-GUARD:] == SENTINEL).all().item())
+
+
+def _shuffle_operands(row, kind):
+    """Stored operands of a SHUFFLE_ROWS row: the weight and bias are drawn in PyTorch's [channel][sub-position] order and re-ordered the way
+    RCANEngine does it."""
+    from biapy_amd.rcan_engine import rows_to_subposition_major
+
+    B, (D, H, W), Cin, s3 = row["B"], row["S"], row["Cin"], row["s"] ** 3
+    g = torch.Generator().manual_seed(100 + len(row["name"]) + DT[kind])
+    x = CB.round_to(torch.randn(B, D, H, W, Cin, generator=g), kind)
+    w = CB.round_to(torch.randn(16 * s3, Cin, 3, 3, 3, generator=g) / (27 * Cin) ** 0.5, kind)
+    b = (torch.randn(16 * s3, generator=g) * 0.1).float()
+    wu, bu = rows_to_subposition_major(w, b, 16, s3)
+    return dict(x=x, wu=wu, bu=bu, rec=_recs(B, Cin, g) if row["act"] else None)
+
+
+def _run_shuffle(row, kind, o, lo, hi, unfused):
+    """bpx_conv3d_fwd_shuffle on samples lo..hi-1 of the operands, into a guarded view; with `unfused` also bpx_conv3d_fwd of the same operands
+    (Cout = 16 s^3, same packed weight) whose stored tensor, permuted here, must hold the same bits."""
+    L = _L()
+    lib, dt, T = L.lib, DT[kind], CB.TORCH_DT[kind]
+    (D, H, W), Cin, s = row["S"], row["Cin"], row["s"]
+    B, Cout = hi - lo, 16 * s ** 3
+    xd = o["x"][lo:hi].to(T).to(DEV).contiguous()
+    wp = _pack(o["wu"], L.PK_K3, Cin, Cout, kind)
+    bd = o["bu"].to(DEV)
+    recd = o["rec"][lo:hi].contiguous().to(DEV) if o["rec"] is not None else None
+    buf, y = _guarded(B * D * H * W * Cout * 2)
+    L.check(lib.bpx_conv3d_fwd_shuffle(dt, B, D, H, W, L.tview(xd), L.ptr(recd), row["act"], wp.data_ptr(), bd.data_ptr(), s, L.Tensor(y.data_ptr(), 16, 16, 0),
+                                       L.stream_ptr()))
+    torch.cuda.synchronize()
+    out = dict(y=y.view(T).view(B, D * s, H * s, W * s, 16), guards=_guards_untouched(buf), keep=buf)
+    if unfused:
+        yu = _nan((B, D, H, W, Cout), kind)
+        L.check(lib.bpx_conv3d_fwd(dt, B, D, H, W, L.tview(xd), L.ptr(recd), row["act"], wp.data_ptr(), bd.data_ptr(), L.NULL_T, None, None, L.tview(yu), None,
+                                   L.stream_ptr()))
+        torch.cuda.synchronize()
+        out["same_as_unfused"] = torch.equal(CB.shuffle_to_fine_grid(yu, s).contiguous().view(torch.int16), out["y"].view(torch.int16))
+    return out
+
+
+SHUFFLE_CASES = [(r, k) for r in CB.SHUFFLE_ROWS for k in r["kinds"]]
+
+
+@pytest.mark.parametrize("row,kind", SHUFFLE_CASES, ids=[f"{r['name']}-{k}" for r, k in SHUFFLE_CASES])
+def test_conv3d_fwd_shuffle_elementwise(row, kind):
+    """The RCAN up-scaling stage's forward at its own entry: every element of the (B, sD, sH, sW, 16) output against the fp64 conv moved to the
+    fine grid (conv_bounds.shuffle_reference), on volumes with edge tiles on every axis, B > 1, a prologue, 32 input channels and byte offsets
+    up to 2^31; nothing outside the output written; the same bits as the unfused lean launch, and as the sample run alone."""
+    o = _shuffle_operands(row, kind)
+    B, sel = row["B"], row["samples"]
+    got = _run_shuffle(row, kind, o, 0, B, unfused=sel is None)
+    idx = list(range(B)) if sel is None else list(sel)
+    pick = lambda t: None if t is None else t[idx].to(DEV)
+    ref, bound, _ = CB.shuffle_reference(pick(o["x"]), o["wu"].to(DEV), o["bu"].to(DEV), kind, row["s"], rec=pick(o["rec"]), act=row["act"])
+    tag = f"shuffle[{row['name']} {kind} B{B} {row['S']} {row['Cin']}->16 x{row['s']} act{row['act']}]"
+    rows = [CB.compare(tag + ".y", got["y"][idx], ref, bound)]
+    if sel is not None:      # the samples that are not compared element by element: at least written, every element
+        left = int((got["y"].view(torch.int16) == SENTINEL).sum().item())
+        rows.append(dict(name=tag + ".every_sample_written", err=float(left), tol=0.0, ok=left == 0, extra=f"elements still holding the pre-fill {left}"))
+    rows.append(dict(name=tag + ".guards_untouched", err=float(not got["guards"]), tol=0.0, ok=got["guards"], extra=""))
+    if sel is None:
+        same = got["same_as_unfused"]
+        rows.append(dict(name=tag + ".is_permutation_of_unfused", err=float(not same), tol=0.0, ok=same, extra=""))
+    if row["name"] == "x2_ragged":
+        alone = _run_shuffle(row, kind, o, 1, 2, unfused=False)
+        same = torch.equal(alone["y"][0].view(torch.int16), got["y"][1].view(torch.int16))
+        rows.append(dict(name=tag + ".sample1_alone_same_bits", err=float(not same), tol=0.0, ok=same, extra=""))
+    _check(rows)
+
+
+# (name, dtype code, N, S, Cin, s, y.C = y.ld): what bpx_conv3d_fwd_shuffle must refuse.  Every buffer has the size the call would need if it
+# were accepted (x, the packed weight and bias of 16 s^3 rows, y with its guard bands), so a missing check shows as a written y or a zero return
+# code and never as an access outside an allocation.
+SHUFFLE_REFUSALS = [("s1", 1, 1, (32, 32, 32), 16, 1, 16), ("s5", 1, 1, (32, 32, 32), 16, 5, 16), ("f32", 0, 1, (32, 32, 32), 16, 2, 16),
+                    ("yC32", 1, 1, (32, 32, 32), 16, 2, 32), ("W8", 1, 1, (64, 64, 8), 16, 2, 16), ("vol_16x32x32", 1, 1, (16, 32, 32), 16, 2, 16),
+                    ("out_2pow30", 1, 32, (32, 32, 32), 16, 4, 16)]
+
+
+@pytest.mark.parametrize("case", SHUFFLE_REFUSALS, ids=[c[0] for c in SHUFFLE_REFUSALS])
+def test_conv3d_fwd_shuffle_refuses(case):
+    L = _L()
+    lib = L.lib
+    _, dt, N, (D, H, W), Cin, s, yC = case
+    es = 4 if dt == L.F32 else 2
+    T = torch.float32 if dt == L.F32 else torch.bfloat16
+    Cout = 16 * s ** 3
+    x = torch.zeros((N, D, H, W, Cin), dtype=T, device=DEV)
+    wp = torch.zeros(max(int(lib.bpx_packed_weight_elems(L.PK_K3, Cin, Cout, dt)), (Cin // 16) * 56 * 8 * Cout), dtype=T, device=DEV)
+    bias = torch.zeros(Cout, device=DEV)
+    buf, y = _guarded(N * D * H * W * s ** 3 * yC * es)
+    rc = lib.bpx_conv3d_fwd_shuffle(dt, N, D, H, W, L.tview(x), None, 0, wp.data_ptr(), bias.data_ptr(), s, L.Tensor(y.data_ptr(), yC, yC, 0), L.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc != 0, "accepted"
+    assert bool((buf == SENTINEL).all().item()), "y or its guard bands were written"
+
+
 # ---- input gradient ------------------------------------------------------------------------------------------------------------------
 # (name, B, S, Cdy, Cg, ws, norm): the dgrad routes - 4x4x8 / 4x4x16 double-buffered, the lean kernel (hook and default size), NS 1..4
 # (name, B, S, Cdy, Cg, ws, norm, act, planar t): the dgrad routes - 4x4x8 (two K groups at >= 4 even dy chunks), 4x4x16 and 4x8x16 double-buffered,
@@ -216,7 +331,11 @@ DGRAD_ROWS = [("s448_ns1", 3, (5, 6, 7), 16, 16, 0, True, 1, False), ("s448_ns4"
               ("s4416_ns3", 3, (5, 13, 65), 16, 48, 0, True, 1, False), ("s4416_ns2_plain", 1, (9, 17, 33), 32, 32, 0, False, 1, False),
               ("s4416_ws4_silu_planar", 1, (9, 17, 33), 16, 16, 4, True, 3, True), ("lean4416_ws5_ns2", 1, (9, 17, 33), 16, 32, 5, True, 1, False),
               ("s4816_ws4_tanh", 1, CB.BIG, 16, 16, 4, True, 6, False), ("lean4816", 3, CB.BIG, 16, 16, 0, True, 1, False),
-              ("lean4816_planar", 1, CB.BIG, 32, 16, 0, True, 1, True), ("lean4416_ns3", 1, CB.BIG, 16, 48, 0, True, 1, False)]
+              ("lean4816_planar", 1, CB.BIG, 32, 16, 0, True, 1, True), ("lean4416_ns3", 1, CB.BIG, 16, 48, 0, True, 1, False),
+              # the RCAN up-scaling stage's backward (rcan_engine: blocks of 8 or 3 sub-positions = 128- / 48-channel dy into 16 channels, 8 and 3
+              # K chunks per tap, no t operand).  bf16 and mix16 (no t: the same instance) reach conv3_lp_kernel<4, 8, 16, 1, EPI_DGRAD, 0>, f32
+              # conv3_kernel<float, 4, 4, 16, 1, EPI_DGRAD, 0>
+              ("lean4816_dy128_plain", 1, CB.BIG, 128, 16, 0, False, 1, False), ("lean4816_dy48_plain", 3, CB.BIG, 48, 16, 0, False, 1, False)]
 DGRAD_CASES = [(r, m) for r in DGRAD_ROWS for m in ("f32", "bf16", "mix16")]
 
 
@@ -424,7 +543,14 @@ def test_convT_fwd_f16_elementwise(k1, S, Cin, Cout, planar):
 WGRAD_S, WGRAD_B = (9, 17, 33), 2
 WGRAD_ROWS = [("k3_tile_f32", "f32", 3, 16, 16, 1, 1), ("k3_tile_bf16", "bf16", 3, 16, 16, 3, 1), ("k3_sdm_bf16", "bf16", 3, 16, 16, 5, 1),
               ("k3_sd_ns2_bf16", "bf16", 3, 32, 32, 5, 3), ("k3_mix16", "mix16", 3, 16, 16, 5, 1), ("k3_tile_bf16_gelu", "bf16", 3, 16, 32, 3, 5),
-              ("k1_tile_bf16", "bf16", 1, 48, 16, 1, 0), ("k1_tile_f32", "f32", 1, 16, 32, 1, 1)]
+              ("k1_tile_bf16", "bf16", 1, 48, 16, 1, 0), ("k1_tile_f32", "f32", 1, 16, 32, 1, 1),
+              # the RCAN up-scaling stage's weight gradients, 16 -> 128 and 16 -> 48 (blocks of 8 and 3 sub-positions), no prologue.  pick_wcfg
+              # splits 16 -> 128 down to NS 1 (90 groups x 1 chunk x 8 co blocks = 720 >= 512 only there) and 48 is NS 1 anyway; its group count is
+              # min(T, cap, 2048 / (chunks x co blocks)) = min(90, 11574, 256 | 683) = 90.  use_tr 5: launch_wgrad_sd with ns 1 and sdm_plan mc 1
+              # (one input chunk) - wgrad_sdm_kernel<1, 0> (bf16) / <1, 0, true> (mix16), groups min(8-aligned 1024 / (8 | 3 units) = 128 | 344,
+              # cap, T) = 90.  use_tr 3: wgrad_kernel<uint16_t, 4, 4, 16, 1, 27, true, 0>, 90 groups.  G = T = 90 in every row.
+              ("k3_sdm_bf16_c128", "bf16", 3, 16, 128, 5, 0), ("k3_sdm_mix16_c128", "mix16", 3, 16, 128, 5, 0),
+              ("k3_sdm_bf16_c48", "bf16", 3, 16, 48, 5, 0), ("k3_tile_bf16_c128", "bf16", 3, 16, 128, 3, 0)]
 
 
 @pytest.mark.parametrize("row", WGRAD_ROWS, ids=[r[0] for r in WGRAD_ROWS])
@@ -456,7 +582,14 @@ def test_conv3d_wgrad_elementwise(row):
         lib.bpx_debug_set_wgrad_tr(1)
         lib.bpx_debug_set_wgrad_cap(100)
     T = B * -(-D // 4) * -(-H // 4) * -(-W // 16)
+    if k == 3:   # the workspace holds max(pick_wcfg groups, sdm_plan groups) slabs of (27 Cin + 1) Cout floats: G = T, as the chains below assume
+        assert ws.numel() == T * (27 * Cin + 1) * Cout * 4, (ws.numel(), T)
     chains = CB.wgrad_chains(T, T, 256)
+    if mode == "mix16" and rec is None:
+        # MIX16 stages the fp16 x as the bf16 MFMA operand (WgradParams.x_f16: v_cvt_pk_bf16_f32, round to nearest even).  Behind a prologue that
+        # conversion is the u_op |a| term of E_a; without one the operand is exactly the stored x rounded to bf16, which the host reproduces:
+        # the reference takes that operand and E stays 0 (the stored fp16 x itself as the operand misses by up to 2^-9 |x| per product)
+        x = CB.round_to(x, "bf16")
     ref, bound, dbr, dbb = CB.wgrad_reference(x.to(DEV), dy.to(DEV), k, "f32" if mode == "f32" else "bf16", rec=recd, act=act, chains=chains)
     tag = f"wgrad[{name} {mode} B{B} {WGRAD_S} {Cin}->{Cout} k{k} tr{use_tr} act{act}]"
     _check([CB.compare(tag + ".dw", dw, ref, bound, axes="oikyx"), CB.compare(tag + ".db", db, dbr, dbb, axes="o")])
