@@ -1,31 +1,15 @@
 // The pieces the loss kernels share (plain_losses.hip: seg / chan / softmax CE; losses.hip: Dice; n2v.hip: masked MSE), each written once and
 // inlined: no classes, no dispatch.  What differs between the families in the last bit stays apart under its own name: two sigmoid forms, two
-// orders of the four-wave sum; seg takes log(1 + en) from seg_log1p_unit, chan and Dice from log1pf.  Every kernel here runs 256 threads.
+// orders of the four-wave sum (block_sums.h); seg takes log(1 + en) from seg_log1p_unit, chan and Dice from log1pf.  Every kernel here runs 256
+// threads.
 #pragma once
 #include <algorithm>
 
+#include "block_sums.h"
 #include "bpx_common.h"
 
 // blocks per plane of the streaming sums kernels (chan, softmax CE, Dice, N2V): 1024 voxels per block, 512 blocks (= partial rows) at the most
 static inline int loss_blocks(int64_t voxels) { return (int)std::min<int64_t>(std::max<int64_t>(1, cdiv64(voxels, 1024)), 512); }
-
-// ---- a block's sums: wave shuffle, then the four waves through LDS --------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {   // every lane receives the wave's total
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-// lane 0 of each wave hands the wave's ROW sums over: red[wave][k] = v[k]; the block meets behind it
-template <int ROW> __device__ __forceinline__ void four_wave_hand_over(const float (&v)[ROW], float (&red)[4][ROW]) {
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < ROW; ++k) red[threadIdx.x >> 6][k] = v[k];
-  }
-  __syncthreads();
-}
-// the four wave values of column k: left to right (seg, chan, N2V) or in pairs (softmax CE, Dice) - fp32, the two differ in the last bit
-template <int ROW> __device__ __forceinline__ float four_wave_sum_seq(const float (&red)[4][ROW], int k) { return red[0][k] + red[1][k] + red[2][k] + red[3][k]; }
-template <int ROW> __device__ __forceinline__ float four_wave_sum_pairs(const float (&red)[4][ROW], int k) { return (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]); }
 
 // ---- per element: p = sigmoid(z) and en = exp(-|z|) with it; BCE with logits = max(z, 0) - z t + log(1 + en) ------------------------------
 // one reciprocal, the negative side a product (seg sums, Dice) | a division on either side (seg backward, chan): they round differently

@@ -1647,7 +1647,7 @@ int run_wgrad(const char* fn, int dtype, WgradParams& p, int taps, void* ws, int
 
 }  // namespace
 
-// for the small weight-gradient kernels of elementwise.hip (first layer, rank-1 shortcut, head): the same fixed-order reduction of
+// for the small weight-gradient kernels of ends.hip (first layer, rank-1 shortcut, head) and the pool backward's rank-1 tail: the same fixed-order reduction of
 // per-workgroup partials, queued with the others while the deferred mode is on
 namespace bpxred {
 int reduce_partials(const char* fn, const float* part, float* dw, int groups, int taps, int Cin, int Cout, int64_t si, int64_t sj, int64_t st,

@@ -1,6 +1,6 @@
-"""Element-wise error bounds for the kernels at the two ENDS of a network in biapy_amd/csrc/elementwise.hip - the dropout pair
-(bpx_norm_act_dropout_fwd / _bwd), the output head (bpx_head_fwd / _bwd) and the first layer's weight gradients (bpx_conv3d_c1_wgrad, _nb,
-bpx_conv1x1_c1_wgrad) - in the form of tests/conv_bounds.py, tests/norm_bounds.py and tests/gate_bounds.py, whose comparator, rounding helpers,
+"""Element-wise error bounds for the kernels at the two ENDS of a network - the dropout pair (bpx_norm_act_dropout_fwd / _bwd) of
+biapy_amd/csrc/elementwise.hip, the output head (bpx_head_fwd / _bwd) and the first layer's weight gradients (bpx_conv3d_c1_wgrad, _nb,
+bpx_conv1x1_c1_wgrad) of ends.hip - in the form of tests/conv_bounds.py, tests/norm_bounds.py and tests/gate_bounds.py, whose comparator, rounding helpers,
 activation terms and partial-sum bound are reused:
 
     |got - ref| <= u_out |ref| + (1 + u_out) (E + K 2^-24 M) + floor          (conv_bounds.finish)
@@ -249,9 +249,9 @@ def head_bwd_reference(x, w, dout, mode, db_init):
 
 # ---- the first layer's weight gradients -----------------------------------------------------------------------------------------------------
 def c1_plan(kernel, N, D, H, W, persist=0):
-    """(tile extents (tz, ty, tx), tiles, workgroup columns = partial rows) of c1_wgrad_impl: the scalar kernel walks 4 x 8 x 8 tiles over
-    min(tiles, 1024) columns, the MFMA kernel 4 x 4 x 16 tiles over min(tiles, 768, bpx_debug_set_c1_persist's cap) persistent workgroups."""
-    t = (4, 8, 8) if kernel == "scalar" else (4, 4, 16)
+    """(tile extents (tz, ty, tx), tiles, workgroup columns = partial rows) of c1_wgrad_impl (ends.hip): N C1ScalarTile::tiles(D, H, W) over
+    min(tiles, 1024) columns, or N C1MfmaTile::tiles(D, H, W) over min(tiles, 768, bpx_debug_set_c1_persist's cap) persistent workgroups."""
+    t = (4, 8, 8) if kernel == "scalar" else (4, 4, 16)        # C1ScalarTile, C1MfmaTile
     tiles = N * cdiv(D, t[0]) * cdiv(H, t[1]) * cdiv(W, t[2])
     rows = min(tiles, WG_ROWS) if kernel == "scalar" else min(tiles, C1_MFMA_WGS, persist if persist > 0 else tiles)
     return t, tiles, rows

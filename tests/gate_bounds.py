@@ -1,4 +1,4 @@
-"""Element-wise error bounds for the gate, channel-affine and 1-channel up-sampling kernels of biapy_amd/csrc/elementwise.hip - the hot path
+"""Element-wise error bounds for the gate and channel-affine kernels of biapy_amd/csrc/elementwise.hip and the 1-channel up-sampling kernels of ends.hip - the hot path
 of the RCAN trunk, of ResUNet++'s squeeze-excite and attention blocks and of ResUNet's super-resolution "pre" path - in the form of
 tests/conv_bounds.py and tests/norm_bounds.py, whose comparator, rounding helpers, activation terms and partial-sum bound are reused:
 

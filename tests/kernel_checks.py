@@ -1243,7 +1243,7 @@ def check_planar_layouts(dt, S=(8, 16, 32), lean=False):
 def check_parameter_gradients_are_reproducible(dtype):
     """No atomics anywhere in the parameter gradients: conv / transposed-conv bias gradients are column sums of
     per-workgroup partials combined in a fixed order (wgrad.hip), the first layer, the rank-1 shortcut and the head likewise
-    (elementwise.hip).  Two backward passes over the same tensors give bit-identical gradients for EVERY parameter."""
+    (ends.hip).  Two backward passes over the same tensors give bit-identical gradients for EVERY parameter."""
     from biapy_amd.resunet import ResUNet
 
     torch.manual_seed(0)

@@ -153,7 +153,7 @@ def _isa(src: str, tmp_path_factory) -> str:
 def test_head_kernels_use_no_scratch(tmp_path_factory):
     """Every instance of the head kernels (forward: 3 types x 2 widths x Cout 1..8; backward: the Cout <= 4 kernel and the channel-sliced Cout 5..8
     kernel) keeps its accumulators in registers."""
-    text = _isa("elementwise", tmp_path_factory)
+    text = _isa("ends", tmp_path_factory)
     found = {}
     for m in re.finditer(r"^\s+\.name:\s+(\S+)\s*\n\s+\.private_segment_fixed_size:\s+(\d+)", text, re.M):
         if re.search(r"head_(fwd|bwd|bwd_slice)_kernel", m.group(1)):

@@ -1,4 +1,4 @@
-"""The dropout pair, the output head and the first layer's weight gradients of elementwise.hip element by element against float64
+"""The dropout pair of elementwise.hip, the output head and the first layer's weight gradients of ends.hip element by element against float64
 (tests/ends_bounds.py): bpx_norm_act_dropout_fwd / _bwd (the mask bit for bit against a host Philox4x32-10), bpx_head_fwd / _bwd, bpx_conv3d_c1_wgrad,
 bpx_conv3d_c1_wgrad_nb and bpx_conv1x1_c1_wgrad.  Every output is pre-filled with NaN, the padding of every input row and output stride holds NaN
 or a sentinel that must keep its value, every backward runs twice and must give the same bits, and each row records max(|got - ref| / bound)

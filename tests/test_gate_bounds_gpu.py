@@ -1,6 +1,6 @@
-"""The gate, channel-affine and 1-channel up-sampling kernels of elementwise.hip element by element against float64 (tests/gate_bounds.py):
-bpx_channel_affine, bpx_dot_stats, bpx_gate_mul_fwd / _bwd (bit for bit), bpx_upsample_c1_fwd / _bwd and bpx_gate_mlp_fwd / _bwd.  Every output
-is pre-filled with NaN, carries one sentinel voxel or row past its end that must keep its value, sliced buffers are checked for untouched
+"""The gate and channel-affine kernels of elementwise.hip and the 1-channel up-sampling kernels of ends.hip element by element against float64
+(tests/gate_bounds.py): bpx_channel_affine, bpx_dot_stats, bpx_gate_mul_fwd / _bwd (bit for bit), bpx_upsample_c1_fwd / _bwd and
+bpx_gate_mlp_fwd / _bwd.  Every output is pre-filled with NaN, carries one sentinel voxel or row past its end that must keep its value, sliced buffers are checked for untouched
 neighbours, and each row records max(|got - ref| / bound) with the position of its worst element."""
 import math
 

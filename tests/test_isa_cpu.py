@@ -48,8 +48,8 @@ def pointwise_isa(tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
-def elementwise_isa(tmp_path_factory):
-    return _isa("elementwise", tmp_path_factory)
+def ends_isa(tmp_path_factory):
+    return _isa("ends", tmp_path_factory)
 
 
 def _loops(text: str, name_pattern: str):
@@ -94,14 +94,14 @@ def test_transposed_conv_one_k_step_kernel_waits_with_counts_only(pointwise_isa)
         assert waits and min(waits) >= 8, (name, waits)              # the stores of at least one whole block stay in flight at every wait
 
 
-def test_first_layer_buffer_instances_wait_with_counts_only(elementwise_isa):
-    fwd = _loops(elementwise_isa, r"conv_c1_fwd_kernelI\w+Lb1E")
+def test_first_layer_buffer_instances_wait_with_counts_only(ends_isa):
+    fwd = _loops(ends_isa, r"conv_c1_fwd_kernelI\w+Lb1E")
     assert len(fwd) == 3, [k for k, _ in fwd]                       # bf16, fp16, fp32 storage
     for name, loops in fwd:
         reg = _main_loop(loops)
         assert any("buffer_store" in l for l in reg) and any("buffer_load_dword " in l for l in reg), name
         assert not any("s_waitcnt vmcnt(0)" in l for l in reg), f"{name}: the tile loop waits for the previous tile's stores again"
-    wg = _loops(elementwise_isa, r"conv_c1_wgrad_mfma_kernelI\w+Lb1ELb1E")
+    wg = _loops(ends_isa, r"conv_c1_wgrad_mfma_kernelI\w+Lb1ELb1E")
     assert len(wg) == 2, [k for k, _ in wg]                         # t as fp16 (mixed mode) and bf16, IN-backward folded in, buffer-addressed
     for name, loops in wg:
         reg = _main_loop(loops)
